@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the rasterizer hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--views V]
+    python bench.py --gpus N --steps K --warmup W [--views V] [--full] [--dump-outputs DIR]
     (N > 1: launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`, or started plainly:
-     without WORLD_SIZE in the environment `--gpus N` re-executes itself under torch.distributed.run with N ranks on
+     without WORLD_SIZE in the environment `--gpus N` runs itself as a child under torch.distributed.run with N ranks on
      127.0.0.1, and refuses to run if fewer than N GPUs are visible -- it never reports n_gpus = 1 for --gpus N)
 
 Workload (BASELINE.json metric, config C4): synth-v1 scene, 1,000,000 Gaussians, SH degree 3
@@ -15,11 +15,17 @@ reference's own batch loop (threestudio/systems/GassuianEditor.py:165-207), bit-
 A step = forward + backward of this rank's view(s) through the drop-in L1 API + the gradient
 exchange (SUM over the views, MAX over radii); inputs are resident in HBM.
 
-One JSON line is printed by rank 0: the train rate is `value`; the forward-only rate (renders/s, Mpixels/s), the
-per-stage GPU times, the roofline block of the dominant stage (section 8(d) bytes, the compulsory-byte model, counter
-traffic and VALU issue share), the other BASELINE configurations (`extra_configs`: 6 M forward, the 512^2 edit loop,
-tracing) and the CPU baselines ride along in the same object; N > 1 lines add `multi_gpu` (per-rank step times, exchange
-time and bytes, route, RCCL version).
+One JSON line is printed by rank 0: the train rate is `value`, the wall time of one timed step `ms_per_step`; N > 1 lines
+add `multi_gpu` (per-rank step times, exchange time and bytes, route, RCCL version).  A plain run does only that: set up,
+warm up, time the `--steps` steps, write the outputs (`--dump-outputs`) and print the line.  `--full` adds the
+measurements that take runs of their own: the forward-only rate (renders/s, Mpixels/s), the per-stage GPU times, the
+roofline block of the dominant stage (section 8(d) bytes, the compulsory-byte model, counter traffic and VALU issue share),
+the other BASELINE configurations (`extra_configs`: 6 M forward, the 512^2 edit loop, tracing) and the CPU baselines.
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller (image, depth, radii and the exchanged
+gradients of rank 0) as DIR/<name>.npy in float32; an array larger than its share of the 48 MiB budget is replaced by a
+fixed, seeded sample of its elements (the same indices for the same shape in every run; the line's `dumped_outputs` says
+which).  The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -79,8 +85,10 @@ def compulsory_bytes(P, V, R, N, T, M):
 
 
 def self_launch(n: int) -> None:
-    """`python bench.py --gpus N` without a launcher: become `torch.distributed.run` with N ranks (one per GPU)."""
+    """`python bench.py --gpus N` without a launcher: run `torch.distributed.run` with N ranks (one per GPU) as a child
+    process and exit with its status.  (A child, not an exec: this process may already have initialised the GPU runtime.)"""
     import socket
+    import subprocess
 
     have = torch.cuda.device_count() if torch.cuda.is_available() else 0
     if have < n:
@@ -91,7 +99,7 @@ def self_launch(n: int) -> None:
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    raise SystemExit(subprocess.call(cmd))
 
 
 def percentile(xs, q):
@@ -101,6 +109,39 @@ def percentile(xs, q):
     i = q * (len(xs) - 1)
     lo, hi = int(math.floor(i)), int(math.ceil(i))
     return xs[lo] + (xs[hi] - xs[lo]) * (i - lo)
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs: all files together (float32)
+
+
+def dump_outputs(path, arrays, budget_bytes=DUMP_BUDGET_BYTES):
+    """Write `arrays` (name -> tensor, any device) as path/<name>.npy in float32.  The budget is dealt out smallest array
+    first; an array larger than its share is replaced by a sample of its flattened elements at sorted, unique indices drawn
+    from a generator seeded by the array's name and shape -- the same elements in every run.  -> what was written, per name."""
+    import zlib
+
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    left = budget_bytes // 4
+    items = sorted(((k, v) for k, v in arrays.items() if v is not None), key=lambda kv: kv[1].numel())
+    written = {}
+    for i, (name, t) in enumerate(items):
+        share = left // (len(items) - i)
+        flat = t.detach().reshape(-1)
+        entry = {"shape": list(t.shape), "source_dtype": str(t.dtype).replace("torch.", "")}
+        if flat.numel() > share:
+            seed = zlib.crc32(f"{name}:{tuple(t.shape)}".encode())
+            idx = np.unique(np.random.default_rng(seed).integers(0, flat.numel(), size=share, dtype=np.int64))
+            flat = flat.index_select(0, torch.from_numpy(idx).to(flat.device))
+            entry["sampled"] = {"elements": int(idx.size), "of": int(t.numel()), "seed": seed}
+        a = flat.to(torch.float32).cpu().numpy()
+        if "sampled" not in entry:
+            a = a.reshape(tuple(t.shape))
+        np.save(os.path.join(path, f"{name}.npy"), a)
+        left -= a.size
+        written[name] = entry
+    return written
 
 
 def csrc_sha16() -> str:
@@ -662,11 +703,19 @@ def main():
                     help="v1 = synth-v1, the uniform cube of SURVEY.md section 8(d) (the headline); v2 = synth-v2, surfaces of "
                          "disk-like Gaussians with bimodal opacity seen from inside (every tile non-empty, most visible "
                          "Gaussians receive a gradient: gaussianeditor_amd/synth.py)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-configs", action="store_true", help="skip the `extra_configs` block (6 M forward, edit loop, tracing)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what needs runs of its own: forward-only rate, per-stage times and "
+                         "roofline, CPU baselines, `extra_configs` (default: only the timed train steps and the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (image, depth, radii, exchanged gradients) as DIR/<name>.npy "
+                         "in float32, at most 48 MiB in all (larger arrays as a fixed, seeded sample of their elements)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extra-configs", action="store_true",
+                    help="with --full: skip the `extra_configs` block (6 M forward, edit loop, tracing)")
     ap.add_argument("--train-only", action="store_true",
                     help="profiling runs (tools/gpu_counters.sh): only the warm-up and the timed train iterations, nothing else "
-                         "is launched -- every kernel launch of the process belongs to a train iteration")
+                         "is launched -- every kernel launch of the process belongs to a train iteration (a plain run without "
+                         "--full is the same; with --full this keeps the extra measurements off)")
     ap.add_argument("--cpu-iters", type=int, default=15, help="oracle train iterations timed for cpu_baseline")
     ap.add_argument("--ply", type=str, default=None,
                     help="a 3DGS point cloud in the reference's save_ply layout (gaussiansplatting/scene/gaussian_model.py:"
@@ -687,7 +736,7 @@ def main():
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
-        self_launch(args.gpus)  # does not return
+        self_launch(args.gpus)  # does not return (exits with the child's status)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     # The contract: rank 0 prints ONE JSON line.  RCCL writes a version banner to the process's stdout through C stdio (it
@@ -800,20 +849,22 @@ def main():
     rows_env = os.environ.get("GSR_BENCH_ROWS")
     rows_mode = "auto" if rows_env is None else (rows_env == "1")
     marks_log = []
+    last = {}  # what the latest step returned (references only: kept for --dump-outputs)
 
     def train_step(record=False, marks=None):
         if record and marks is None:
             marks = {}
         if batch_mode:
             # the fixed batch: this rank's block of views, one message per view, one all-gather (multiview_batch_step)
-            _, radii, _, _ = multiview_batch_step(rs_list, params, [G] * len(rs_list), bucket, marks=marks)
+            color, radii, depth, _ = multiview_batch_step(rs_list, params, [G] * len(rs_list), bucket, marks=marks)
         else:
             # forward, radii MAX all-reduce started, backward, gradient exchange (gaussianeditor_amd/multiview.py)
-            _, radii, _, _ = multiview_step(rs, params, G, bucket, rows=True if args.force_exchange else rows_mode,
-                                            force_exchange=args.force_exchange, marks=marks)
+            color, radii, depth, _ = multiview_step(rs, params, G, bucket, rows=True if args.force_exchange else rows_mode,
+                                                    force_exchange=args.force_exchange, marks=marks)
         route["last"] = bucket.last_route
         if record:
             marks_log.append(marks)
+        last.update(color=color, radii=radii, depth=depth)
         return radii
 
     exchange = bucket.sh_exchange
@@ -856,6 +907,20 @@ def main():
     step_ms = [step_ev[i].elapsed_time(step_ev[i + 1]) for i in range(args.steps)]
     local_ms = [step_ev[i].elapsed_time(m["local_done"]) for i, m in enumerate(marks_log) if m and "local_done" in m]
     exch_ms = [m["local_done"].elapsed_time(m["step_done"]) for m in marks_log if m and "step_done" in m]
+
+    # ---------------- --dump-outputs: what the last timed step handed its caller (rank 0) ----------------
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        if args.steps < 1:
+            raise SystemExit("--dump-outputs needs at least one timed step")
+        arrays = {"radii": last["radii"]}
+        if batch_mode:
+            for v, c, d in zip(my_views, last["color"], last["depth"]):
+                arrays[f"color_view{v}"], arrays[f"depth_view{v}"] = c, d
+        else:
+            arrays["color"], arrays["depth"] = last["color"], last["depth"]
+        arrays.update({f"grad_{k}": t for k, t in bucket.grads().items()})
+        dumped = dump_outputs(args.dump_outputs, arrays)
 
     # ---------------- multi-GPU diagnostics: every rank's view of the step ----------------
     multi_gpu = None
@@ -905,7 +970,9 @@ def main():
 
     fwd_s, fwd_ms = None, []
     stage_ms, ab, cb, R, V, pix_inst, k7_info = {}, {}, {}, 0, 0, 0, {}
-    if not args.train_only:
+    # everything below the timed steps except the line itself needs --full (a plain run is timed steps + line only)
+    extras = args.full and not args.train_only
+    if extras:
         # ---------------- forward only ----------------
         rast = GaussianRasterizer(rs)
         m2d = torch.zeros_like(params["xyz"])
@@ -939,7 +1006,7 @@ def main():
     # oracle's OpenMP runtime on a 256-thread host oversubscribes it into a crawl) with a hard timeout, blends every 8th
     # non-empty tile and scales the blend time up (anchor, measured once in full: profiles/r04_a_torch_cpu_full.md).
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.train_only:
+    if rank == 0 and world == 1 and not args.no_cpu_baseline and extras:
         from oracle import cpu as O
 
         cam0 = cam
@@ -1001,7 +1068,7 @@ def main():
     # (only next to the headline workload: a bench line of another workload -- tests, --ply, deep tiles -- stays short)
     is_headline = (args.ply is None and args.scene == "v1" and (P, W, H) == (1_000_000, 1920, 1080) and args.s0 == 0.01
                    and not batch_mode)
-    if rank == 0 and world == 1 and is_headline and not (args.no_extra_configs or args.train_only or args.force_exchange):
+    if rank == 0 and world == 1 and is_headline and extras and not (args.no_extra_configs or args.force_exchange):
         del bucket
         torch.cuda.empty_cache()
         extra = extra_configs(dev, flags)
@@ -1020,6 +1087,7 @@ def main():
                             "first": step_ms[0] if step_ms else None, "max": max(step_ms) if step_ms else None,
                             "note": "HIP events around every timed step on the launch stream of rank 0"},
             "prewarm_steps": max(args.prewarm, 0),
+            "full": bool(args.full),
             "higher_is_better": True,
             "scaling": "strong" if batch_mode else "weak",
             "vs_baseline": None,
@@ -1051,7 +1119,9 @@ def main():
         }
         if multi_gpu is not None:
             out["multi_gpu"] = multi_gpu
-        if not args.train_only:
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+        if extras:
             renders_per_s = world * args.steps / fwd_s
             dominant = max(stage_ms, key=stage_ms.get)
             counters, src = (load_counters(workload_key(P, W, H, args.s0, args.scene)) if args.ply is None

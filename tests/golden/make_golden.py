@@ -10,6 +10,10 @@ modules (only possible where /root/reference exists; the fixtures themselves are
                   `GaussianModel.get_near_gaussians_by_mask` (scene/gaussian_model.py:865-898; the method's source is
                   compiled out of the reference file and run on a stub holding `_xyz`, so none of the module's GPU-only
                   imports are needed) -> pins the oracle's near_points / get_near_gaussians_by_mask
+    near_method.npz  the same method of the reference on two more seeded clouds (tests/test_cpu_near.py)
+    reference_{render,point_cloud_render,optimizer_surgery}.npz, reference_save_ply.ply
+                  the reference's render / point_cloud_render / camera2rasterizer, optimizer surgery and save_ply run as
+                  written on the drop-in (tests/test_cpu_reference_modules.py holds the functions that ran them)
 """
 import ast
 import importlib.util
@@ -71,6 +75,8 @@ def main():
     np.savez(os.path.join(HERE, "cameras.npz"), **cams)
     print("wrote", os.path.join(HERE, "sh_eval.npz"), os.path.join(HERE, "cameras.npz"))
     near_points_fixture()
+    near_method_fixture()
+    reference_modules_fixtures()
 
 
 def reference_method(path, name, globs):
@@ -112,6 +118,74 @@ def near_points_fixture():
     out["nn_dist"], out["nn_idx"] = dist.numpy(), idx.numpy()
     np.savez_compressed(os.path.join(HERE, "near_points.npz"), **out)
     print("wrote", os.path.join(HERE, "near_points.npz"), {k: int(out[k].sum()) for k in ("mask", "near0", "near1", "near2")})
+
+
+NEAR_METHOD_CASES = ((2000, 0.1), (5000, 0.04))
+
+
+def near_method_inputs():
+    """-> [(xyz, mask, dist_thresh)] of near_method.npz: seeded, regenerated by tests/test_cpu_near.py."""
+    rng = np.random.default_rng(5)
+    cases = []
+    for n, th in NEAR_METHOD_CASES:
+        xyz = (rng.standard_normal((n, 3)) * 0.6).astype(np.float32)
+        cases.append((xyz, np.linalg.norm(xyz, axis=1) < 0.5, th))
+    return cases
+
+
+def near_method_fixture():
+    """near_method.npz: the reference's `get_near_gaussians_by_mask` on the seeded clouds of near_method_inputs()."""
+    knn = load(os.path.join(REF, "knn.py"), "ref_knn")
+    fn = reference_method(os.path.join(REF, "scene", "gaussian_model.py"), "get_near_gaussians_by_mask",
+                          {"torch": torch, "K_nearest_neighbors": knn.K_nearest_neighbors})
+    out = {}
+    for i, (xyz, mask, th) in enumerate(near_method_inputs()):
+        class Stub:
+            _xyz = torch.from_numpy(xyz)
+
+        out[f"near{i}"] = fn(Stub(), torch.from_numpy(mask)[:, None], dist_thresh=th).numpy()
+    np.savez_compressed(os.path.join(HERE, "near_method.npz"), **out)
+    print("wrote", os.path.join(HERE, "near_method.npz"), {k: int(v.sum()) for k, v in out.items()})
+
+
+def reference_modules_fixtures():
+    """reference_{render,point_cloud_render,optimizer_surgery}.npz + reference_save_ply.ply: the reference's render / point_cloud_render / camera2rasterizer,
+    GaussianModel.cat_tensors_to_optimizer / _prune_optimizer and GaussianModel.save_ply, imported unmodified after
+    gaussianeditor_amd.install() and run on the drop-in (native calls routed to the oracle, tests/oracle_backend.py) by the
+    functions of tests/test_cpu_reference_modules.py."""
+    import pytest
+
+    tests = os.path.dirname(HERE)
+    for p in (os.path.dirname(tests), tests):
+        if p not in _sys.path:
+            _sys.path.insert(0, p)
+    import oracle_backend
+    import test_cpu_reference_modules as T
+
+    import gaussianeditor_amd
+    from oracle import cpu
+
+    cpu.build()
+    gaussianeditor_amd.install()
+    with pytest.MonkeyPatch.context() as mp:
+        mp.syspath_prepend(os.path.dirname(REF))
+        import gaussiansplatting.gaussian_renderer as ref_renderer  # the reference's file, unmodified
+        from gaussiansplatting.scene.gaussian_model import GaussianModel
+
+        assert ref_renderer.GaussianRasterizer is _sys.modules["gaussianeditor_amd.diff_gaussian_rasterization"].GaussianRasterizer
+        T.cpu_zeros_like(mp)
+        oracle_backend.install(mp)
+        out = T.render_outputs(ref_renderer.render, ref_renderer.camera2rasterizer)
+        out.update(T.point_cloud_outputs(ref_renderer.point_cloud_render))
+        out.update(T.surgery_outputs(GaussianModel.cat_tensors_to_optimizer, GaussianModel._prune_optimizer))
+        gm = GaussianModel.__new__(GaussianModel)
+        for k, t in T.ply_model().items():
+            setattr(gm, k, t)
+        gm.save_ply(T.PLY_FIXTURE)
+    for path, prefixes in T.FIXTURES.items():
+        np.savez_compressed(path, **{k: v for k, v in out.items() if k.startswith(prefixes)})
+    assert all(k.startswith(sum(T.FIXTURES.values(), ())) for k in out)  # (every array went into one of the files)
+    print("wrote", *T.FIXTURES, T.PLY_FIXTURE)
 
 
 if __name__ == "__main__":

@@ -74,3 +74,29 @@ def test_roofline_block_arithmetic(monkeypatch):
     assert rf["pixel_instances_per_s"] == pytest.approx(97_394_339 / 0.2e-3) and "limiter" in rf
     none = bench.roofline_block(st, ab, cb, "preprocess", None, "stale: ...", "cuda:0", 0)
     assert none["traffic"] is None and none["frac_counter"] is None and "limiter" not in none and 0 < none["frac"] < 1
+
+
+def test_dump_outputs_stays_in_budget_and_samples_the_same_elements_every_time(tmp_path):
+    """--dump-outputs: float32 files, the whole set within the budget, small arrays whole and in shape, large ones sampled
+    at the same indices in every run (two builds are compared element for element)."""
+    import numpy as np
+    import torch
+
+    g = torch.Generator().manual_seed(0)
+    arrays = {"color": torch.rand(3, 300, 400, generator=g), "radii": torch.randint(0, 9, (5000,), generator=g, dtype=torch.int32),
+              "grad_sh": torch.randn(20000, 16, 3, generator=g), "missing": None}
+    budget = 1 << 20
+    runs = []
+    for d in ("a", "b"):
+        w = bench.dump_outputs(str(tmp_path / d), arrays, budget_bytes=budget)
+        assert set(w) == {"color", "radii", "grad_sh"}
+        files = {n: np.load(tmp_path / d / f"{n}.npy") for n in w}
+        assert all(a.dtype == np.float32 for a in files.values())
+        assert sum(os.path.getsize(tmp_path / d / f"{n}.npy") for n in w) <= budget + 3 * 128  # (+ .npy headers)
+        runs.append(files)
+    assert runs[0]["radii"].shape == (5000,) and np.array_equal(runs[0]["radii"], arrays["radii"].numpy())
+    assert "sampled" in w["grad_sh"] and "sampled" in w["color"]
+    for n in runs[0]:
+        assert np.array_equal(runs[0][n], runs[1][n]), n
+    flat = arrays["grad_sh"].reshape(-1).numpy()
+    assert np.isin(runs[0]["grad_sh"], flat).all()  # sampled elements, not a reduction

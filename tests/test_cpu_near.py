@@ -1,7 +1,7 @@
 """CPU: the Delete path's neighbour query.  The oracle's restatement of
 GaussianModel.get_near_gaussians_by_mask / K_nearest_neighbors (gaussiansplatting/scene/gaussian_model.py:865-898,
 gaussiansplatting/knn.py) against the fixture produced by running the reference's own code (tests/golden/make_golden.py),
-against scipy's KDTree directly, and -- where /root/reference exists -- against the reference's method run live."""
+against scipy's KDTree directly, and against the reference's method as recorded on two more seeded clouds (near_method.npz)."""
 import ctypes
 import os
 
@@ -53,30 +53,20 @@ def test_oracle_near_points_edges(oracle):
     assert near.tolist() == [True, False]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/gaussiansplatting"), reason="the reference checkout is only in the development container")
 def test_oracle_matches_reference_method_live(oracle):
+    """The reference's `get_near_gaussians_by_mask` as recorded by tests/golden/make_golden.py (near_method.npz) on two more
+    seeded clouds, against the oracle."""
     import importlib.util
     import sys
-
-    import torch
 
     sys.dont_write_bytecode = True
     spec = importlib.util.spec_from_file_location("make_golden", os.path.join(os.path.dirname(GOLD), "make_golden.py"))
     mg = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mg)
-    knn = mg.load(os.path.join(mg.REF, "knn.py"), "ref_knn")
-    fn = mg.reference_method(os.path.join(mg.REF, "scene", "gaussian_model.py"), "get_near_gaussians_by_mask",
-                             {"torch": torch, "K_nearest_neighbors": knn.K_nearest_neighbors})
-    rng = np.random.default_rng(5)
-    for n, th in ((2000, 0.1), (5000, 0.04)):
-        xyz = (rng.standard_normal((n, 3)) * 0.6).astype(np.float32)
-        mask = np.linalg.norm(xyz, axis=1) < 0.5
-
-        class Stub:
-            _xyz = torch.from_numpy(xyz)
-
-        want = fn(Stub(), torch.from_numpy(mask)[:, None], dist_thresh=th).numpy()
-        assert np.array_equal(oracle.get_near_gaussians_by_mask(xyz, mask, th), want) and want.any()
+    with np.load(os.path.join(os.path.dirname(GOLD), "near_method.npz")) as z:
+        for i, (xyz, mask, th) in enumerate(mg.near_method_inputs()):
+            want = z[f"near{i}"]
+            assert np.array_equal(oracle.get_near_gaussians_by_mask(xyz, mask, th), want) and want.any()
 
 
 def test_abi_near_points_argument_checks():

@@ -94,7 +94,7 @@ def test_scene_from_ply_renders_like_the_oracle_and_benches(oracle, tmp_path):
     assert np.array_equal(radii.cpu().numpy(), f["radii"]) and np.array_equal(color.cpu().numpy(), f["color"])
     assert np.array_equal(depth.cpu().numpy(), f["depth"])
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--ply", path, "--steps", "3", "--warmup", "1", "--width", "640",
-                        "--height", "360", "--no-cpu-baseline"], cwd=ROOT, capture_output=True, text=True, timeout=600)
+                        "--height", "360", "--full", "--no-cpu-baseline"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["config"]["gaussians"] == 30000 and "point_cloud.ply" in line["config"]["workload"] and line["value"] > 0
@@ -217,7 +217,7 @@ def test_bench_line_carries_the_contract_fields_and_the_gradient_row_mode():
 
     for extra, word in (([], "every row"), (["--persistent-grads"], "persistent")):
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gaussians", "50000", "--steps", "5", "--warmup", "2",
-                            "--no-cpu-baseline"] + extra, capture_output=True, text=True, timeout=600, cwd=ROOT,
+                            "--full", "--no-cpu-baseline"] + extra, capture_output=True, text=True, timeout=600, cwd=ROOT,
                            env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
         assert p.returncode == 0, p.stderr[-2000:]
         line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])

@@ -140,7 +140,7 @@ def test_batch_step_on_the_gpu_equals_the_sequential_single_process_sums(monkeyp
 def test_default_bench_line_carries_extra_configs_and_both_roofline_fractions():
     """VERDICT r03 items 4 + 5: the default line (headline workload) reports the compulsory-byte fraction next to section
     8(d)'s, pixel-instances/s for the blend kernel that dominates, and an `extra_configs` block with C2 / C3 / C5."""
-    line = _bench(["--steps", "20", "--warmup", "5", "--no-cpu-baseline"], timeout=1200)
+    line = _bench(["--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline"], timeout=1200)
     rf = line["roofline"]
     assert set(rf) >= {"bound", "achieved", "peak", "unit", "frac", "traffic", "frac_8d", "frac_compulsory", "frac_counter",
                        "valu_issue_frac"}

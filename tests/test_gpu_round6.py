@@ -476,3 +476,42 @@ def test_apply_weights_grouped_loop_edges(oracle, C, W, H, s0, opaque):
     assert np.abs(got_w[ok] - w_ref[ok]).max() <= 2e-5 * max(1.0, float(np.abs(w_ref[ok]).max()))
     if opaque:  # the scene does what it is here for: most Gaussians in the frustum are hidden behind saturated pixels
         assert (c_ref > 0).sum() < 0.5 * P
+
+
+def test_plain_bench_run_is_lean_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps steps and prints the line without the extra measurements;
+    --dump-outputs writes what the last timed step returned, and two runs with the same arguments get the same inputs: the
+    forward outputs agree bit for bit, the gradients to the blend backward's run-to-run spread (atomics)."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    outs = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--gaussians", "50000", "--width", "640",
+                            "--height", "368", "--steps", "4", "--warmup", "1", "--prewarm", "2", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600, cwd=root, env=env)
+        assert p.returncode == 0, p.stderr[-2000:]
+        line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == 4 and line["ms_per_step"] > 0 and line["value"] > 0 and line["full"] is False
+        for key in ("roofline", "stage_ms", "forward_ms", "cpu_baseline", "extra_configs"):
+            assert key not in line, key
+        names = set(line["dumped_outputs"]["arrays"])
+        assert {"color", "depth", "radii", "grad_means3D", "grad_sh", "grad_opacities", "grad_scales", "grad_rotations",
+                "grad_means2D"} <= names
+        files = {n: np.load(d / f"{n}.npy") for n in names}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in files.values())
+        assert sum(os.path.getsize(d / f"{n}.npy") for n in names) <= 64 << 20
+        assert files["color"].shape == (3, 368, 640) and float(np.abs(files["grad_means3D"]).max()) > 0
+        outs.append(files)
+    for n in ("color", "depth", "radii"):
+        assert np.array_equal(outs[0][n], outs[1][n]), n
+    for n in outs[0]:
+        a, b = outs[0][n], outs[1][n]
+        assert a.shape == b.shape and float(np.abs(a - b).max()) <= 1e-4 * max(1.0, float(np.abs(b).max())), n

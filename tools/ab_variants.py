@@ -2,7 +2,7 @@
 
     python tools/ab_variants.py [--steps 100] [--smoke] name[=ENV=VAL,ENV=VAL...][@lib] ...
 
-Each configuration runs `bench.py --no-cpu-baseline` in a fresh process (the library is loaded once per process):
+Each configuration runs `bench.py --full --no-cpu-baseline` in a fresh process (the library is loaded once per process):
 `@lib` selects build_variants/libgsr_<lib>.so through GSR_LIBRARY_PATH (default: the in-tree library), `ENV=VAL` pairs
 are added to the environment.  `--smoke` first checks every configuration against the oracle
 (`__graft_entry__.smoke()`), so a variant that miscompiles is not timed.  Prints one table; every JSON line goes to
@@ -64,7 +64,7 @@ def main():
             if p.returncode != 0:
                 rows.append((name, None, "SMOKE FAILED: " + (p.stderr.strip().splitlines() or ["?"])[-1]))
                 continue
-        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-extra-configs", "--steps", steps, "--warmup", "10"]
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-extra-configs", "--steps", steps, "--warmup", "10"]
                            + extra, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
         line = next((ln for ln in reversed(p.stdout.splitlines()) if ln.startswith("{")), None)
         if p.returncode != 0 or line is None:

@@ -12,12 +12,12 @@ O=gpurun_out
 timeout 1200 python -m pytest tests -m gpu -q 2>&1 | tail -12 > $O/${TAG}_pytest.txt
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu.ids > $O/${TAG}_smoke.txt
 if [ "${COUNTERS:-1}" = "1" ]; then bash tools/gpu_counters.sh ${TAG} > $O/${TAG}_counters.log 2>&1; fi
-timeout 900 python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
-timeout 300 python bench.py --steps 100 --s0 0.05 --no-cpu-baseline --no-extra-configs > $O/${TAG}_bench_deep_s005.json 2>> $O/${TAG}_bench.err
-timeout 300 python bench.py --steps 50 --gaussians 6000000 --no-cpu-baseline --no-extra-configs > $O/${TAG}_bench_6m.json 2>> $O/${TAG}_bench.err
-timeout 300 python bench.py --scene v2 --steps 100 --no-cpu-baseline --no-extra-configs > $O/${TAG}_bench_v2.json 2>> $O/${TAG}_bench.err
-timeout 300 python bench.py --views 8 --steps 50 --warmup 10 --no-cpu-baseline --no-extra-configs > $O/${TAG}_bench_views8.json 2>> $O/${TAG}_bench.err
-timeout 300 python bench.py --views 8 --steps 50 --warmup 10 --no-cpu-baseline --no-extra-configs --no-view-pipeline > $O/${TAG}_bench_views8_serial.json 2>> $O/${TAG}_bench.err
+timeout 900 python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+timeout 300 python bench.py --full --steps 100 --s0 0.05 --no-cpu-baseline --no-extra-configs > $O/${TAG}_bench_deep_s005.json 2>> $O/${TAG}_bench.err
+timeout 300 python bench.py --full --steps 50 --gaussians 6000000 --no-cpu-baseline --no-extra-configs > $O/${TAG}_bench_6m.json 2>> $O/${TAG}_bench.err
+timeout 300 python bench.py --full --scene v2 --steps 100 --no-cpu-baseline --no-extra-configs > $O/${TAG}_bench_v2.json 2>> $O/${TAG}_bench.err
+timeout 300 python bench.py --full --views 8 --steps 50 --warmup 10 --no-cpu-baseline --no-extra-configs > $O/${TAG}_bench_views8.json 2>> $O/${TAG}_bench.err
+timeout 300 python bench.py --full --views 8 --steps 50 --warmup 10 --no-cpu-baseline --no-extra-configs --no-view-pipeline > $O/${TAG}_bench_views8_serial.json 2>> $O/${TAG}_bench.err
 prof() { # name, rocprof args ... -- bench args
   name=$1; shift
   mkdir -p $R/$O/$name
@@ -26,7 +26,7 @@ prof() { # name, rocprof args ... -- bench args
 }
 DB=$(prof ${TAG}_kt --kernel-trace --stats -d $R/$O/${TAG}_kt -o p -- python $R/bench.py --train-only --steps 10 --warmup 2 --prewarm 50)
 python tools/rocpd_kernel_stats.py $DB > $O/${TAG}_kernel_stats.md 2>&1; python tools/rocpd_timeline.py $DB 2 >> $O/${TAG}_kernel_stats.md 2>&1
-DB=$(prof ${TAG}_ktb --kernel-trace --stats -d $R/$O/${TAG}_ktb -o p -- python $R/bench.py --no-cpu-baseline --no-extra-configs)
+DB=$(prof ${TAG}_ktb --kernel-trace --stats -d $R/$O/${TAG}_ktb -o p -- python $R/bench.py --full --no-cpu-baseline --no-extra-configs)
 python tools/rocpd_kernel_stats.py $DB > $O/${TAG}_default_bench_kernel_stats.md 2>&1
 rm -rf $O/${TAG}_kt $O/${TAG}_ktb
 tail -3 $O/${TAG}_pytest.txt; tail -2 $O/${TAG}_smoke.txt

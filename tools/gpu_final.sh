@@ -25,7 +25,7 @@ python tools/rocpd_kernel_stats.py $DB > $O/${TAG}_6m_kernel_stats.md 2>&1; pyth
 DB=$(prof ${TAG}_ktv --kernel-trace --stats -d $R/$O/${TAG}_ktv -o p -- python $R/bench.py --train-only --steps 10 --warmup 2 --prewarm 30 --scene v2)
 python tools/rocpd_kernel_stats.py $DB > $O/${TAG}_v2_kernel_stats.md 2>&1; python tools/rocpd_timeline.py $DB 2 >> $O/${TAG}_v2_kernel_stats.md 2>&1
 # the default bench command itself under the kernel trace (the dominant kernel's average must agree with the line's stage event)
-DB=$(prof ${TAG}_ktb --kernel-trace --stats -d $R/$O/${TAG}_ktb -o p -- python $R/bench.py --no-cpu-baseline --no-extra-configs)
+DB=$(prof ${TAG}_ktb --kernel-trace --stats -d $R/$O/${TAG}_ktb -o p -- python $R/bench.py --full --no-cpu-baseline --no-extra-configs)
 python tools/rocpd_kernel_stats.py $DB > $O/${TAG}_default_bench_kernel_stats.md 2>&1
 rm -rf $O/${TAG}_kt $O/${TAG}_kt6 $O/${TAG}_ktv $O/${TAG}_ktb
 timeout 200 python tools/bwd_items_profile.py > $O/${TAG}_bwd_items.txt 2>&1

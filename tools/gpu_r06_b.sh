@@ -12,7 +12,7 @@ timeout 1500 python tools/ab_variants.py --steps 150 base abl1=GSR_BWD_ABLATE=1 
 cat $O/${T}_ablate.txt
 timeout 900 python tools/ab_variants.py --steps 60 --scene v2 v2base v2abl1=GSR_BWD_ABLATE=1 v2abl2=GSR_BWD_ABLATE=2 v2abl5=GSR_BWD_ABLATE=5 v2abl6=GSR_BWD_ABLATE=6 > $O/${T}_ablate_v2.txt 2>&1
 cat $O/${T}_ablate_v2.txt
-timeout 900 python bench.py --no-cpu-baseline > $O/${T}_bench.json 2> $O/${T}_bench.err
+timeout 900 python bench.py --full --no-cpu-baseline > $O/${T}_bench.json 2> $O/${T}_bench.err
 python - <<PY
 import json
 d = json.load(open("$O/${T}_bench.json"))

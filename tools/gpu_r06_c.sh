@@ -12,8 +12,8 @@ timeout 900 python tools/ab_variants.py --steps 200 base abl2=GSR_BWD_ABLATE=2 b
 cat $O/${T}_ab.txt
 timeout 600 python tools/ab_variants.py --steps 100 --scene v2 v2base v2abl2=GSR_BWD_ABLATE=2 > $O/${T}_ab_v2.txt 2>&1
 cat $O/${T}_ab_v2.txt
-timeout 300 python bench.py --steps 100 --s0 0.05 --no-cpu-baseline --no-extra-configs > $O/${T}_bench_deep.json 2>/dev/null
-timeout 300 python bench.py --steps 50 --gaussians 6000000 --no-cpu-baseline --no-extra-configs > $O/${T}_bench_6m.json 2>/dev/null
+timeout 300 python bench.py --full --steps 100 --s0 0.05 --no-cpu-baseline --no-extra-configs > $O/${T}_bench_deep.json 2>/dev/null
+timeout 300 python bench.py --full --steps 50 --gaussians 6000000 --no-cpu-baseline --no-extra-configs > $O/${T}_bench_6m.json 2>/dev/null
 python - <<PY
 import json
 for n in ("deep", "6m"):

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 O=gpurun_out
 timeout 300 python -c "
 import cProfile, pstats, sys, io
-sys.argv = ['bench.py', '--views', '8', '--steps', '100', '--warmup', '10', '--no-cpu-baseline', '--no-extra-configs']
+sys.argv = ['bench.py', '--full', '--views', '8', '--steps', '100', '--warmup', '10', '--no-cpu-baseline', '--no-extra-configs']
 import runpy
 pr = cProfile.Profile()
 pr.enable()

@@ -21,8 +21,8 @@ echo "== deep again: $cfg" | tee -a $O/${TAG}_defaults.txt
 for it in 0 2 0 2; do
   echo "new ck4 it=$it $(GSR_CK_CHUNKS=4 GSR_BWD_SEG_ITEM=$it python tools/c3_knobs.py $cfg 2>/dev/null)" | tee -a $O/${TAG}_defaults.txt
 done
-python bench.py --no-cpu-baseline > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
-GSR_LIBRARY_PATH=$HEAD_LIB python bench.py --no-cpu-baseline > $O/${TAG}_bench_head.json 2>> $O/${TAG}_bench.err
+python bench.py --full --no-cpu-baseline > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+GSR_LIBRARY_PATH=$HEAD_LIB python bench.py --full --no-cpu-baseline > $O/${TAG}_bench_head.json 2>> $O/${TAG}_bench.err
 python - <<'PY'
 import json
 for n in ("gpurun_out/%s_bench.json" % "$TAG", "gpurun_out/%s_bench_head.json" % "TAGX"):
