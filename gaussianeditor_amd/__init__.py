@@ -68,6 +68,23 @@ def get_fast_exp() -> bool:
     return bool(options.default_flags() & options.FLAG_FAST_EXP)
 
 
+def set_depth_grad(on: bool) -> None:
+    """Opt-in: the default of GSR_FLAG_DEPTH_GRAD (include/gsr.h) -- a loss on the rendered depth image (the third output
+    of the rasterizer, `render_pkg["depth_3dgs"]`) reaches means3D, scales, rotations, opacities and colours.  Off
+    (default): the depth image carries no gradient, exactly as in the reference.  Like every flag it is read once by a
+    render's forward and reused by that render's backward."""
+    from . import options
+
+    f = options.default_flags() & ~options.FLAG_DEPTH_GRAD
+    options.set_default_flags(f | (options.FLAG_DEPTH_GRAD if on else 0))
+
+
+def get_depth_grad() -> bool:
+    from . import options
+
+    return bool(options.default_flags() & options.FLAG_DEPTH_GRAD)
+
+
 def set_view_reuse(on: bool) -> None:
     """View reuse (default on; `GSR_VIEW_REUSE=0` in the environment turns it off): a colour-override render of the view
     the rasterizer rendered last -- the reference's second `render(..., override_color=...)` of every training view and

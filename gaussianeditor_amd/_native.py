@@ -18,7 +18,7 @@ GSR_ABI_VERSION = 6
 
 _P = c_void_p
 #: floats per row of the blend backward's accumulator table and its columns (include/gsr.h: GSR_ACC_*)
-ACC_ROW, ACC_MEAN2D, ACC_OPACITY, ACC_CONIC, ACC_COLOR = 16, 0, 3, 4, 8
+ACC_ROW, ACC_MEAN2D, ACC_OPACITY, ACC_CONIC, ACC_COLOR, ACC_DEPTH = 16, 0, 3, 4, 8, 11
 
 
 class AdamTensor(ctypes.Structure):
@@ -62,6 +62,11 @@ SIGNATURES = {
                              _P, _P, c_float, c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_uint]),
     # (stream, P, R, W, H, bg, geom, binning, image, dL_dpix, acc, touched, flags)
     "gsr_blend_backward": (c_int, [_P, c_int, c_int64, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_uint]),
+    # depth gradients (GSR_FLAG_DEPTH_GRAD): gsr_blend_backward / gsr_backward with dL_ddepth (1,H,W) behind dL_dpix
+    "gsr_blend_backward_depth": (c_int, [_P, c_int, c_int64, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_uint]),
+    "gsr_backward_depth": (c_int, [_P, c_int, c_int, c_int, c_int64, c_int, c_int, _P, _P, _P, _P, _P, c_float, _P, _P, _P,
+                                   _P, _P, c_float, c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                   c_uint]),
     # (... radii, geom, acc, dL_dmeans2D, dL_dopacity, dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drots, flags)
     "gsr_preprocess_backward": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_float, _P, _P, _P, _P, _P,
                                         c_float, c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_uint]),

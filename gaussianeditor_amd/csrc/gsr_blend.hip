@@ -740,6 +740,10 @@ __device__ __forceinline__ void wave_lds_sync() {
 
 constexpr int BWD_WAVES = 4;  // one workgroup = the four quadrants of one tile (or two quadrants of a heavy one)
 constexpr int ACC_LDS_ROW = 9;  // floats per chunk slot of the backward's LDS accumulators: the nine raw moments
+// ... of a DEPTH backward (gsr_blend_backward_depth): ten raw moments (the tenth: alpha T dL_ddepth) in rows of 11 floats
+// (odd, as 9: the slots of the tail's four ds_add lanes and the four rows of a flush instruction spread over the banks)
+template <bool DEPTH> constexpr int bwd_moments() { return DEPTH ? 10 : 9; }
+template <bool DEPTH> constexpr int bwd_lds_row() { return DEPTH ? 11 : ACC_LDS_ROW; }
 constexpr uint32_t BWD_ITEM_HALF = 0x80000000u;   // item code: the workgroup handles one half of the tile ...
 constexpr uint32_t BWD_ITEM_PART = 0x40000000u;   // ... quadrants {2,3} instead of {0,1}
 // ... or (round 4) A RUN OF LIST SEGMENTS of a deep tile: the segments lo .. hi between its checkpoints, i.e. positions
@@ -762,10 +766,19 @@ static_assert(BWD_ITEM_TILE + 1u == (uint32_t)GSR_MAX_TILES, "include/gsr.h stat
 // the CU.  The global float atomics execute at the memory side on this chip and were the largest single
 // cost of the backward (about 200 of 530 us with one atomic per quadrant); a Gaussian typically touches
 // 2-3 of a tile's 4 quadrants.
-template <int ABLATE, bool FAST, bool SEG>  // ABLATE: 0 = product; 1..6 = timing experiments only (wrong results), see launch_blend_backward
+//
+// DEPTH (gsr_blend_backward_depth): the depth image D = sum_i d_i alpha_i T_i is a fourth blended channel with background 0.
+// Its share of dL/dalpha_i is (d_i - depth behind) T_i dL_dD: the entry's depth (staged in s1.z) joins cdot as d_i dL_dD,
+// and B_acc, which follows the same linear recurrence, then carries the depth behind as well.  The tenth raw moment
+// alpha T dL_dD is dL/dd_i, flushed into column ACC_DEPTH.  No list segments (SEG): the forward's checkpoints hold the
+// colour behind a segment, not its depth.
+template <int ABLATE, bool FAST, bool SEG, bool DEPTH>  // ABLATE: 0 = product; 1..6 = timing experiments only (wrong results), see launch_blend_backward
 __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint4 item, const float bg0, const float bg1,
                                               const float bg2, float4 (*s0)[WAVE], float4 (*s1)[WAVE], float4 (*s2)[WAVE],
-                                              uint32_t (*sid)[WAVE], float4 (*sco)[WAVE], float (*sacc)[WAVE][ACC_LDS_ROW]) {
+                                              uint32_t (*sid)[WAVE], float4 (*sco)[WAVE],
+                                              float (*sacc)[WAVE][bwd_lds_row<DEPTH>()]) {
+  static_assert(!(DEPTH && SEG), "depth backwards walk whole lists: the checkpoints hold no depth");
+  constexpr int NM = bwd_moments<DEPTH>();  // raw moments per entry
   const int w = (int)(threadIdx.x >> 6), lane = lane_id();
   // The item's descriptor (assembled by the caller from three scalar loads): x = code -- a whole tile, wave w = quadrant w; or
   // half a tile, waves (0,1) and (2,3) = the upper / lower 8x4 pixels of its two quadrants; or one list segment --, y = first
@@ -800,6 +813,7 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
   const float T_final_ld = a.final_T[pix];
   const uint32_t n_contrib_ld = a.n_contrib[pix];
   const float dpx_ld[3] = {a.dL_dpix[pix], a.dL_dpix[HW + pix], a.dL_dpix[2 * HW + pix]};
+  const float dpd_ld = DEPTH ? a.dL_ddepth[pix] : 0.f;
   // back to front over the item's positions [seg_lo, seg_hi) of the tile's list, all four waves in the same chunks
   ChunkWalker<false> walk(a, list_base + seg_lo, seg_hi - seg_lo);
 
@@ -808,6 +822,7 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
   const uint32_t last_contributor = live ? n_contrib_ld : 0u;
   const uint32_t maxc = wave_max_u32_dpp(last_contributor);  // (this wave's pixels; the item's is tile_max)
   const float dpx[3] = {live ? dpx_ld[0] : 0.f, live ? dpx_ld[1] : 0.f, live ? dpx_ld[2] : 0.f};
+  const float dpd = live ? dpd_ld : 0.f;  // (DEPTH) dL_dout_depth of the pixel
   const float bg_dot_dpixel = (0.f + bg0 * dpx[0]) + bg1 * dpx[1] + bg2 * dpx[2];
   const float neg_Tfinal_bg = -T_final * bg_dot_dpixel;  // the background's share of dL/dalpha is this times 1 / (1 - alpha)
   const float ddelx_dx = 0.5f * a.W, ddely_dy = 0.5f * a.H;
@@ -866,17 +881,19 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
   auto flush = [&](uint32_t fb, uint32_t fsize) __attribute__((always_inline)) {
     constexpr bool emit = ABLATE != 2 && ABLATE != 3 && ABLATE != 6;  // (experiments: no global atomics)
     const uint32_t col = (uint32_t)lane & 15u, sub = (uint32_t)lane >> 4;
-    // raw moments a column reads: dL_dmean2D needs (1, 2); conic x / y / w: 3 / 4 / 5; opacity: 0; colour: 6 / 7 / 8
+    // raw moments a column reads: dL_dmean2D needs (1, 2); conic x / y / w: 3 / 4 / 5; opacity: 0; colour: 6 / 7 / 8;
+    // (DEPTH) depth: 9
     const uint32_t ia = col == ACC_MEAN2D || col == ACC_MEAN2D + 1u ? 1u
                         : col == ACC_OPACITY ? 0u
                         : col == ACC_CONIC ? 3u : col == ACC_CONIC + 1u ? 4u : col == ACC_CONIC + 3u ? 5u
-                        : col >= ACC_COLOR && col < ACC_COLOR + 3u ? 6u + (col - ACC_COLOR) : 9u;  // 9: the column is not used
+                        : col >= ACC_COLOR && col < ACC_COLOR + 3u ? 6u + (col - ACC_COLOR)
+                        : DEPTH && col == ACC_DEPTH ? 9u : (uint32_t)NM;  // NM: the column is not used
 #pragma unroll
     for (uint32_t jj = 0; jj < 4u; ++jj) {
       const uint32_t p = 16u * (uint32_t)w + 4u * jj + sub;
       if (16u * (uint32_t)w + 4u * jj >= fsize) break;  // (wave-uniform: slots >= fsize are never added to)
       float* const row = sacc[fb][p];
-      const bool used = p < fsize && ia < 9u;
+      const bool used = p < fsize && ia < (uint32_t)NM;
       const float ma = used ? row[ia] : 0.f;
       const float mb = used && ia == 1u ? row[2] : 0.f;
       const float4 co = sco[fb][p];  // conic.x, conic.y, conic.z, opacity
@@ -889,7 +906,7 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
         val = -(scale * co.w) * (c1 * ma + c2 * mb);
         nz = ma != 0.f || mb != 0.f;
       } else {
-        const bool conic = ia >= 3u && ia <= 5u;  // backward.cu:549-551: -0.5 o t; opacity (:554) and colour (:523): the moment itself
+        const bool conic = ia >= 3u && ia <= 5u;  // backward.cu:549-551: -0.5 o t; opacity (:554), colour (:523), depth: the moment itself
         val = conic ? (-0.5f * co.w) * ma : ma;
         nz = ma != 0.f;
       }
@@ -898,7 +915,7 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
         const uint64_t nzm = __ballot(used && nz);  // group marks the group's Gaussian if any of its columns was added to
         if (col == 15u && p < fsize && ((nzm >> (16u * sub)) & 0xffffull) != 0ull) a.touched[sid[fb][p]] = 1;
       }
-      if (p < fsize && col < 9u) row[col] = 0.f;  // (every read of this instruction precedes it: one wave, program order)
+      if (p < fsize && col < (uint32_t)NM) row[col] = 0.f;  // (every read of this instruction precedes it: one wave, program order)
     }
   };
 
@@ -956,6 +973,7 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
       float G[GROUP], al[GROUP], dxs[GROUP], dys[GROUP];
       bool contrib[GROUP];
       float4 cos_[GROUP], cols[GROUP];
+      float dep[GROUP];  // (DEPTH) the entries' view-space depths
       bool any = false;
 #if GSR_BWD_HYBRID_EXP
       // The exponential of the backward (round 6).  The FORWARD's colours are compared bit for bit, so it evaluates the
@@ -970,6 +988,7 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
 #pragma unroll
       for (int u = 0; u < GROUP; ++u) {
         const float4 g = s1[w][j + u];
+        dep[u] = DEPTH ? g.z : 0.f;
         cos_[u] = s0[w][j + u];
         cols[u] = s2[w][j + u];
         dxs[u] = g.x - pfx;
@@ -998,6 +1017,7 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
 #pragma unroll
       for (int u = 0; u < GROUP; ++u) {
         const float4 g = s1[w][j + u];
+        dep[u] = DEPTH ? g.z : 0.f;
         cos_[u] = s0[w][j + u];
         cols[u] = s2[w][j + u];
         const uint32_t c = __float_as_uint(g.w);  // 0-based position of this instance in the tile list
@@ -1013,7 +1033,7 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
       if (!__any(any)) continue;  // wave-uniform
       if (ABLATE == 4) continue;  // experiment: footprint + exp only
 
-      float v[9][GROUP];
+      float v[NM][GROUP];
       {
 #pragma clang fp contract(fast)  // gradients are tolerance-checked (<= 1e-5), not bit-compared: let a*b+c fuse here
 #pragma unroll
@@ -1038,7 +1058,9 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
 #else
           const float inv_one_m = __builtin_amdgcn_rcpf(1.f - alpha);
 #endif
-          const float cdot = cols[u].x * dpx[0] + cols[u].y * dpx[1] + cols[u].z * dpx[2];
+          // (DEPTH: the depth channel joins the collapsed recurrence, d * dL_dD; its background is 0)
+          const float cdot = DEPTH ? cols[u].x * dpx[0] + cols[u].y * dpx[1] + cols[u].z * dpx[2] + dep[u] * dpd
+                                   : cols[u].x * dpx[0] + cols[u].y * dpx[1] + cols[u].z * dpx[2];
           T = T * inv_one_m;                                      // T / (1 - alpha), backward.cu:503
           B_acc = B_acc + last_alpha * (last_cdot - B_acc);       // accum_rec update, backward.cu:515
           const float dL_dalpha = (cdot - B_acc) * T + neg_Tfinal_bg * inv_one_m;
@@ -1059,20 +1081,21 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
           v[6][u] = mD * dpx[0];
           v[7][u] = mD * dpx[1];
           v[8][u] = mD * dpx[2];
+          if constexpr (DEPTH) v[9][u] = mD * dpd;  // dL/dd of the entry
         }
       }
       // 4-entry transposed wave reduction: afterwards lane 15 of row r holds the wave totals of entry j + r and adds the
       // nine RAW moments to the tile-level accumulator of the entry's chunk slot (they are relative to the entry's own
       // mean, so the quadrants' sums simply add; the flush turns them into the reference's terms).
-      float tot[9];
+      float tot[NM];
 #pragma unroll
-      for (int k = 0; k < 9; ++k)
+      for (int k = 0; k < NM; ++k)
         tot[k] = (ABLATE == 1 || ABLATE == 3) ? (v[k][0] + v[k][1]) + (v[k][2] + v[k][3])  // experiment: no reduction
                                               : wave_sum4_to_rows(v[k][0], v[k][1], v[k][2], v[k][3]);
       // keep the reductions whole in front of the 4-lane tail: otherwise the last row_shr step is sunk into the masked
       // region as v_mov 0 + v_mov_dpp + v_add (3 instructions per term instead of one v_add_f32_dpp)
 #pragma unroll
-      for (int k = 0; k < 9; ++k) asm volatile("" : "+v"(tot[k]));
+      for (int k = 0; k < NM; ++k) asm volatile("" : "+v"(tot[k]));
       if ((lane & 15) == 15) {
 #if GSR_BWD_SLOT_REG  // (A/B) the row's accumulator slot from the colour records already in registers: no LDS round trip in the tail
         const uint32_t row = (uint32_t)lane >> 4;
@@ -1082,7 +1105,7 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
         const uint32_t my_slot = __float_as_uint(s2[w][j + (uint32_t)(lane >> 4)].w);
 #endif
 #pragma unroll
-        for (int k = 0; k < 9; ++k) atomicAdd(&sacc[cb][my_slot][k], tot[k]);
+        for (int k = 0; k < NM; ++k) atomicAdd(&sacc[cb][my_slot][k], tot[k]);
       }
     }
     if (ABLATE != 5 && ABLATE != 6) __syncthreads();  // (B) every quadrant's contribution to this chunk is in sacc[cb]
@@ -1103,15 +1126,16 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
 #ifndef GSR_BWD_WAVES_PER_EU
 #define GSR_BWD_WAVES_PER_EU 4  // (A/B builds: 5 with GSR_BLEND_WAVES_PER_SIMD=5)
 #endif
-template <int ABLATE, bool FAST, bool SEG>
+template <int ABLATE, bool FAST, bool SEG, bool DEPTH>
 __global__ void __launch_bounds__(WAVE* BWD_WAVES) __attribute__((amdgpu_waves_per_eu(GSR_BWD_WAVES_PER_EU, GSR_BWD_WAVES_PER_EU)))
 blend_backward_kernel(const BlendArgs a) {
+  constexpr int LDS_ROW = bwd_lds_row<DEPTH>();
   __shared__ float4 s0[BWD_WAVES][WAVE], s1[BWD_WAVES][WAVE], s2[BWD_WAVES][WAVE];
   __shared__ uint32_t sid[2][WAVE];  // (sid, sco, sacc: double-buffered by chunk parity, see backward_tile)
   __shared__ float4 sco[2][WAVE];
-  __shared__ float sacc[2][WAVE][ACC_LDS_ROW];  // raw moments 0..8 of every chunk slot (row stride 9: odd, the four rows of a flush instruction spread over the banks)
+  __shared__ float sacc[2][WAVE][LDS_ROW];  // raw moments 0..8 (DEPTH: 0..9) of every chunk slot (row stride 9 / 11: odd, the four rows of a flush instruction spread over the banks)
   __shared__ uint32_t s_item;
-  for (int i = threadIdx.x; i < 2 * WAVE * ACC_LDS_ROW; i += WAVE * BWD_WAVES) (&sacc[0][0][0])[i] = 0.f;
+  for (int i = threadIdx.x; i < 2 * WAVE * LDS_ROW; i += WAVE * BWD_WAVES) (&sacc[0][0][0])[i] = 0.f;
   // (element i was zeroed by thread i % 256, i.e. by any wave: with the deferred flush the placement-assigned first item
   // reaches its first ds_add_f32 without passing a workgroup barrier otherwise.  Once per kernel, not per item.)
   __syncthreads();
@@ -1144,7 +1168,7 @@ blend_backward_kernel(const BlendArgs a) {
     const uint32_t r01 = max(cmax.x, cmax.y), r23 = max(cmax.z, cmax.w);
     const uint4 item = make_uint4(code, crange.x, (code & BWD_ITEM_HALF) ? ((code & BWD_ITEM_PART) ? r23 : r01) : max(r01, r23), 0u);
     const uint32_t tile = item.x;
-    const uint32_t tmax = backward_tile<ABLATE, FAST, SEG>(a, item, bg0, bg1, bg2, s0, s1, s2, sid, sco, sacc);
+    const uint32_t tmax = backward_tile<ABLATE, FAST, SEG, DEPTH>(a, item, bg0, bg1, bg2, s0, s1, s2, sid, sco, sacc);
     if (prof) {
       const uint64_t d = __builtin_amdgcn_s_memtime() - t_tile;
       if (a.profile_items != nullptr && threadIdx.x == 0 && a.work_est != nullptr) {
@@ -1686,7 +1710,8 @@ hipError_t launch_blend_backward(hipStream_t s, BlendArgs a) {
     // (Merging consecutive strides of a cut tile into items of about equal measured work -- the plan of
     //  profiles/r06_k -- was built and swept over eleven workloads at 2 .. 12 sixteenths of a fair share per item: equal at
     //  best, 8-40 % slower where pixels walk deep; removed: profiles/r06_m_fine_checkpoints.md.)
-    seg_items = a.ck_table != nullptr && a.ck_chunks > 0 && seg_share > 0 && ablate == 0;
+    // (a depth backward: no segments -- the checkpoints hold no depth behind a segment, backward_tile)
+    seg_items = a.ck_table != nullptr && a.ck_chunks > 0 && seg_share > 0 && ablate == 0 && a.dL_ddepth == nullptr;
     if (seg_items)
       hipLaunchKernelGGL(backward_worklist_kernel<true>, dim3(1u + fill_blocks), dim3(1024), 0, s, a.gx * a.gy, a.work_est,
                          a.bwd_order, a.bwd_meta, blend_grid_size(true, s, sh) / BWD_WAVES, halves, clear, (const uint32_t*)a.tile_maxc,
@@ -1698,20 +1723,25 @@ hipError_t launch_blend_backward(hipStream_t s, BlendArgs a) {
   }
   // #CUs x 4 workgroups of 4 waves: the same 4 waves per SIMD as the forward
   const dim3 g(blend_grid_size(true, s, sh) / BWD_WAVES), b(WAVE * BWD_WAVES);
+  if (a.dL_ddepth != nullptr) {  // (the product kernel only: the ablation experiments have no depth variant)
+    if (a.fast_exp) hipLaunchKernelGGL((blend_backward_kernel<0, true, false, true>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((blend_backward_kernel<0, false, false, true>), g, b, 0, s, a);
+    return hipGetLastError();
+  }
   switch (ablate) {
-    case 1: hipLaunchKernelGGL((blend_backward_kernel<1, false, false>), g, b, 0, s, a); break;
-    case 2: hipLaunchKernelGGL((blend_backward_kernel<2, false, false>), g, b, 0, s, a); break;
-    case 3: hipLaunchKernelGGL((blend_backward_kernel<3, false, false>), g, b, 0, s, a); break;
-    case 4: hipLaunchKernelGGL((blend_backward_kernel<4, false, false>), g, b, 0, s, a); break;
-    case 5: hipLaunchKernelGGL((blend_backward_kernel<5, false, false>), g, b, 0, s, a); break;
-    case 6: hipLaunchKernelGGL((blend_backward_kernel<6, false, false>), g, b, 0, s, a); break;
+    case 1: hipLaunchKernelGGL((blend_backward_kernel<1, false, false, false>), g, b, 0, s, a); break;
+    case 2: hipLaunchKernelGGL((blend_backward_kernel<2, false, false, false>), g, b, 0, s, a); break;
+    case 3: hipLaunchKernelGGL((blend_backward_kernel<3, false, false, false>), g, b, 0, s, a); break;
+    case 4: hipLaunchKernelGGL((blend_backward_kernel<4, false, false, false>), g, b, 0, s, a); break;
+    case 5: hipLaunchKernelGGL((blend_backward_kernel<5, false, false, false>), g, b, 0, s, a); break;
+    case 6: hipLaunchKernelGGL((blend_backward_kernel<6, false, false, false>), g, b, 0, s, a); break;
     default:
       if (seg_items) {
-        if (a.fast_exp) hipLaunchKernelGGL((blend_backward_kernel<0, true, true>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((blend_backward_kernel<0, false, true>), g, b, 0, s, a);
+        if (a.fast_exp) hipLaunchKernelGGL((blend_backward_kernel<0, true, true, false>), g, b, 0, s, a);
+        else hipLaunchKernelGGL((blend_backward_kernel<0, false, true, false>), g, b, 0, s, a);
       } else {
-        if (a.fast_exp) hipLaunchKernelGGL((blend_backward_kernel<0, true, false>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((blend_backward_kernel<0, false, false>), g, b, 0, s, a);
+        if (a.fast_exp) hipLaunchKernelGGL((blend_backward_kernel<0, true, false, false>), g, b, 0, s, a);
+        else hipLaunchKernelGGL((blend_backward_kernel<0, false, false, false>), g, b, 0, s, a);
       }
       break;
   }

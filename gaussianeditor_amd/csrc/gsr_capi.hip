@@ -349,6 +349,10 @@ extern "C" {
 
 int gsr_abi_version(void) { return GSR_ABI_VERSION; }
 
+// The flags the forward / trace entry points, gsr_blend_backward and gsr_backward accept: all but GSR_FLAG_DEPTH_GRAD, which
+// only the depth backwards and K8+K9 read (include/gsr.h)
+static constexpr unsigned VIEW_FLAGS = GSR_FLAG_ALL & ~GSR_FLAG_DEPTH_GRAD;
+
 const char* gsr_status_string(int status) {
   switch (status) {
     case GSR_OK: return "ok";
@@ -410,7 +414,7 @@ int preprocess_args_ok(int P, int D, int M, const float* means3D, const float* s
                        const float* opacities, const float* shs, const float* cov3D_precomp, const float* colors_precomp,
                        const float* viewmatrix, const float* projmatrix, const float* campos, int W, int H, int skip_color,
                        unsigned flags, const int32_t* radii, const void* geom) {
-  if (P < 0 || W <= 0 || H <= 0 || D < 0 || D > 3 || (flags & ~GSR_FLAG_ALL)) return GSR_ERR_BAD_ARGUMENT;
+  if (P < 0 || W <= 0 || H <= 0 || D < 0 || D > 3 || (flags & ~VIEW_FLAGS)) return GSR_ERR_BAD_ARGUMENT;
   if (!means3D || !opacities || !viewmatrix || !projmatrix || !radii || !geom || misaligned(geom)) return GSR_ERR_BAD_ARGUMENT;
   if (cov3D_precomp == nullptr && (scales == nullptr || rotations == nullptr)) return GSR_ERR_BAD_ARGUMENT;
   if (!skip_color) {
@@ -604,7 +608,7 @@ int gsr_bin(void* stream, int P, int64_t R, int64_t G, int W, int H, const void*
 
 int gsr_blend_forward(void* stream, int P, int64_t R, int W, int H, const float* bg, const void* geom,
                       const void* binning, void* image, float* out_color, float* out_depth, unsigned flags) {
-  if (P < 0 || R < 0 || W <= 0 || H <= 0 || !bg || !image || !out_color || !out_depth || (flags & ~GSR_FLAG_ALL))
+  if (P < 0 || R < 0 || W <= 0 || H <= 0 || !bg || !image || !out_color || !out_depth || (flags & ~VIEW_FLAGS))
     return GSR_ERR_BAD_ARGUMENT;
   if (R > 0 && (!geom || !binning)) return GSR_ERR_BAD_ARGUMENT;
   const Geom g = carve_geom(const_cast<void*>(geom), P);
@@ -623,7 +627,7 @@ int gsr_blend_forward(void* stream, int P, int64_t R, int W, int H, const float*
 int gsr_blend_forward_aux(void* stream, int P, int64_t R, int W, int H, const float* bg, const void* geom,
                           const void* binning, void* image, const float* colors, float* out_color, float* out_depth,
                           unsigned flags) {
-  if (P < 0 || R < 0 || W <= 0 || H <= 0 || !bg || !image || !out_color || (flags & ~GSR_FLAG_ALL)) return GSR_ERR_BAD_ARGUMENT;
+  if (P < 0 || R < 0 || W <= 0 || H <= 0 || !bg || !image || !out_color || (flags & ~VIEW_FLAGS)) return GSR_ERR_BAD_ARGUMENT;
   if (R > 0 && (!geom || !binning || !colors)) return GSR_ERR_BAD_ARGUMENT;
   const Geom g = carve_geom(const_cast<void*>(geom), P);
   const Binning b = carve_binning_view(binning, R, W, H);
@@ -665,9 +669,10 @@ int gsr_debug_blend_forward_profile(void* stream, int P, int64_t R, int W, int H
   return GSR_OK;
 }
 
-int gsr_blend_backward(void* stream, int P, int64_t R, int W, int H, const float* bg, const void* geom,
-                       const void* binning, const void* image, const float* dL_dpix, float* acc, uint8_t* touched,
-                       unsigned flags) {
+// gsr_blend_backward and gsr_blend_backward_depth (dL_ddepth != null: the DEPTH kernels)
+static int blend_backward_impl(void* stream, int P, int64_t R, int W, int H, const float* bg, const void* geom,
+                               const void* binning, const void* image, const float* dL_dpix, const float* dL_ddepth,
+                               float* acc, uint8_t* touched, unsigned flags) {
   // (a backward of a view whose forward was declared forward-only: the flags of one view travel together)
   if ((flags & ~GSR_FLAG_ALL) || (flags & (GSR_FLAG_FORWARD_ONLY | GSR_FLAG_ACC_SELF_CLEAN))) return GSR_ERR_BAD_ARGUMENT;
   if (P == 0) return GSR_OK;
@@ -687,6 +692,7 @@ int gsr_blend_backward(void* stream, int P, int64_t R, int W, int H, const float
   const Binning b = carve_binning_view(binning, R, W, H);
   BlendArgs a = make_blend_args(W, H, g, b, im, bg, 1, R);
   a.dL_dpix = dL_dpix;
+  a.dL_ddepth = dL_ddepth;
   a.acc = acc;
   a.touched = touched;
   a.fast_exp = (flags & GSR_FLAG_FAST_EXP) ? 1 : 0;
@@ -697,6 +703,22 @@ int gsr_blend_backward(void* stream, int P, int64_t R, int W, int H, const float
   return GSR_OK;
 }
 
+int gsr_blend_backward(void* stream, int P, int64_t R, int W, int H, const float* bg, const void* geom,
+                       const void* binning, const void* image, const float* dL_dpix, float* acc, uint8_t* touched,
+                       unsigned flags) {
+  if (flags & GSR_FLAG_DEPTH_GRAD) return GSR_ERR_BAD_ARGUMENT;  // (gsr_blend_backward_depth: the entry point with the input)
+  return blend_backward_impl(stream, P, R, W, H, bg, geom, binning, image, dL_dpix, nullptr, acc, touched, flags);
+}
+
+int gsr_blend_backward_depth(void* stream, int P, int64_t R, int W, int H, const float* bg, const void* geom,
+                             const void* binning, const void* image, const float* dL_dpix, const float* dL_ddepth, float* acc,
+                             uint8_t* touched, unsigned flags) {
+  // (dL_ddepth is required whenever there is something to blend; P == 0 / R == 0 touch no pixel)
+  if (P > 0 && R > 0 && !dL_ddepth) return GSR_ERR_BAD_ARGUMENT;
+  return blend_backward_impl(stream, P, R, W, H, bg, geom, binning, image, dL_dpix, dL_ddepth, acc, touched,
+                             flags & ~GSR_FLAG_DEPTH_GRAD);
+}
+
 static int preprocess_backward_impl(void* stream, int P, int D, int M, int W, int H, const float* means3D, const float* shs,
                                     const float* scales, float scale_modifier, const float* rotations,
                                     const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
@@ -704,7 +726,7 @@ static int preprocess_backward_impl(void* stream, int P, int D, int M, int W, in
                                     const void* geom, const float* acc, float* dL_dmeans2D, float* dL_dopacity,
                                     float* dL_dcolors, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
                                     float* dL_drgb, float* dL_dscales, float* dL_drots, uint8_t* row_state = nullptr,
-                                    bool self_clean = false) {
+                                    bool self_clean = false, bool depth = false) {
   if (P == 0) return GSR_OK;
   if (P < 0 || W <= 0 || H <= 0 || D < 0 || D > 3) return GSR_ERR_BAD_ARGUMENT;
   if (!means3D || !viewmatrix || !projmatrix || !radii || !geom) return GSR_ERR_BAD_ARGUMENT;
@@ -735,6 +757,7 @@ static int preprocess_backward_impl(void* stream, int P, int D, int M, int W, in
   pa.dL_drot = scales ? dL_drots : nullptr;
   pa.row_state = row_state;
   pa.acc_clean = self_clean ? const_cast<float*>(acc) : nullptr;  // (GSR_FLAG_ACC_SELF_CLEAN: the caller's table, writable by contract)
+  pa.depth = depth ? 1 : 0;  // (GSR_FLAG_DEPTH_GRAD: column ACC_DEPTH enters dL_dmeans3D)
   GSR_HIP(launch_preprocess_backward((hipStream_t)stream, pa));
   return GSR_OK;
 }
@@ -773,11 +796,11 @@ int gsr_preprocess_backward(void* stream, int P, int D, int M, int W, int H, con
                             float* dL_dcolors, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
                             float* dL_dscales, float* dL_drots, unsigned flags) {
   if (shs && !dL_dsh) return GSR_ERR_BAD_ARGUMENT;
-  if (flags & ~GSR_FLAG_ACC_SELF_CLEAN) return GSR_ERR_BAD_ARGUMENT;  // (the one flag this half reads)
+  if (flags & ~(GSR_FLAG_ACC_SELF_CLEAN | GSR_FLAG_DEPTH_GRAD)) return GSR_ERR_BAD_ARGUMENT;  // (the two flags this half reads)
   return preprocess_backward_impl(stream, P, D, M, W, H, means3D, shs, scales, scale_modifier, rotations, cov3D_precomp,
                                   viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom, acc, dL_dmeans2D, dL_dopacity,
                                   dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, nullptr, dL_dscales, dL_drots, nullptr,
-                                  (flags & GSR_FLAG_ACC_SELF_CLEAN) != 0);
+                                  (flags & GSR_FLAG_ACC_SELF_CLEAN) != 0, (flags & GSR_FLAG_DEPTH_GRAD) != 0);
 }
 
 int gsr_preprocess_backward_rgb(void* stream, int P, int D, int M, int W, int H, const float* means3D, const float* shs,
@@ -788,11 +811,11 @@ int gsr_preprocess_backward_rgb(void* stream, int P, int D, int M, int W, int H,
                                 float* dL_dmeans3D, float* dL_dcov3D, float* dL_drgb,
                                 float* dL_dscales, float* dL_drots, unsigned flags) {
   if (!shs || !dL_drgb) return GSR_ERR_BAD_ARGUMENT;
-  if (flags & ~GSR_FLAG_ACC_SELF_CLEAN) return GSR_ERR_BAD_ARGUMENT;
+  if (flags & ~(GSR_FLAG_ACC_SELF_CLEAN | GSR_FLAG_DEPTH_GRAD)) return GSR_ERR_BAD_ARGUMENT;
   return preprocess_backward_impl(stream, P, D, M, W, H, means3D, shs, scales, scale_modifier, rotations, cov3D_precomp,
                                   viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom, acc, dL_dmeans2D, dL_dopacity,
                                   nullptr, dL_dmeans3D, dL_dcov3D, nullptr, dL_drgb, dL_dscales, dL_drots, nullptr,
-                                  (flags & GSR_FLAG_ACC_SELF_CLEAN) != 0);
+                                  (flags & GSR_FLAG_ACC_SELF_CLEAN) != 0, (flags & GSR_FLAG_DEPTH_GRAD) != 0);
 }
 
 int gsr_preprocess_backward_rows(void* stream, int P, int D, int M, int W, int H, const float* means3D, const float* shs,
@@ -916,6 +939,28 @@ int gsr_backward(void* stream, int P, int D, int M, int64_t R, int W, int H, con
                                  self_clean ? GSR_FLAG_ACC_SELF_CLEAN : 0u);
 }
 
+int gsr_backward_depth(void* stream, int P, int D, int M, int64_t R, int W, int H, const float* bg, const float* means3D,
+                       const float* shs, const float* colors_precomp, const float* scales, float scale_modifier,
+                       const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                       const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy, const int32_t* radii,
+                       const void* geom, const void* binning, const void* image, const float* dL_dpix,
+                       const float* dL_ddepth, float* acc, float* dL_dmeans2D, float* dL_dopacity, float* dL_dcolors,
+                       float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drots,
+                       unsigned flags) {
+  (void)colors_precomp;
+  if (P == 0) return GSR_OK;
+  if (R > 0 && !binning) return GSR_ERR_BAD_ARGUMENT;
+  const bool self_clean = (flags & GSR_FLAG_ACC_SELF_CLEAN) != 0;
+  if (self_clean && (flags & GSR_FLAG_CLEAR_GRADS)) return GSR_ERR_BAD_ARGUMENT;
+  int st = gsr_blend_backward_depth(stream, P, R, W, H, bg, geom, binning, image, dL_dpix, dL_ddepth, acc, nullptr,
+                                    flags & ~GSR_FLAG_ACC_SELF_CLEAN);
+  if (st != GSR_OK) return st;
+  return gsr_preprocess_backward(stream, P, D, M, W, H, means3D, shs, scales, scale_modifier, rotations, cov3D_precomp,
+                                 viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom, acc, dL_dmeans2D, dL_dopacity,
+                                 dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drots,
+                                 (self_clean ? GSR_FLAG_ACC_SELF_CLEAN : 0u) | GSR_FLAG_DEPTH_GRAD);
+}
+
 int gsr_mark_visible(void* stream, int P, const float* means3D, const float* viewmatrix, const float* projmatrix,
                      uint8_t* present) {
   (void)projmatrix;  // computed but unused by the reference as well (auxiliary.h:149-154)
@@ -928,7 +973,7 @@ int gsr_mark_visible(void* stream, int P, const float* means3D, const float* vie
 int gsr_trace_weights(void* stream, int P, int64_t R, int W, int H, int C, const void* geom, const void* binning,
                       const void* image, const float* image_weights, float* weights, int32_t* cnt, unsigned flags) {
   if (C < 1 || C > 3) return GSR_ERR_BAD_CHANNELS;
-  if (flags & ~GSR_FLAG_ALL) return GSR_ERR_BAD_ARGUMENT;
+  if (flags & ~VIEW_FLAGS) return GSR_ERR_BAD_ARGUMENT;
   if (P < 0 || R < 0 || W <= 0 || H <= 0 || !image || !image_weights || !weights || !cnt) return GSR_ERR_BAD_ARGUMENT;
   if (R == 0) return GSR_OK;
   if (!geom || !binning) return GSR_ERR_BAD_ARGUMENT;

@@ -31,6 +31,8 @@ struct PreArgs {
 // K8+K9 arguments (preprocess_backward_kernel, gsr_preprocess.hip)
 struct PreBwdArgs {
   int P, D, M;
+  int depth;                   // GSR_FLAG_DEPTH_GRAD: column ACC_DEPTH (dL_ddepth) enters dL_dmeans3D (not with row_state)
+                               // (in the padding in front of the pointers: the struct's size and layout stay what they were)
   const float* means3D;
   const int32_t* radii;
   const float* shs;
@@ -80,7 +82,11 @@ struct BlendArgs {
   uint32_t* n_contrib;
   // forward outputs
   float* out_color;
-  float* out_depth;
+  union {
+    float* out_depth;
+    const float* dL_ddepth;  // backward: (1,H,W) gradient of out_depth (gsr_blend_backward_depth), or null -- the slot of the
+                             // forward-only output, so that the struct (and every kernel's argument layout) keeps its size
+  };
   // backward
   const float* dL_dpix;
   float* acc;      // (P, ACC_ROW): one 64-byte row of accumulators per Gaussian (ACC_* columns, gsr_common.h / include/gsr.h)

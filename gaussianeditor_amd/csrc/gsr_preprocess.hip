@@ -550,7 +550,10 @@ __device__ __forceinline__ void sh_tile_store_rows(float* __restrict__ dst_rows,
 // Gaussians of ten get all-zero gradients from a view (culled, or no pixel blended them); their rows are rewritten only if
 // they do not hold this kernel's zeros already (row_state[g] != 0), so what leaves the chip per view is the rows that are
 // non-zero now or were the last time -- 248 B x ~20 % instead of 248 B x P.  dL_dcov3D is always written.
-template <bool ROWS>
+// DEPTH (GSR_FLAG_DEPTH_GRAD, not with ROWS): column ACC_DEPTH of the row -- dL/dd, d the view-space z of the mean -- adds
+// dL/dd * dd/dmean = dL/dd * (view[2], view[6], view[10]) to dL_dmeans3D (transformPoint4x3, auxiliary.h); and it is one
+// more column that decides whether a row is zero.
+template <bool ROWS, bool DEPTH>
 __global__ void __launch_bounds__(GAUSS_BLOCK) __attribute__((amdgpu_waves_per_eu(3, 3)))
 preprocess_backward_kernel(const PreBwdArgs a) {
   __shared__ float4 sh_tile[GAUSS_BLOCK / 64][SH_TILE_F4];
@@ -590,13 +593,14 @@ preprocess_backward_kernel(const PreBwdArgs a) {
   const acc_f4 acc_m2d_ = K9_ACC_LD(ACC_MEAN2D / 4), acc_col_ = K9_ACC_LD(ACC_COLOR / 4), acc_con_ = K9_ACC_LD(ACC_CONIC / 4);
 #undef K9_ACC_LD
   const float4 acc_m2d = make_float4(acc_m2d_.x, acc_m2d_.y, acc_m2d_.z, acc_m2d_.w);  // dL_dmean2D.x, .y, (0), dL_dopacity
-  const float4 acc_col = make_float4(acc_col_.x, acc_col_.y, acc_col_.z, acc_col_.w);  // dL_dcolor r, g, b, (0)
+  const float4 acc_col = make_float4(acc_col_.x, acc_col_.y, acc_col_.z, acc_col_.w);  // dL_dcolor r, g, b, (0 | DEPTH: dL_ddepth)
   const float4 acc_con = make_float4(acc_con_.x, acc_con_.y, acc_con_.z, acc_con_.w);  // dL_dconic x, y, (0), w
   if (a.acc_clean != nullptr && live) {
     // GSR_FLAG_ACC_SELF_CLEAN: the table is the caller's across backwards -- a row K7 touched (one in ten on the benchmark
     // view) goes back to zero here, whole 64-byte lines, so that the next backward starts from a zero table without a clear
     const bool dirty = !(acc_m2d.x == 0.f) || !(acc_m2d.y == 0.f) || !(acc_m2d.w == 0.f) || !(acc_con.x == 0.f) ||
-                       !(acc_con.y == 0.f) || !(acc_con.w == 0.f) || !(acc_col.x == 0.f) || !(acc_col.y == 0.f) || !(acc_col.z == 0.f);
+                       !(acc_con.y == 0.f) || !(acc_con.w == 0.f) || !(acc_col.x == 0.f) || !(acc_col.y == 0.f) || !(acc_col.z == 0.f) ||
+                       (DEPTH && !(acc_col.w == 0.f));
     if (dirty) {
       float4* const w = reinterpret_cast<float4*>(a.acc_clean + (size_t)idx * ACC_ROW);
       const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -645,7 +649,8 @@ preprocess_backward_kernel(const PreBwdArgs a) {
       cov3d_from_values(sc0, sc1, sc2, a.scale_modifier, quat, c3);  // what K1 computed, bit for bit
     }
     const V3 dL_dcon = {gc.x, gc.y, gc.w};
-    nonzero_in = gc.x != 0.f || gc.y != 0.f || gc.w != 0.f || acc_m2d.w != 0.f || acc_col.x != 0.f || acc_col.y != 0.f || acc_col.z != 0.f;
+    nonzero_in = gc.x != 0.f || gc.y != 0.f || gc.w != 0.f || acc_m2d.w != 0.f || acc_col.x != 0.f || acc_col.y != 0.f || acc_col.z != 0.f ||
+                 (DEPTH && acc_col.w != 0.f);
 
     // ---- computeCov2DCUDA, backward.cu:159-273 ----
     V3 t = {view[0] * mean.x + view[4] * mean.y + view[8] * mean.z + view[12],
@@ -722,6 +727,10 @@ preprocess_backward_kernel(const PreBwdArgs a) {
     dL_dmean.y = (proj[4] * m_w - proj[7] * mul1) * g2x + (proj[5] * m_w - proj[7] * mul2) * g2y;
     dL_dmean.z = (proj[8] * m_w - proj[11] * mul1) * g2x + (proj[9] * m_w - proj[11] * mul2) * g2y;
     dmean = dmean + dL_dmean;
+    if (DEPTH) {  // the depth image's share: d = view[2] x + view[6] y + view[10] z + view[14]
+      const float gd = acc_col.w;
+      dmean = dmean + V3{view[2] * gd, view[6] * gd, view[10] * gd};
+    }
 
     if (a.shs != nullptr) {
       // computeColorFromSH (backward), backward.cu:20-139
@@ -1273,8 +1282,10 @@ hipError_t launch_view_messages_accumulate(hipStream_t s, int64_t P, int D, int 
 }
 hipError_t launch_preprocess_backward(hipStream_t s, const PreBwdArgs& a) {
   const int nb = (a.P + GAUSS_BLOCK - 1) / GAUSS_BLOCK;
-  if (a.row_state != nullptr) hipLaunchKernelGGL(preprocess_backward_kernel<true>, dim3(nb), dim3(GAUSS_BLOCK), 0, s, a);
-  else hipLaunchKernelGGL(preprocess_backward_kernel<false>, dim3(nb), dim3(GAUSS_BLOCK), 0, s, a);
+  if (a.row_state != nullptr && a.depth) return hipErrorInvalidValue;  // (gsr_preprocess_backward_rows takes no depth)
+  if (a.row_state != nullptr) hipLaunchKernelGGL((preprocess_backward_kernel<true, false>), dim3(nb), dim3(GAUSS_BLOCK), 0, s, a);
+  else if (a.depth) hipLaunchKernelGGL((preprocess_backward_kernel<false, true>), dim3(nb), dim3(GAUSS_BLOCK), 0, s, a);
+  else hipLaunchKernelGGL((preprocess_backward_kernel<false, false>), dim3(nb), dim3(GAUSS_BLOCK), 0, s, a);
   return hipGetLastError();
 }
 

@@ -36,7 +36,8 @@ def attach_grad_allocator(output: torch.Tensor, fn) -> None:
 
 
 def _flags(flags) -> int:
-    return options.current_flags() if flags is None else int(flags)
+    # (FLAG_DEPTH_GRAD never reaches the library as a bit: a backward with a depth gradient calls the _depth entry points)
+    return (options.current_flags() if flags is None else int(flags)) & ~options.FLAG_DEPTH_GRAD
 
 
 def _require_cuda(t: torch.Tensor, name: str) -> None:
@@ -286,7 +287,8 @@ def _alloc(fn, name: str, shape, zero: bool, dev) -> torch.Tensor:
 
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
                                  viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
-                                 geomBuffer, R, binningBuffer, imageBuffer, debug, flags=None, grad_allocator=None):
+                                 geomBuffer, R, binningBuffer, imageBuffer, debug, flags=None, grad_allocator=None,
+                                 dL_dout_depth=None):
     """RasterizeGaussiansBackwardCUDA, rasterize_points.cu:97-157 ->
     (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D | None, dL_dsh, dL_dscales, dL_drotations).
     `flags` (extension, keyword): the flags the forward of this view ran with; None = options.current_flags().
@@ -305,7 +307,10 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
       "row_state"          shape (P,): a uint8 tensor here says that "means2D", "opacities", "means3D", "sh" / "sh_rgb",
                            "scales" and "rotations" were answered with tensors the allocator keeps across calls, with this
                            per-Gaussian state next to them (include/gsr.h: gsr_preprocess_backward_rows): rows that still
-                           hold the zeros of an earlier call are not rewritten."""
+                           hold the zeros of an earlier call are not rewritten.
+    `dL_dout_depth` (extension, keyword): (1,H,W) gradient of the depth output, or None (the reference: the depth image
+    carries no gradient).  Given, the backward also differentiates the depth image (include/gsr.h: GSR_FLAG_DEPTH_GRAD,
+    gsr_backward_depth); not with the "row_state" mode (gsr_preprocess_backward_rows takes no depth gradient)."""
     flags = _flags(flags)
     dev = means3D.device
     P = int(means3D.size(0))
@@ -322,6 +327,12 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                                                     _f32(rotations, "rotations", dev),
                                                     _f32(cov3D_precomp, "cov3D_precomp", dev), _f32(sh, "sh", dev))
     dL_dpix = _f32(dL_dout_color, "dL_dout_color", dev)
+    dL_ddepth = None
+    if dL_dout_depth is not None:
+        dL_ddepth = _f32(dL_dout_depth, "dL_dout_depth", dev)
+        if dL_ddepth.numel() != H * W or dL_ddepth.device != dev:
+            raise RuntimeError(f"diff_gaussian_rasterization: `dL_dout_depth` must be a (1, {H}, {W}) tensor on {dev}, "
+                               f"got {tuple(dL_ddepth.shape)} on {dL_ddepth.device}")
     _on_device(radii, "radii", dev, torch.int32)
     for name, buf in (("geomBuffer", geomBuffer), ("binningBuffer", binningBuffer), ("imageBuffer", imageBuffer)):
         _on_device(buf, name, dev, torch.uint8)
@@ -357,6 +368,9 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     if row_state is not None and not (isinstance(row_state, torch.Tensor) and row_state.dtype == torch.uint8 and
                                       row_state.numel() == P and row_state.is_contiguous() and row_state.device == dev):
         row_state = None
+    if row_state is not None and dL_ddepth is not None:
+        raise RuntimeError("diff_gaussian_rasterization: depth gradients are not supported with persistent gradient rows "
+                           "(the grad_allocator's \"row_state\" mode)")
     # Which table?  The one kept across backwards on this stream: zero on entry, zeroed again by K8+K9 -- no clear (nobody reads
     # the table between K7 and K8+K9: the exchange routes plan their messages from K7's `touched` mask, handed to
     # after_blend_backward).  With an allocator's own table or persistent rows: a table cleared by K7's own launch.
@@ -392,6 +406,15 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                 _ptr(dL_dsh) if dL_drgb is None else None, None if dL_drgb is None else dL_drgb.data_ptr(),
                 dL_dscales.data_ptr() if has_scales else None, dL_drotations.data_ptr() if has_scales else None,
                 row_state.data_ptr()))
+        elif dL_drgb is None and dL_ddepth is not None:
+            _native.check("gsr_backward_depth", L.gsr_backward_depth(
+                _stream(dev), P, int(degree), M, int(R), W, H, background.data_ptr(), means3D.data_ptr(), _ptr(sh),
+                _ptr(colors), _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp),
+                viewmatrix.data_ptr(), projmatrix.data_ptr(), _ptr(campos), float(tan_fovx), float(tan_fovy),
+                radii.data_ptr(), geomBuffer.data_ptr(), _ptr(binningBuffer), imageBuffer.data_ptr(), dL_dpix.data_ptr(),
+                dL_ddepth.data_ptr(), acc.data_ptr(), dL_dmeans2D.data_ptr(), dL_dopacity.data_ptr(), col_out,
+                dL_dmeans3D.data_ptr(), _ptr(dL_dcov3D), _ptr(dL_dsh), dL_dscales.data_ptr() if has_scales else None,
+                dL_drotations.data_ptr() if has_scales else None, bwd_flags))
         elif dL_drgb is None:
             _native.check("gsr_backward", L.gsr_backward(
                 _stream(dev), P, int(degree), M, int(R), W, H, background.data_ptr(), means3D.data_ptr(), _ptr(sh),
@@ -404,10 +427,16 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
         else:
             # (also when nothing was rendered: the call then only clears the accumulator table)
             touched = torch.empty(((P + 15) // 16) * 16, dtype=torch.uint8, device=dev)  # K7 clears it and marks the rows it adds to
-            _native.check("gsr_blend_backward", L.gsr_blend_backward(
-                _stream(dev), P, int(R), W, H, background.data_ptr(), geomBuffer.data_ptr(), _ptr(binningBuffer),
-                imageBuffer.data_ptr(), dL_dpix.data_ptr(), acc.data_ptr(), touched.data_ptr(),
-                bwd_flags & ~options.FLAG_ACC_SELF_CLEAN))
+            if dL_ddepth is None:
+                _native.check("gsr_blend_backward", L.gsr_blend_backward(
+                    _stream(dev), P, int(R), W, H, background.data_ptr(), geomBuffer.data_ptr(), _ptr(binningBuffer),
+                    imageBuffer.data_ptr(), dL_dpix.data_ptr(), acc.data_ptr(), touched.data_ptr(),
+                    bwd_flags & ~options.FLAG_ACC_SELF_CLEAN))
+            else:
+                _native.check("gsr_blend_backward_depth", L.gsr_blend_backward_depth(
+                    _stream(dev), P, int(R), W, H, background.data_ptr(), geomBuffer.data_ptr(), _ptr(binningBuffer),
+                    imageBuffer.data_ptr(), dL_dpix.data_ptr(), dL_ddepth.data_ptr(), acc.data_ptr(), touched.data_ptr(),
+                    bwd_flags & ~options.FLAG_ACC_SELF_CLEAN))
             # notification (no allocation): K7 is enqueued, K8+K9 not yet -- multiview.py starts the exchange of the
             # touched-row counts here (from K7's row mask), so that it and the host's wait for it run underneath K8+K9
             grad_alloc("after_blend_backward", touched[:P], False)
@@ -417,7 +446,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                 float(tan_fovx), float(tan_fovy), radii.data_ptr(), geomBuffer.data_ptr(), acc.data_ptr(),
                 dL_dmeans2D.data_ptr(), dL_dopacity.data_ptr(), dL_dmeans3D.data_ptr(), _ptr(dL_dcov3D), dL_drgb.data_ptr(),
                 dL_dscales.data_ptr() if has_scales else None, dL_drotations.data_ptr() if has_scales else None,
-                options.FLAG_ACC_SELF_CLEAN if persist else 0))
+                (options.FLAG_ACC_SELF_CLEAN if persist else 0) | (options.FLAG_DEPTH_GRAD if dL_ddepth is not None else 0)))
         if debug:
             torch.cuda.synchronize(dev)
     if persist:  # both halves are enqueued: in stream order the table is all zero again

@@ -100,12 +100,13 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out_color, grad_radii, grad_depth, grad_aux=None):
-        # grad_radii / grad_depth are ignored exactly as in the reference (:137, :155-177):
-        # depth is a forward-only output.
+        # grad_radii is ignored exactly as in the reference (:137, :155-177); so is grad_depth -- depth is a forward-only
+        # output -- unless this render ran with FLAG_DEPTH_GRAD (gaussianeditor_amd.set_depth_grad)
         rs = ctx.raster_settings
         (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
          imgBuffer) = ctx.saved_tensors
-        if grad_out_color is None:  # only the (gradient-free) depth output was used downstream
+        depth_grad = _depth_grad(ctx.gsr_flags, grad_depth)
+        if grad_out_color is None:  # only the depth output was used downstream
             grad_out_color = torch.zeros((3, rs.image_height, rs.image_width), dtype=torch.float32, device=means3D.device)
         # argument order of _C.rasterize_gaussians_backward (rasterize_points.h:38-60)
         args = (rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
@@ -114,12 +115,23 @@ class _RasterizeGaussians(torch.autograd.Function):
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
          grad_rotations) = _call_native(
              lambda *a: _C.rasterize_gaussians_backward(*a, flags=ctx.gsr_flags,
-                                                        grad_allocator=getattr(ctx, "gsr_grad_allocator", None)),
+                                                        grad_allocator=getattr(ctx, "gsr_grad_allocator", None),
+                                                        **_depth_kw(depth_grad)),
              args, rs.debug, "snapshot_bw.dump",
              "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
         # one slot per forward() input (:213-225)
         return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
                 grad_cov3Ds_precomp, None, None)
+
+
+def _depth_grad(flags, grad_depth):
+    """The depth image's gradient a backward passes on: only for a render that ran with FLAG_DEPTH_GRAD."""
+    return grad_depth if (flags & _options.FLAG_DEPTH_GRAD) and grad_depth is not None else None
+
+
+def _depth_kw(depth_grad):
+    # (the keyword only where there is a depth gradient: without one the call is today's, to any `_C` backend)
+    return {} if depth_grad is None else {"dL_dout_depth": depth_grad}
 
 
 class _ReusedRender(torch.autograd.Function):
@@ -148,6 +160,7 @@ class _ReusedRender(torch.autograd.Function):
     def backward(ctx, grad_out_color, grad_radii, grad_depth):
         rs, flags = ctx.raster_settings, ctx.gsr_flags
         means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp = ctx.saved_tensors
+        depth_grad = _depth_grad(flags, grad_depth)
         if grad_out_color is None:
             grad_out_color = torch.zeros((3, rs.image_height, rs.image_width), dtype=torch.float32, device=means3D.device)
         fwd = _C.rasterize_gaussians(rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier,
@@ -158,7 +171,7 @@ class _ReusedRender(torch.autograd.Function):
          grad_rotations) = _C.rasterize_gaussians_backward(
              rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
              rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, sh, rs.sh_degree, rs.campos, geomBuffer, num_rendered,
-             binningBuffer, imgBuffer, rs.debug, flags=flags)
+             binningBuffer, imgBuffer, rs.debug, flags=flags, **_depth_kw(depth_grad))
         return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
                 grad_cov3Ds_precomp, None, None)
 

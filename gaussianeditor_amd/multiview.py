@@ -304,7 +304,8 @@ def render_view_grads(settings: GaussianRasterizationSettings, means3D, opacitie
     """Forward + backward of ONE view (the L0 entry points the drop-in L1 API calls) with `dL_dcolor` as the
     pixel gradient.  Returns (color, radii, depth, grads) where grads has the six
     rasterizer-input gradients (views of `bucket` when one is given).  `after_forward(radii)` is called between the
-    forward and the backward (multiview_step starts the radii's MAX all-reduce there, so that it overlaps the backward)."""
+    forward and the backward (multiview_step starts the radii's MAX all-reduce there, so that it overlaps the backward).
+    The depth image takes no gradient on this route, whatever gaussianeditor_amd.set_depth_grad says."""
     state = _view_forward(settings, means3D, opacities, shs, scales, rotations)
     color, radii, depth, _ = state
     if after_forward is not None:
@@ -517,7 +518,7 @@ def multiview_step(settings: GaussianRasterizationSettings, params: Dict[str, to
     """One data-parallel iteration for this rank's view: forward, backward, gradient all-reduce.
     `params`: xyz, opacity, features, scaling, rotation (activated, as the rasterizer consumes them).
     After the call `bucket.views[...]` hold the batch-summed gradients on every rank and
-    `radii` the batch-max radii."""
+    `radii` the batch-max radii.  No depth gradient: the loss is the colour image's alone (render_view_grads)."""
     pending = []
 
     def start_radii(radii):  # known after the forward: the collective runs while the backward computes
@@ -603,7 +604,8 @@ def multiview_batch_step(settings_list, params: Dict[str, torch.Tensor], dL_dcol
 
     The bucket must be in the "rgb" exchange mode (the messages carry the colour gradient; the SH gradient is rebuilt).
     Returns (colors, radii, depths, grads): lists for this rank's views, the batch-max radii, and the batch-summed gradients
-    (`bucket.views`).  `bucket.last_counts` holds the touched rows of all K views, `bucket.last_exchange` what was sent."""
+    (`bucket.views`).  `bucket.last_counts` holds the touched rows of all K views, `bucket.last_exchange` what was sent.
+    No depth gradient: the loss is the colour images' alone (render_view_grads)."""
     k_local = len(settings_list)
     if k_local < 1 or len(dL_dcolor_list) != k_local:
         raise ValueError("multiview_batch_step: one pixel gradient per local view, at least one view")

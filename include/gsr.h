@@ -60,13 +60,17 @@ extern "C" {
  * instead of four arrays, and gsr_preprocess_backward* copies dL_dmeans2D / dL_dopacity (/ dL_dcolors) out of it: the
  * signatures of gsr_backward, gsr_blend_backward, gsr_preprocess_backward{,_rgb,_rows}, gsr_view_message_plan_blend and
  * gsr_debug_blend_backward_profile changed. */
-/* 6 (round 6): adds gsr_preprocess_begin / gsr_preprocess_end (nothing else changed). */
+/* 6 (round 6): adds gsr_preprocess_begin / gsr_preprocess_end (nothing else changed).  Later, purely additive (the number
+ * stays): GSR_FLAG_DEPTH_GRAD, the GSR_ACC_DEPTH column, gsr_blend_backward_depth and gsr_backward_depth -- every earlier
+ * entry point keeps its signature and its behaviour. */
 #define GSR_ABI_VERSION 6
 /* The blend backward's accumulator table: GSR_ACC_ROW floats (one 64-byte line) per Gaussian, 64-byte aligned.  Columns:
  *   [GSR_ACC_MEAN2D] .x [+1] .y of dL_dmean2D      (backward.cu:545-546)
  *   [GSR_ACC_OPACITY] dL_dopacity                  (backward.cu:554)
  *   [GSR_ACC_CONIC] .x [+1] .y [+3] .w of dL_dconic (backward.cu:549-551; the reference's float4 layout, .z unused)
  *   [GSR_ACC_COLOR .. +2] dL_dcolor                (backward.cu:523)
+ *   [GSR_ACC_DEPTH] dL_ddepth, the gradient of the Gaussian's view-space depth: sum over pixels of alpha T dL_dout_depth
+ *       (written by gsr_blend_backward_depth only; no reference counterpart)
  * every other column stays zero.  Why one row: float atomics execute at the memory side on this chip and cost per REQUEST;
  * the lanes of a wave instruction that fall into one 64-byte line travel as one request, so the (up to nine) adds of a
  * (tile, Gaussian) pair leave as one instead of nine (tools/microbench/atomic_merge.hip: 8.8x). */
@@ -75,6 +79,7 @@ extern "C" {
 #define GSR_ACC_OPACITY 3
 #define GSR_ACC_CONIC 4
 #define GSR_ACC_COLOR 8
+#define GSR_ACC_DEPTH 11
 /* Largest image the blend BACKWARD accepts, in 16 x 16 tiles (its work items carry the tile id in 20 bits). */
 #define GSR_MAX_TILES (1 << 20)
 
@@ -148,6 +153,13 @@ int gsr_scratch_sizes(int P, int64_t R, int64_t G, int W, int H, size_t sizes[3]
  *                        SIMD instead of 4, which leaves wave slots and registers for the other stream's kernels (a rank
  *                        that renders several views of a batch: -15 % per view, profiles/r04_c_pipelining.md).  Never
  *                        changes a result.  The environment knob GSR_BLEND_WAVES_PER_SIMD, where set, takes precedence.
+ *   GSR_FLAG_DEPTH_GRAD  (read by gsr_preprocess_backward / _rgb; accepted by gsr_blend_backward_depth / gsr_backward_depth,
+ *                        which imply it) the backward also differentiates the depth image out_depth = sum_i d_i alpha_i T_i
+ *                        (background 0; d_i = view-space z): K7 adds sum alpha T dL_dout_depth into GSR_ACC_DEPTH and folds
+ *                        d_i dL_dout_depth into dL/dalpha, K8+K9 adds dL_ddepth * (view[2], view[6], view[10]) to
+ *                        dL_dmeans3D.  The reference has no such gradient.  Only the backward entry points above accept
+ *                        this bit; the forward / trace entry points, gsr_blend_backward and gsr_backward refuse it (a caller
+ *                        keeps it to itself until the backward).
  * Unknown bits are rejected with GSR_ERR_BAD_ARGUMENT. */
 #define GSR_FLAG_TILE_BOUNDS_ALPHA 1u
 #define GSR_FLAG_FAST_EXP 2u
@@ -155,7 +167,8 @@ int gsr_scratch_sizes(int P, int64_t R, int64_t G, int W, int H, size_t sizes[3]
 #define GSR_FLAG_FORWARD_ONLY 8u
 #define GSR_FLAG_SHARED_SIMDS 16u
 #define GSR_FLAG_ACC_SELF_CLEAN 32u
-#define GSR_FLAG_ALL 63u
+#define GSR_FLAG_DEPTH_GRAD 64u
+#define GSR_FLAG_ALL 127u
 
 /* Number of sort-key bits, 32 + getHigherMsb(tiles) (rasterizer_impl.cu:36-49, 253). */
 int gsr_sort_key_bits(int W, int H);
@@ -278,7 +291,27 @@ int gsr_preprocess_backward(void* stream, int P, int D, int M, int W, int H, con
                             const float* campos, float tan_fovx, float tan_fovy, const int32_t* radii,
                             const void* geom, float* acc, float* dL_dmeans2D, float* dL_dopacity,
                             float* dL_dcolors, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
-                            float* dL_dscales, float* dL_drots, unsigned flags /* 0 | GSR_FLAG_ACC_SELF_CLEAN */);
+                            float* dL_dscales, float* dL_drots,
+                            unsigned flags /* 0 | GSR_FLAG_ACC_SELF_CLEAN | GSR_FLAG_DEPTH_GRAD */);
+
+/* Depth gradients (opt-in, GSR_FLAG_DEPTH_GRAD): gsr_blend_backward / gsr_backward with one more input,
+ *   dL_ddepth (1,H,W): the gradient of out_depth of gsr_blend_forward.
+ * gsr_blend_backward_depth also writes GSR_ACC_DEPTH of `acc`; then gsr_preprocess_backward(_rgb) with GSR_FLAG_DEPTH_GRAD
+ * reads it (without the flag the column is ignored, and with GSR_FLAG_ACC_SELF_CLEAN not cleaned: pass the flag).
+ * gsr_backward_depth == gsr_blend_backward_depth followed by gsr_preprocess_backward(flags | GSR_FLAG_DEPTH_GRAD).  The
+ * work list of these backwards has no list segments (the forward's checkpoints hold no depth): views with long lists take
+ * longer than gsr_blend_backward.  flags: as gsr_blend_backward / gsr_backward, plus GSR_FLAG_DEPTH_GRAD (optional). */
+int gsr_blend_backward_depth(void* stream, int P, int64_t R, int W, int H, const float* bg, const void* geom,
+                             const void* binning, const void* image, const float* dL_dpix, const float* dL_ddepth, float* acc,
+                             uint8_t* touched, unsigned flags);
+int gsr_backward_depth(void* stream, int P, int D, int M, int64_t R, int W, int H, const float* bg, const float* means3D,
+                       const float* shs, const float* colors_precomp, const float* scales, float scale_modifier,
+                       const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                       const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy, const int32_t* radii,
+                       const void* geom, const void* binning, const void* image, const float* dL_dpix,
+                       const float* dL_ddepth, float* acc, float* dL_dmeans2D, float* dL_dopacity, float* dL_dcolors,
+                       float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drots,
+                       unsigned flags);
 
 /* Multi-GPU exchange support (gaussianeditor_amd/multiview.py).  Per view the SH gradient is
  * rank one, dL_dsh[k] = c_k(dir) * dL_dRGB with dir = normalize(mean - campos) (backward.cu:44-98), so ranks exchange
@@ -294,7 +327,8 @@ int gsr_preprocess_backward_rgb(void* stream, int P, int D, int M, int W, int H,
                                 const float* campos, float tan_fovx, float tan_fovy, const int32_t* radii,
                                 const void* geom, float* acc, float* dL_dmeans2D, float* dL_dopacity,
                                 float* dL_dmeans3D, float* dL_dcov3D, float* dL_drgb,
-                                float* dL_dscales, float* dL_drots, unsigned flags /* 0 | GSR_FLAG_ACC_SELF_CLEAN */);
+                                float* dL_dscales, float* dL_drots,
+                                unsigned flags /* 0 | GSR_FLAG_ACC_SELF_CLEAN | GSR_FLAG_DEPTH_GRAD */);
 
 /* The same kernel for gradient arrays the caller keeps ACROSS calls (a training loop's gradient bucket).  A view leaves
  * nine Gaussians of ten with all-zero gradients (culled, or blended by no pixel), and rewriting those zeros is most of
