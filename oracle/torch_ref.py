@@ -17,9 +17,15 @@ Conventions that make autograd reproduce the reference's analytic backward
   * `means2D` is an explicit zero offset added to the projected mean in
     "NDC-scaled pixel units" so that its gradient equals dL_dmean2D
     (backward.cu:545-546: the 0.5*W, 0.5*H factors).
-Gaussians whose view-space x/z or y/z is clamped to 1.3*tanfov (forward.cu:82-87)
-are differentiated by the reference with the clamped value treated as a constant
-in dL/dtz; test scenes keep all Gaussians inside that cone.
+  * off-cone Gaussians: where the view-space |x/z| exceeds 1.3*tanfovx, the forward
+    (forward.cu:82-87) uses tx = clamp(x/z)*tz, and the analytic backward
+    (backward.cu:168-176, 262-263) zeroes dL/dtx (x_grad_mul) and differentiates J02
+    by tz with that clamped tx held constant.  Here tx is that clamped value,
+    DETACHED, which gives autograd exactly that derivative; likewise for y.  Inside
+    the cone tx is the view-space x itself.
+The discrete decisions (alpha >= 1/255, power <= 0, T < 1e-4) are taken in float64
+here and in float32 by the kernels; `stats` returns this side's per-pixel n_contrib
+and final T so that a test can find the pixels where the two disagree.
 """
 from __future__ import annotations
 
@@ -55,7 +61,7 @@ def _sh_to_rgb(D: int, shs: torch.Tensor, dirs: torch.Tensor) -> torch.Tensor:
 
 def render_f64(struct: Dict[str, np.ndarray], means3D, means2D, opacities, scales, rotations, shs, colors_precomp,
                cov3D_precomp, viewmatrix, projmatrix, campos, bg, W: int, H: int, tanfovx: float, tanfovy: float,
-               scale_modifier: float = 1.0, sh_degree: int = 0, dL_dimage=None) -> torch.Tensor:
+               scale_modifier: float = 1.0, sh_degree: int = 0, dL_dimage=None, stats=None) -> torch.Tensor:
     """Differentiable colour image (3,H,W) in float64.
 
     `dL_dimage` (3,H,W): the gradient of a loss by the image.  The backward then runs INSIDE this call, tile by tile (a
@@ -66,6 +72,9 @@ def render_f64(struct: Dict[str, np.ndarray], means3D, means2D, opacities, scale
     struct: dict from oracle.cpu.forward() supplying `point_list`, `ranges`, `radii`.
     Tensor arguments are float64 torch tensors (requires_grad as desired); pass
     None for absent optionals exactly like the L1 API.
+    `stats`: a dict that receives `n_contrib` (H*W int64: the number of list entries processed up to and including the
+    last blended one, as the kernels' n_contrib), `final_T` (H*W float64), `stopped` (H*W bool: the pixel ended on
+    T < 1e-4, not on the end of its list) and `saturated` (the number of blended (pixel, instance) pairs with o*G > 0.99).
     """
     dt = torch.float64
     V = viewmatrix.to(dt)  # flat[4c+r] = W2C[r][c]  ->  V[c, r]
@@ -95,8 +104,10 @@ def render_f64(struct: Dict[str, np.ndarray], means3D, means2D, opacities, scale
     fx, fy = W / (2.0 * tanfovx), H / (2.0 * tanfovy)
     tz = p_view[:, 2]
     limx, limy = 1.3 * tanfovx, 1.3 * tanfovy
-    tx = torch.clamp(p_view[:, 0] / tz, -limx, limx) * tz
-    ty = torch.clamp(p_view[:, 1] / tz, -limy, limy) * tz
+    txtz, tytz = p_view[:, 0] / tz, p_view[:, 1] / tz
+    offx, offy = (txtz.abs() > limx).detach(), (tytz.abs() > limy).detach()
+    tx = torch.where(offx, (torch.clamp(txtz, -limx, limx) * tz).detach(), p_view[:, 0])
+    ty = torch.where(offy, (torch.clamp(tytz, -limy, limy) * tz).detach(), p_view[:, 1])
     zero = torch.zeros_like(tz)
     J = torch.stack([fx / tz, zero, -(fx * tx) / (tz * tz), zero, fy / tz, -(fy * ty) / (tz * tz)], dim=1).reshape(P, 2, 3)
     Rv = V[:3, :3].transpose(0, 1)  # W2C rotation
@@ -134,6 +145,10 @@ def render_f64(struct: Dict[str, np.ndarray], means3D, means2D, opacities, scale
     ranges = struct["ranges"]
     gx, gy = (W + 15) // 16, (H + 15) // 16
     out = torch.zeros(3, H, W, dtype=dt)
+    n_contrib = torch.zeros(H, W, dtype=torch.int64)
+    final_T = torch.ones(H, W, dtype=dt)
+    stopped_px = torch.zeros(H, W, dtype=torch.bool)
+    saturated = 0
     bgd = bg.to(dt)
     for tile in range(gx * gy):
         r0, r1 = int(ranges[tile, 0]), int(ranges[tile, 1])
@@ -166,6 +181,13 @@ def render_f64(struct: Dict[str, np.ndarray], means3D, means2D, opacities, scale
             w = torch.where(live, alpha * Texcl, torch.zeros_like(alpha))
             Tfinal = torch.where(live, one_m, torch.ones_like(one_m)).prod(dim=1)
             col = (w @ rgb[ids]).transpose(0, 1) + Tfinal[None, :] * bgd[:, None]
+            if stats is not None:
+                pos = torch.arange(1, ids.numel() + 1, dtype=torch.int64)
+                nc_tile = torch.where(live, pos[None, :], torch.zeros_like(pos)[None, :]).max(dim=1).values
+                n_contrib[ty0:ty0 + ys.numel(), tx0:tx0 + xs.numel()] = nc_tile.reshape(ys.numel(), xs.numel())
+                final_T[ty0:ty0 + ys.numel(), tx0:tx0 + xs.numel()] = Tfinal.detach().reshape(ys.numel(), xs.numel())
+                stopped_px[ty0:ty0 + ys.numel(), tx0:tx0 + xs.numel()] = stop.any(dim=1).reshape(ys.numel(), xs.numel())
+                saturated += int((live & (raw.detach() > 0.99)).sum())
         hh, ww = ys.numel(), xs.numel()
         if per_gaussian is not None:
             if col.requires_grad:
@@ -176,4 +198,9 @@ def render_f64(struct: Dict[str, np.ndarray], means3D, means2D, opacities, scale
         pairs = [(t, l.grad) for t, l in zip(per_gaussian, leaves) if l.grad is not None and t.requires_grad]
         if pairs:
             torch.autograd.backward([t for t, _ in pairs], [g for _, g in pairs])
+    if stats is not None:
+        stats["n_contrib"] = n_contrib.reshape(-1)
+        stats["final_T"] = final_T.reshape(-1)
+        stats["stopped"] = stopped_px.reshape(-1)
+        stats["saturated"] = saturated
     return out

@@ -1,0 +1,249 @@
+"""The float64 regime matrix: small scenes, each built to hit one regime of the backward where a kernel can be wrong without
+the other tests noticing, with the float64 autograd gradients (oracle/torch_ref.py) that every backward route is held to.
+
+A case is small (<= 4 000 Gaussians, <= 256x256 pixels, W and H not multiples of 16, non-zero background) so that float64
+on the CPU takes seconds.  `regime_count` asserts that the case really hits its regime and returns the count it printed: a
+change to synth.py that quietly empties a regime fails here instead of turning the comparison into a tautology.
+
+Conventions of the reference's analytic backward that the expectation follows (all documented in oracle/torch_ref.py
+except the first):
+  * dL_dscales is taken w.r.t. the MODIFIED scale scale_modifier * s (backward.cu computeCov3D: the scale_modifier factor
+    of the chain rule is left out), i.e. autograd's gradient w.r.t. s divided by scale_modifier;
+  * quaternions are not normalised (forward.cu computeCov3D, backward.cu: the gradient is w.r.t. the raw quaternion);
+  * off-cone Gaussians: the clamped tx / ty are constants (x_grad_mul / y_grad_mul).
+Rows that may be masked are counted and bounded: Gaussians under pixels whose float64 and float32 discrete decisions differ
+(helpers.flipped_pixels / gaussians_under), and Gaussians within float rounding of the 1.3 tan(fov) cone edge.
+"""
+import numpy as np
+import torch
+
+from helpers import flipped_pixels, gaussians_under, make_case, seed_gradient
+
+M = 16  # every case carries 16 SH coefficients, whatever its active degree (the editor trains with M = 16, D = 0..3)
+TOL = 2e-5
+CONE_EDGE_REL = 1e-6
+
+CASES = ["sh_D0", "sh_D1", "sh_D2", "sh_D3", "clamped_colours", "scale_mod_0.5", "scale_mod_1.7", "colors_precomp",
+         "cov3D_precomp", "both_precomp", "off_cone", "saturated", "unnormalised_quat", "depth"]
+SH_CASES = ["sh_D0", "sh_D1", "sh_D2", "sh_D3", "clamped_colours", "scale_mod_0.5", "scale_mod_1.7", "off_cone", "saturated",
+            "unnormalised_quat"]
+
+
+def _v2_case(P, W, H, seed, view=3):
+    """A synth-v2 scene seen from a ring camera inside its dome: every view from inside a scene has Gaussians beside and
+    behind the camera, and some of them beyond the 1.3 tan(fov) cone still touch the image."""
+    from gaussianeditor_amd.synth import synth_scene_v2
+
+    case = make_case(P, W, H, seed=seed, view=view, nviews=8, bg=(0.2, 0.5, 0.7))
+    case["sc"] = synth_scene_v2(P, seed=seed)
+    return case
+
+
+def regime(name):
+    """-> dict(name, case, D, sm, colors_precomp, cov3D_precomp, G, GD): the case `name` of CASES."""
+    D, sm, cols, cov, GD = 3, 1.0, None, None, None
+    if name.startswith("sh_D"):
+        D = int(name[-1])
+        case = make_case(3000, 200, 136, seed=21 + D, s0=0.04, view=1, scale_xyz=0.8, bg=(0.2, 0.5, 0.7))
+    elif name == "clamped_colours":
+        case = make_case(3000, 184, 120, seed=31, s0=0.04, view=2, scale_xyz=0.8, bg=(0.3, 0.1, 0.6))
+        f = case["sc"]["features"].clone()
+        f[:, 0] -= 1.5  # the DC term pulls rgb = 0.28 * dc + 0.5 + ... below zero for a good share of the channels
+        case["sc"]["features"] = f.contiguous()
+    elif name.startswith("scale_mod_"):
+        sm = float(name.split("_")[-1])
+        case = make_case(2500, 168, 152, seed=41 if sm < 1 else 42, s0=0.05, view=0, scale_xyz=0.8, bg=(0.2, 0.5, 0.7))
+    elif name in ("colors_precomp", "cov3D_precomp", "both_precomp"):
+        from oracle import cpu
+
+        case = make_case(2500, 200, 120, seed=51, s0=0.05, view=3, scale_xyz=0.8, bg=(0.2, 0.5, 0.7))
+        if name != "cov3D_precomp":
+            cols = torch.rand(2500, 3, generator=torch.Generator().manual_seed(52)).contiguous()
+        if name != "colors_precomp":
+            sc = case["sc"]
+            # a generic symmetric positive definite 6-vector: the computed covariance of the scene, not an input the
+            # kernels could special-case
+            cov = torch.from_numpy(cpu.forward(sc["xyz"], sc["scaling"], sc["rotation"], sc["opacity"], sc["features"], None,
+                                               None, case["cam"].world_view_transform, case["cam"].full_proj_transform,
+                                               case["cam"].camera_center, case["bg"], case["W"], case["H"], case["tfx"],
+                                               case["tfy"], 1.0, 3)["cov3D"].copy())
+    elif name == "off_cone":
+        case = _v2_case(4000, 216, 120, seed=11)
+    elif name == "saturated":
+        # o in [0.998, 0.9999]: o*G > 0.99 within ~0.14 sigma of a centre.  A pixel stops after two such instances, so the
+        # saturated pairs are a fixed small share of the image whatever the density: hence the larger image
+        case = make_case(800, 248, 200, seed=61, s0=0.1, view=1, scale_xyz=0.7, bg=(0.2, 0.5, 0.7))
+        u = torch.rand(800, 1, generator=torch.Generator().manual_seed(62))
+        case["sc"]["opacity"] = (0.998 + 0.0019 * u).contiguous()
+    elif name == "unnormalised_quat":
+        case = make_case(3000, 200, 136, seed=71, s0=0.025, view=2, scale_xyz=0.8, bg=(0.2, 0.5, 0.7))
+        g = torch.Generator().manual_seed(72)
+        norms = torch.exp(torch.empty(3000, 1).uniform_(float(np.log(0.5)), float(np.log(2.0)), generator=g))
+        case["sc"]["rotation"] = (case["sc"]["rotation"] * norms).contiguous()
+    elif name == "depth":
+        case = _v2_case(4000, 200, 136, seed=13, view=5)
+        GD = seed_gradient(136, 200, 81)[:1] * 136 * 200
+    else:
+        raise KeyError(name)
+    case["D"] = D
+    H, W = case["H"], case["W"]
+    G = seed_gradient(H, W, 7 + len(name)) * H * W
+    return dict(name=name, case=case, D=D, sm=sm, colors_precomp=cols, cov3D_precomp=cov, G=G, GD=GD)
+
+
+def grad_keys(r):
+    keys = ["dL_dmeans3D", "dL_dmeans2D", "dL_dopacity"]
+    keys += ["dL_dsh"] if r["colors_precomp"] is None else ["dL_dcolors"]
+    keys += ["dL_dscales", "dL_drotations"] if r["cov3D_precomp"] is None else ["dL_dcov3D"]
+    return keys
+
+
+def oracle_run(O, r):
+    """The float32 oracle's forward and backward of the case -> (forward dict, gradient dict).  The depth case's gradients
+    are those of <G, C> + <GD, D>, by the linearity construction of depth_helpers."""
+    from helpers import oracle_backward, oracle_forward
+
+    kw = dict(colors_precomp=r["colors_precomp"], cov3D_precomp=r["cov3D_precomp"], D=r["D"], scale_modifier=r["sm"])
+    f = oracle_forward(O, r["case"], **kw)
+    if r["GD"] is not None:
+        from depth_helpers import depth_expectation
+
+        return f, depth_expectation(O, r["case"], r["G"], r["GD"], **kw)
+    return f, oracle_backward(O, r["case"], f, r["G"], **kw)
+
+
+def f64_run(f, r):
+    """float64 autograd of the case's loss, the discrete structure (tile lists) taken from the float32 forward `f`.
+    -> (gradient dict in the reference's conventions, stats of render_f64, image)."""
+    from oracle.torch_ref import render_f64
+
+    case, d = r["case"], torch.float64
+    sc, cam = case["sc"], case["cam"]
+    P, W, H = sc["xyz"].shape[0], case["W"], case["H"]
+    leaf = lambda t: t.to(d).clone().requires_grad_(True)  # noqa: E731
+    xyz, op, m2 = leaf(sc["xyz"]), leaf(sc["opacity"]), torch.zeros(P, 3, dtype=d, requires_grad=True)
+    leaves = dict(dL_dmeans3D=xyz, dL_dmeans2D=m2, dL_dopacity=op)
+    sh = cols = scl = rot = cov = None
+    if r["colors_precomp"] is None:
+        sh = leaves["dL_dsh"] = leaf(sc["features"])
+    else:
+        cols = leaves["dL_dcolors"] = leaf(r["colors_precomp"])
+    if r["cov3D_precomp"] is None:
+        scl, rot = leaves["dL_dscales"], leaves["dL_drotations"] = leaf(sc["scaling"]), leaf(sc["rotation"])
+    else:
+        cov = leaves["dL_dcov3D"] = leaf(r["cov3D_precomp"])
+    geo = (cam.world_view_transform, cam.full_proj_transform, cam.camera_center)
+    stats = {}
+    img = render_f64(f, xyz, m2, op, scl, rot, sh, cols, cov, *geo, case["bg"], W, H, case["tfx"], case["tfy"], r["sm"], r["D"],
+                     dL_dimage=r["G"].to(d), stats=stats)
+    if r["GD"] is not None:
+        # the depth image is the colour image of colours (tz, 0, 0) on background 0: tz = view-space z, differentiable
+        V = cam.world_view_transform.to(d).reshape(4, 4)
+        tz = xyz @ V[:3, 2] + V[3, 2]
+        dcol = torch.stack([tz, torch.zeros_like(tz), torch.zeros_like(tz)], dim=1)
+        gd = torch.zeros(3, H, W, dtype=d)
+        gd[0] = r["GD"].to(d).reshape(H, W)
+        render_f64(f, xyz, m2, op, scl, rot, None, dcol, cov, *geo, torch.zeros(3), W, H, case["tfx"], case["tfy"], r["sm"],
+                   r["D"], dL_dimage=gd)
+    want = {k: (t.grad if t.grad is not None else torch.zeros_like(t)).numpy() for k, t in leaves.items()}
+    if "dL_dscales" in want:
+        want["dL_dscales"] = want["dL_dscales"] / r["sm"]  # w.r.t. the modified scale (module docstring)
+    return want, stats, img
+
+
+def view_ratios(r):
+    """float64 view-space (x/z, y/z) of every Gaussian and the cone limits 1.3 tan(fov)."""
+    case, d = r["case"], torch.float64
+    P = case["sc"]["xyz"].shape[0]
+    pv = torch.cat([case["sc"]["xyz"].to(d), torch.ones(P, 1, dtype=d)], 1) @ case["cam"].world_view_transform.to(d)
+    return (pv[:, 0] / pv[:, 2]).numpy(), (pv[:, 1] / pv[:, 2]).numpy(), 1.3 * case["tfx"], 1.3 * case["tfy"]
+
+
+def off_cone_rows(r):
+    xz, yz, lx, ly = view_ratios(r)
+    return (np.abs(xz) > lx) | (np.abs(yz) > ly)
+
+
+def cone_edge_rows(r):
+    """Rows within float rounding of the cone edge: float32 and float64 may disagree on which side they are."""
+    xz, yz, lx, ly = view_ratios(r)
+    return (np.abs(np.abs(xz) - lx) < CONE_EDGE_REL * lx) | (np.abs(np.abs(yz) - ly) < CONE_EDGE_REL * ly)
+
+
+def masked_rows(r, f, stats):
+    """-> (mask, report): the rows a comparison with float64 may leave out, counted and bounded here."""
+    P, W = r["case"]["sc"]["xyz"].shape[0], r["case"]["W"]
+    N = W * r["case"]["H"]
+    flips = flipped_pixels(stats["n_contrib"].numpy(), stats["final_T"].numpy(), f["n_contrib"], f["final_T"])
+    under = gaussians_under(flips, W, f, stats["n_contrib"].numpy())
+    edge = cone_edge_rows(r) & (f["radii"] > 0)
+    assert flips.size <= 4 + 2e-4 * N, (r["name"], flips.size)
+    assert under.sum() <= 0.02 * P + 64, (r["name"], int(under.sum()))
+    assert edge.sum() <= 4, (r["name"], int(edge.sum()))
+    return under | edge, f"flipped pixels {flips.size} of {N}, Gaussians under them {int(under.sum())}, on the cone edge {int(edge.sum())}"
+
+
+def regime_count(r, f, want, stats, got=None):
+    """Assert that the case hits its regime; print and return the count.  `got`: the gradients under test (the SH cases
+    check that the coefficients beyond (D+1)^2 are exactly zero in them: the binding allocates dL_dsh with torch.empty)."""
+    name, vis = r["name"], f["radii"] > 0
+    P = vis.shape[0]
+    if name.startswith("sh_D") or (got is not None and "dL_dsh" in got and r["colors_precomp"] is None):
+        n_act = (r["D"] + 1) ** 2
+        if got is not None:
+            tail = np.asarray(got["dL_dsh"]).reshape(P, M, 3)[:, n_act:]
+            assert not np.any(tail != 0), (name, "dL_dsh beyond (D+1)^2 not zero", int((tail != 0).sum()))
+    if name.startswith("sh_D"):
+        if r["D"] < 3:
+            n = P * (M - n_act) * 3  # entries that must be exactly zero
+            assert not np.any(want["dL_dsh"].reshape(P, M, 3)[:, n_act:] != 0)
+        else:
+            n = int((np.abs(want["dL_dsh"].reshape(P, M, 3)[:, 9:]).max(axis=(1, 2)) > 0).sum())  # rows using degree 3
+        assert n > 0
+    elif name == "clamped_colours":
+        n = int(f["clamped"][vis].any(axis=1).sum())
+        assert n >= 0.1 * vis.sum(), (n, int(vis.sum()))
+    elif name.startswith("scale_mod_"):
+        n = int((np.abs(want["dL_dscales"]).max(axis=1) > 0).sum())
+        assert n > 100
+    elif name in ("colors_precomp", "cov3D_precomp", "both_precomp"):
+        n = 0
+        for k in ("dL_dcolors", "dL_dcov3D"):
+            if k in want:
+                c = int((np.abs(want[k]).max(axis=1) > 0).sum())
+                assert c > 100, (name, k, c)
+                if got is not None:
+                    assert k in got and np.abs(np.asarray(got[k])).max() > 0, (name, k)
+                n += c
+    elif name in ("off_cone", "depth"):
+        n = int((off_cone_rows(r) & vis).sum())
+        assert n >= 50, (name, n)
+        if name == "depth":
+            assert np.abs(r["GD"]).max() > 0
+    elif name == "saturated":
+        n = int(stats["saturated"])
+        stopped = int(stats["stopped"].sum())
+        assert n > 100 and stopped > 100, (n, stopped)
+    elif name == "unnormalised_quat":
+        q = r["case"]["sc"]["rotation"].double()
+        n = int(((q.norm(dim=1) - 1).abs() > 0.1).numpy()[vis].sum())
+        assert n > 100
+        # the forward's covariance is that of the RAW quaternion, not of the normalised one (computeCov3D)
+        s = r["case"]["sc"]["scaling"].double() * r["sm"]
+
+        def cov6(q):
+            w, x, y, z = q.unbind(1)
+            R = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
+                             2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+                             2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], 1).reshape(-1, 3, 3)
+            Mm = R * s[:, None, :]
+            S = Mm @ Mm.transpose(1, 2)
+            return torch.stack([S[:, 0, 0], S[:, 0, 1], S[:, 0, 2], S[:, 1, 1], S[:, 1, 2], S[:, 2, 2]], 1).numpy()
+        raw, unit = cov6(q)[vis], cov6(q / q.norm(dim=1, keepdim=True))[vis]
+        got_cov = f["cov3D"][vis].astype(np.float64)
+        assert np.abs(got_cov - raw).max() <= 1e-5 * np.abs(raw).max()
+        assert np.abs(got_cov - unit).max() > 1e-2 * np.abs(unit).max()
+    else:
+        raise KeyError(name)
+    print(f"[{name}] regime count {n}")
+    return n

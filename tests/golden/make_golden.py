@@ -11,6 +11,13 @@ modules (only possible where /root/reference exists; the fixtures themselves are
                   compiled out of the reference file and run on a stub holding `_xyz`, so none of the module's GPU-only
                   imports are needed) -> pins the oracle's near_points / get_near_gaussians_by_mask
     near_method.npz  the same method of the reference on two more seeded clouds (tests/test_cpu_near.py)
+    cov3d.npz     reference `build_rotation` / `build_scaling_rotation` / `strip_symmetric` (utils/general_utils.py), composed
+                  as GaussianModel.setup_functions does (scene/gaussian_model.py:42-46), in float64 on the CPU, on seeded
+                  unit quaternions and scales with scaling_modifier 0.5, 1 and 1.7 -> pins the 3D covariance of K1 and
+                  gsr_debug_cov3d
+    sh_clamped.npz  the colour the reference's renderer computes when it evaluates the SHs in Python,
+                  clamp_min(eval_sh + 0.5, 0) (gaussian_renderer/__init__.py:112-118), degrees 0..3, on seeded inputs
+                  whose DC term clamps a good share of the channels -> pins K1's rgb and its `clamped` flags
     reference_{render,point_cloud_render,optimizer_surgery}.npz, reference_save_ply.ply
                   the reference's render / point_cloud_render / camera2rasterizer, optimizer surgery and save_ply run as
                   written on the drop-in (tests/test_cpu_reference_modules.py holds the functions that ran them)
@@ -76,6 +83,8 @@ def main():
     print("wrote", os.path.join(HERE, "sh_eval.npz"), os.path.join(HERE, "cameras.npz"))
     near_points_fixture()
     near_method_fixture()
+    cov3d_fixture()
+    sh_clamped_fixture(sh_utils)
     reference_modules_fixtures()
 
 
@@ -118,6 +127,57 @@ def near_points_fixture():
     out["nn_dist"], out["nn_idx"] = dist.numpy(), idx.numpy()
     np.savez_compressed(os.path.join(HERE, "near_points.npz"), **out)
     print("wrote", os.path.join(HERE, "near_points.npz"), {k: int(out[k].sum()) for k in ("mask", "near0", "near1", "near2")})
+
+
+COV3D_MODIFIERS = (0.5, 1.0, 1.7)
+
+
+def cov3d_fixture():
+    """cov3d.npz: the reference's covariance composition on the CPU in float64.  Its helpers allocate with
+    device="cuda" and dtype=torch.float; the shim they are compiled against allocates float64 CPU tensors instead."""
+    import types
+
+    path = os.path.join(REF, "utils", "general_utils.py")
+    shim = types.SimpleNamespace(zeros=lambda *shape, dtype=None, device=None: torch.zeros(*shape, dtype=torch.float64),
+                                 sqrt=torch.sqrt, float=torch.float64)
+    globs = {"torch": shim}
+    for name in ("strip_lowerdiag", "strip_symmetric", "build_rotation", "build_scaling_rotation"):
+        reference_method(path, name, globs)
+    build_cov = reference_method(os.path.join(REF, "scene", "gaussian_model.py"), "setup_functions", dict(
+        torch=torch, build_scaling_rotation=globs["build_scaling_rotation"], strip_symmetric=globs["strip_symmetric"],
+        inverse_sigmoid=None))
+
+    class Stub:
+        pass
+
+    stub = Stub()
+    build_cov(stub)
+    g = torch.Generator().manual_seed(31)
+    P = 1024
+    rot = torch.nn.functional.normalize(torch.randn(P, 4, generator=g, dtype=torch.float64), dim=-1).float()
+    scl = torch.exp(math.log(0.03) + 0.8 * torch.randn(P, 3, generator=g, dtype=torch.float64)).float()
+    out = {"rotation": rot.numpy(), "scaling": scl.numpy(), "modifiers": np.array(COV3D_MODIFIERS)}
+    for i, sm in enumerate(COV3D_MODIFIERS):
+        # (the float32 inputs the kernels read, widened: the fixture is the float64 covariance of exactly those)
+        out[f"cov3D_{i}"] = stub.covariance_activation(scl.double(), sm, rot.double()).numpy()
+    np.savez_compressed(os.path.join(HERE, "cov3d.npz"), **out)
+    print("wrote", os.path.join(HERE, "cov3d.npz"))
+
+
+def sh_clamped_fixture(sh_utils):
+    """sh_clamped.npz: clamp_min(eval_sh + 0.5, 0), the Python colour path of the reference's renderer."""
+    g = torch.Generator().manual_seed(2025)
+    P = 512
+    shs = torch.randn(P, 16, 3, generator=g) * 0.4
+    shs[:, 0] = torch.randn(P, 3, generator=g) * 2.0  # DC: rgb = 0.28 * dc + 0.5 + ... is negative for ~20 % of the channels
+    dirs = torch.nn.functional.normalize(torch.randn(P, 3, generator=g), dim=-1)
+    out = {"shs": shs.numpy(), "dirs": dirs.numpy()}
+    for deg in range(4):
+        sh2rgb = sh_utils.eval_sh(deg, shs.transpose(1, 2), dirs)
+        out[f"rgb_clamped_deg{deg}"] = torch.clamp_min(sh2rgb + 0.5, 0.0).numpy()
+        out[f"rgb_deg{deg}"] = sh2rgb.numpy()
+    np.savez_compressed(os.path.join(HERE, "sh_clamped.npz"), **out)
+    print("wrote", os.path.join(HERE, "sh_clamped.npz"))
 
 
 NEAR_METHOD_CASES = ((2000, 0.1), (5000, 0.04))

@@ -95,6 +95,36 @@ def rel_err(a, b):
     return float(np.abs(a - b).max() / max(1e-30, np.abs(b).max())) if a.size else 0.0
 
 
+def flipped_pixels(nc_a, ft_a, nc_b, ft_b):
+    """Pixels whose discrete blend decisions differ between two implementations: a different last contributor, or a
+    final transmittance that differs by more than rounding (one skipped / extra alpha >= 1/255 entry moves it by
+    >= 0.4 %)."""
+    nc_a, nc_b = nc_a.reshape(-1).astype(np.int64), nc_b.reshape(-1).astype(np.int64)
+    ft_a, ft_b = ft_a.reshape(-1).astype(np.float64), ft_b.reshape(-1).astype(np.float64)
+    rel = np.abs(ft_a - ft_b) / np.maximum(np.maximum(np.abs(ft_a), np.abs(ft_b)), 1e-30)
+    return np.nonzero((nc_a != nc_b) | (rel > 1e-4))[0]
+
+
+def gaussians_under(pixels, W, f, nc_other):
+    """Mask of the Gaussians that are blended at one of `pixels` (flat indices) by either implementation: the entries
+    of the pixel's tile list up to its last contributor whose alpha there reaches the threshold (with some slack)."""
+    P = f["radii"].shape[0]
+    mask = np.zeros(P, bool)
+    gx = (W + 15) // 16
+    nc_a, nc_b = f["n_contrib"].reshape(-1), np.asarray(nc_other).reshape(-1)
+    for p in pixels.tolist():
+        px, py = p % W, p // W
+        lo, hi = (int(v) for v in f["ranges"][(py // 16) * gx + px // 16])
+        n = max(int(nc_a[p]), int(nc_b[p]))
+        ids = f["point_list"][lo:min(hi, lo + n)].astype(np.int64)
+        co, m = f["conic_opacity"][ids].astype(np.float64), f["means2D"][ids].astype(np.float64)
+        dx, dy = m[:, 0] - px, m[:, 1] - py
+        power = -0.5 * (co[:, 0] * dx * dx + co[:, 2] * dy * dy) - co[:, 1] * dx * dy
+        alpha = co[:, 3] * np.exp(np.minimum(power, 0.0))
+        mask[ids[(power <= 1e-6) & (alpha >= 0.5 / 255.0)]] = True
+    return mask
+
+
 ROW_REL, ROW_FLOOR, ROW_FRACTION = 1e-3, 1e-7, 1e-3
 
 
@@ -146,7 +176,8 @@ def v2_fuzz_case(seed):
     return case, sm, D
 
 
-__all__ = ["make_case", "oracle_forward", "oracle_backward", "settings", "hip_state", "rel_err", "seed_gradient", "v2_fuzz_case"]
+__all__ = ["make_case", "oracle_forward", "oracle_backward", "settings", "hip_state", "rel_err", "seed_gradient", "v2_fuzz_case",
+           "flipped_pixels", "gaussians_under", "assert_grads_close"]
 
 
 # ---- the reference's own sources compiled for gfx950 (oracle/_ref): presence is LOUD when asked for ----

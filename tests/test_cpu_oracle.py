@@ -234,11 +234,64 @@ def test_backward_matches_float64_autograd_on_thin_disks(oracle):
     assert np.abs(img.detach().float().numpy() - f["color"]).max() < 5e-6
     (img * G.to(d)).sum().backward()
     # rows whose view-space x/z or y/z is clamped (forward.cu:82-87) are differentiated with the clamped value as a constant
-    # by the reference's analytic backward, not by autograd: compared on the rows inside the cone
+    # (oracle/torch_ref.py reproduces that convention): every row is compared, except the few within float rounding of the
+    # cone edge, where float32 and float64 may disagree on the side
     pv = torch.cat([sc["xyz"].to(d), torch.ones(P, 1, dtype=d)], 1) @ cam.world_view_transform.to(d)
-    inside = (((pv[:, 0] / pv[:, 2]).abs() <= 1.3 * case["tfx"]) & ((pv[:, 1] / pv[:, 2]).abs() <= 1.3 * case["tfy"])).numpy()
-    assert inside.sum() > 50
+    rx, ry = (pv[:, 0] / pv[:, 2]).abs().numpy(), (pv[:, 1] / pv[:, 2]).abs().numpy()
+    lx, ly = 1.3 * case["tfx"], 1.3 * case["tfy"]
+    edge = (np.abs(rx - lx) < 1e-6 * lx) | (np.abs(ry - ly) < 1e-6 * ly)
+    off = ((rx > lx) | (ry > ly)) & (f["radii"] > 0)
+    print(f"off-cone visible rows {int(off.sum())}, rows on the cone edge (masked) {int(edge.sum())}")
+    assert edge.sum() <= 2 and off.sum() > 0
     for k, t, scale in (("dL_dmeans3D", ins["xyz"], 1.0), ("dL_dmeans2D", m2, 1.0), ("dL_dopacity", ins["opacity"], 1.0),
                         ("dL_dscales", ins["scaling"], 1.0 / sm), ("dL_drotations", ins["rotation"], 1.0), ("dL_dsh", ins["features"], 1.0)):
-        a, b = g[k].reshape(P, -1)[inside], (t.grad.numpy() * scale).reshape(P, -1)[inside]
+        a, b = g[k].reshape(P, -1)[~edge], (t.grad.numpy() * scale).reshape(P, -1)[~edge]
         assert rel_err(a, b) < 3e-5, k
+
+
+def _sphere_view(P):
+    """Points on a sphere of radius 3 around campos = 0, seen from a camera 10 units away: all in front of it and on
+    screen (as in test_sh_matches_reference_eval_sh)."""
+    from gaussianeditor_amd.synth import look_at_camera
+
+    cam = look_at_camera([0.0, 0.0, -10.0], [0.0, 0.0, 0.0], 64, 64, fovy_deg=60.0)
+    return cam.world_view_transform.numpy(), cam.full_proj_transform.numpy(), math.tan(cam.FoVy / 2)
+
+
+def test_cov3d_matches_reference_build_scaling_rotation(oracle):
+    """Golden: the reference's build_rotation / build_scaling_rotation / strip_symmetric, composed as
+    GaussianModel.setup_functions does, in float64 (cov3d.npz) pin the oracle's 3D covariance at scaling_modifier 0.5, 1, 1.7
+    to 1e-6 of each covariance's largest entry (the float32 op order differs from the reference's)."""
+    g = np.load(os.path.join(GOLD, "cov3d.npz"))
+    rot, scl = g["rotation"], g["scaling"]
+    P = rot.shape[0]
+    rng = np.random.default_rng(3)
+    means = (rng.standard_normal((P, 3)) * 0.5).astype(np.float32)
+    view, proj, tf = _sphere_view(P)
+    for i, sm in enumerate(g["modifiers"]):
+        geom = oracle.preprocess(means, scl, rot, np.full((P, 1), 0.5, np.float32), np.zeros((P, 16, 3), np.float32), None,
+                                 None, view, proj, np.zeros(3, np.float32), 64, 64, tf, tf, float(sm), 0)
+        vis = geom["radii"] > 0
+        assert vis.sum() > 0.9 * P
+        want = g[f"cov3D_{i}"][vis]
+        err = np.abs(geom["cov3D"][vis].astype(np.float64) - want).max(axis=1) / np.abs(want).max(axis=1)
+        assert err.max() <= 1e-6, (float(sm), float(err.max()))
+
+
+def test_clamped_colour_matches_reference_renderer(oracle):
+    """Golden: clamp_min(eval_sh + 0.5, 0) of the reference's renderer (sh_clamped.npz, about a fifth of the channels
+    clamped) pins the oracle's rgb and `clamped` flags; the flags may differ only where |rgb + 0.5| < 1e-6."""
+    g = np.load(os.path.join(GOLD, "sh_clamped.npz"))
+    shs, dirs = g["shs"], g["dirs"]
+    P = shs.shape[0]
+    view, proj, tf = _sphere_view(P)
+    for deg in range(4):
+        geom = oracle.preprocess((dirs * 3.0).astype(np.float32), np.full((P, 3), 0.01, np.float32),
+                                 np.tile([1, 0, 0, 0], (P, 1)).astype(np.float32), np.full((P, 1), 0.5, np.float32), shs, None,
+                                 None, view, proj, np.zeros(3, np.float32), 64, 64, tf, tf, 1.0, deg)
+        assert (geom["radii"] > 0).all()
+        ref, raw = g[f"rgb_clamped_deg{deg}"], g[f"rgb_deg{deg}"] + 0.5
+        assert 0.1 < (raw < 0).mean() < 0.4
+        assert np.abs(geom["rgb"] - ref).max() <= 2e-6
+        differ = geom["clamped"].astype(bool) != (raw < 0)
+        assert not differ.any() or np.abs(raw[differ]).max() < 1e-6

@@ -144,7 +144,7 @@ def test_apply_weights_vs_reference(oracle, P, W, H, s0, C, big):
     differs between libm's exp (reference) and gsr_expf (here) -- those pixels are found by comparing the two forward
     renders' n_contrib / final_T, counted and bounded; the float weights agree to the atomics' re-association."""
     from gaussianeditor_amd.diff_gaussian_rasterization import GaussianRasterizer
-    from test_gpu_round2 import _flipped_pixels, _gaussians_under
+    from helpers import flipped_pixels as _flipped_pixels, gaussians_under as _gaussians_under
 
     case = make_case(P, W, H, seed=11 if not big else 0, s0=s0, view=0, nviews=8 if big else 4,
                      bg=(0.0, 0.0, 0.0))

@@ -19,6 +19,8 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import flipped_pixels as _flipped_pixels
+from helpers import gaussians_under as _gaussians_under
 from helpers import hip_state, make_case, oracle_backward, oracle_forward, rel_err, seed_gradient, settings
 
 pytestmark = pytest.mark.gpu
@@ -37,69 +39,51 @@ def _ref(variant="nofma"):
     return require_ref(variant).Reference(variant, DEV)
 
 
-def _product(case, G, flags=None):
+def _product(case, G, flags=None, D=None, scale_modifier=1.0, colors_precomp=None, cov3D_precomp=None):
     """Forward + backward of the HIP path through the L1 API -> (color, radii, state dict, grads dict of numpy)."""
     from gaussianeditor_amd import options
     from gaussianeditor_amd.diff_gaussian_rasterization import GaussianRasterizer, _C
 
     sc, cam = case["sc"], case["cam"]
     P, W, H = sc["xyz"].shape[0], case["W"], case["H"]
+    D = case["D"] if D is None else D
     ctx = options.override(flags) if flags is not None else options.override(options.current_flags())
     with ctx:
         leaf = lambda t: t.to(DEV).clone().requires_grad_(True)  # noqa: E731
-        xyz, op, sh, scl, rot = leaf(sc["xyz"]), leaf(sc["opacity"]), leaf(sc["features"]), leaf(sc["scaling"]), leaf(sc["rotation"])
+        xyz, op = leaf(sc["xyz"]), leaf(sc["opacity"])
         m2d = torch.zeros_like(xyz, requires_grad=True)
-        color, radii, depth = GaussianRasterizer(settings(case, DEV))(xyz, m2d, op, shs=sh, scales=scl, rotations=rot)
+        kw, leaves = {}, dict(dL_dmeans3D=xyz, dL_dopacity=op, dL_dmeans2D=m2d)
+        if colors_precomp is None:
+            kw["shs"] = leaves["dL_dsh"] = leaf(sc["features"])
+        else:
+            kw["colors_precomp"] = leaves["dL_dcolors"] = leaf(colors_precomp)
+        if cov3D_precomp is None:
+            kw["scales"] = leaves["dL_dscales"] = leaf(sc["scaling"])
+            kw["rotations"] = leaves["dL_drotations"] = leaf(sc["rotation"])
+        else:
+            kw["cov3D_precomp"] = leaves["dL_dcov3D"] = leaf(cov3D_precomp)
+        color, radii, depth = GaussianRasterizer(settings(case, DEV, D=D, scale_modifier=scale_modifier))(xyz, m2d, op, **kw)
         (color * G.to(DEV)).sum().backward()
         # the internal per-pixel state, from a second (deterministic) forward through the _C layer
         e = torch.empty(0, device=DEV)
-        d = lambda t: t.to(DEV)  # noqa: E731
+        d = lambda t: e if t is None else t.to(DEV)  # noqa: E731
+        sh_in = d(sc["features"]) if colors_precomp is None else e
+        scl_in, rot_in = (d(sc["scaling"]), d(sc["rotation"])) if cov3D_precomp is None else (e, e)
         R, c2, _, _, geom, binning, img = _C.rasterize_gaussians(
-            d(case["bg"]), d(sc["xyz"]), e, d(sc["opacity"]), d(sc["scaling"]), d(sc["rotation"]), 1.0, e,
-            d(cam.world_view_transform), d(cam.full_proj_transform), case["tfx"], case["tfy"], H, W, d(sc["features"]),
-            case["D"], d(cam.camera_center), False, False)
+            d(case["bg"]), d(sc["xyz"]), d(colors_precomp), d(sc["opacity"]), scl_in, rot_in, scale_modifier, d(cov3D_precomp),
+            d(cam.world_view_transform), d(cam.full_proj_transform), case["tfx"], case["tfy"], H, W, sh_in, D,
+            d(cam.camera_center), False, False)
         assert torch.equal(c2, color.detach())
         st = hip_state(P, R, W, H, geom, binning, img)
     torch.cuda.synchronize()
-    grads = dict(dL_dmeans3D=_np(xyz.grad), dL_dopacity=_np(op.grad), dL_dsh=_np(sh.grad), dL_dscales=_np(scl.grad),
-                 dL_drotations=_np(rot.grad), dL_dmeans2D=_np(m2d.grad))
+    grads = {k: _np(v.grad) for k, v in leaves.items()}
     return _np(color), _np(depth), _np(radii), R, st, grads
-
-
-def _flipped_pixels(nc_a, ft_a, nc_b, ft_b):
-    """Pixels whose discrete blend decisions differ between two implementations: a different last contributor, or a
-    final transmittance that differs by more than rounding (one skipped / extra alpha >= 1/255 entry moves it by
-    >= 0.4 %)."""
-    nc_a, nc_b = nc_a.reshape(-1).astype(np.int64), nc_b.reshape(-1).astype(np.int64)
-    ft_a, ft_b = ft_a.reshape(-1).astype(np.float64), ft_b.reshape(-1).astype(np.float64)
-    rel = np.abs(ft_a - ft_b) / np.maximum(np.maximum(np.abs(ft_a), np.abs(ft_b)), 1e-30)
-    return np.nonzero((nc_a != nc_b) | (rel > 1e-4))[0]
-
-
-def _gaussians_under(pixels, W, f, nc_other):
-    """Mask of the Gaussians that are blended at one of `pixels` (flat indices) by either implementation: the entries
-    of the pixel's tile list up to its last contributor whose alpha there reaches the threshold (with some slack)."""
-    P = f["radii"].shape[0]
-    mask = np.zeros(P, bool)
-    gx = (W + 15) // 16
-    nc_a, nc_b = f["n_contrib"].reshape(-1), np.asarray(nc_other).reshape(-1)
-    for p in pixels.tolist():
-        px, py = p % W, p // W
-        lo, hi = (int(v) for v in f["ranges"][(py // 16) * gx + px // 16])
-        n = max(int(nc_a[p]), int(nc_b[p]))
-        ids = f["point_list"][lo:min(hi, lo + n)].astype(np.int64)
-        co, m = f["conic_opacity"][ids].astype(np.float64), f["means2D"][ids].astype(np.float64)
-        dx, dy = m[:, 0] - px, m[:, 1] - py
-        power = -0.5 * (co[:, 0] * dx * dx + co[:, 2] * dy * dy) - co[:, 1] * dx * dy
-        alpha = co[:, 3] * np.exp(np.minimum(power, 0.0))
-        mask[ids[(power <= 1e-6) & (alpha >= 0.5 / 255.0)]] = True
-    return mask
 
 
 ROW_REL, ROW_FLOOR, ROW_FRACTION = 1e-3, 1e-7, 1e-3
 
 
-def _assert_grads(tag, got, want, masked, tol=1e-5):
+def _assert_grads(tag, got, want, masked, tol=1e-5, keys=GRADS):
     """Two bars per gradient tensor (rows = Gaussians, `masked` rows reported but not asserted):
       1. max |a - b| <= tol * max|b|                      -- the tensor-wide bar of north_star (1e-5);
       2. per ROW: |a - b| <= ROW_FLOOR * max|b| + ROW_REL * |b_row|  -- so that a Gaussian whose own gradient is a tiny
@@ -108,7 +92,7 @@ def _assert_grads(tag, got, want, masked, tol=1e-5):
          per-pixel atomics in the reference), so a FEW rows may exceed the per-row bar by rounding alone: at most
          ROW_FRACTION of the rows may, and none of them by more than bar 1."""
     worst = 0.0
-    for k in GRADS:
+    for k in keys:
         a = got[k].reshape(got[k].shape[0], -1).astype(np.float64)
         b = want[k].reshape(a.shape).astype(np.float64)
         scale = max(np.abs(b).max(), 1e-30)
@@ -151,26 +135,65 @@ def test_three_way_parity_forward_and_backward(oracle, P, W, H, s0, seed, D):
     three_way(oracle, case, G, D)
 
 
-def three_way(oracle, case, G, D):
+# the backward regimes of tests/f64_regimes.py at a moderate size: 20 k Gaussians, 248 x 232
+REGIME_CASES = ["sh_D0", "sh_D1", "sh_D2", "scale_mod_0.5", "scale_mod_1.7", "colors_precomp", "cov3D_precomp", "off_cone"]
+
+
+@pytest.mark.parametrize("regime", REGIME_CASES)
+def test_three_way_parity_backward_regimes(oracle, regime):
+    """three_way beyond D = 3, scale_modifier = 1, SH colours and computed covariances: active degrees 0..2 with 16
+    coefficients, scale modifiers 0.5 / 1.7, precomputed colours, precomputed covariances, and a camera inside a synth-v2
+    scene (off-cone Gaussians: x_grad_mul / y_grad_mul of backward.cu)."""
+    from gaussianeditor_amd.synth import synth_scene_v2
+
+    P, W, H = 20000, 248, 232
+    D, sm, cols, cov = 3, 1.0, None, None
+    if regime == "off_cone":
+        case = make_case(P, W, H, seed=11, view=3, nviews=8, bg=(0.2, 0.5, 0.7))
+        case["sc"] = synth_scene_v2(P, seed=11)
+    else:
+        case = make_case(P, W, H, seed=5, s0=0.025, view=1, scale_xyz=0.8, bg=(0.2, 0.5, 0.7))
+    if regime.startswith("sh_D"):
+        D = int(regime[-1])
+    elif regime.startswith("scale_mod_"):
+        sm = float(regime.split("_")[-1])
+    elif regime == "colors_precomp":
+        cols = torch.rand(P, 3, generator=torch.Generator().manual_seed(6)).contiguous()
+    elif regime == "cov3D_precomp":
+        cov = torch.from_numpy(oracle_forward(oracle, case)["cov3D"].copy())
+    case["D"] = D
+    G = seed_gradient(H, W, 9) * H * W
+    three_way(oracle, case, G, D, scale_modifier=sm, colors_precomp=cols, cov3D_precomp=cov)
+
+
+def three_way(oracle, case, G, D, scale_modifier=1.0, colors_precomp=None, cov3D_precomp=None):
     """The body of the three-way test for any case dictionary (tests/helpers.py: make_case) -- also run on the synth-v2
-    scenes by tests/test_gpu_round5.py."""
+    scenes by tests/test_gpu_round5.py.  `D` is the active SH degree (the scene's features may hold more coefficients);
+    with `colors_precomp` / `cov3D_precomp` the SH / scales and rotations are not passed and dL_dcolors / dL_dcov3D are
+    compared instead."""
     sc, cam = case["sc"], case["cam"]
     P, W, H = sc["xyz"].shape[0], case["W"], case["H"]
     N = W * H
+    shs = sc["features"] if colors_precomp is None else None
+    scl, rot = (sc["scaling"], sc["rotation"]) if cov3D_precomp is None else (None, None)
+    keys = ["dL_dmeans3D", "dL_dopacity", "dL_dmeans2D"]
+    keys += ["dL_dsh"] if colors_precomp is None else ["dL_dcolors"]
+    keys += ["dL_dscales", "dL_drotations"] if cov3D_precomp is None else ["dL_dcov3D"]
     # --- the reference itself
     R_ = _ref("nofma")
-    r = R_.forward(sc["xyz"], sc["scaling"], sc["rotation"], sc["opacity"], sc["features"], None, None,
+    r = R_.forward(sc["xyz"], scl, rot, sc["opacity"], shs, colors_precomp, cov3D_precomp,
                    cam.world_view_transform, cam.full_proj_transform, cam.camera_center, case["bg"], W, H, case["tfx"],
-                   case["tfy"], 1.0, D)
+                   case["tfy"], scale_modifier, D)
     gr = {k: _np(v) for k, v in R_.backward(G).items()}
     r_np = {k: _np(v) for k, v in r.items() if isinstance(v, torch.Tensor)}
     del R_
     torch.cuda.empty_cache()
     # --- the oracle
-    f = oracle_forward(oracle, case)
-    go = oracle_backward(oracle, case, f, G)
+    kw = dict(colors_precomp=colors_precomp, cov3D_precomp=cov3D_precomp, D=D, scale_modifier=scale_modifier)
+    f = oracle_forward(oracle, case, **kw)
+    go = oracle_backward(oracle, case, f, G, **kw)
     # --- the product
-    color, depth, radii, R, st, gp = _product(case, G)
+    color, depth, radii, R, st, gp = _product(case, G, **kw)
 
     # integers / indices: bit exact, three ways
     assert r["num_rendered"] == f["num_rendered"] == R
@@ -179,7 +202,7 @@ def three_way(oracle, case, G, D):
     assert np.array_equal(r_np["point_list"].view(np.uint32), f["point_list"]) and np.array_equal(st["point_list"], f["point_list"])
     assert np.array_equal(r_np["ranges"].view(np.uint32), f["ranges"]) and np.array_equal(st["ranges"], f["ranges"])
     vis = f["radii"] > 0
-    for k in ("means2D", "depths", "conic_opacity", "rgb"):
+    for k in ("means2D", "depths", "conic_opacity") + (("rgb",) if colors_precomp is None else ()):
         assert np.array_equal(r_np[k][vis], f[k][vis]), k  # same IEEE operations in the same order
     # product vs oracle forward: bit exact (same exp by specification)
     assert np.array_equal(st["n_contrib"], f["n_contrib"]) and np.array_equal(st["final_T"], f["final_T"])
@@ -195,7 +218,7 @@ def three_way(oracle, case, G, D):
           f"colour max diff outside them {dc[:, keep].max():.2e} (with them {dc.max():.2e})")
     assert flips.size <= 4 + 2e-4 * N
     assert dc[:, keep].max() <= 1e-5
-    cmax = max(1.0, float(np.abs(f["rgb"][vis]).max()))
+    cmax = max(1.0, float(np.abs(f["rgb"][vis] if colors_precomp is None else _np(colors_precomp)[vis]).max()))
     assert dc.max() <= 2.1 * cmax / 255.0 + 1e-5  # a flipped 1/255 decision moves a pixel by at most ~alpha (c + C_behind)
     # the depth image (north_star: "RGB/depth ... within 1e-5"; forward.cu:359, 377) against the reference's own, same bar,
     # relative to the largest depth of the view (depths are O(distance to the scene), colours O(1))
@@ -208,9 +231,9 @@ def three_way(oracle, case, G, D):
     masked = _gaussians_under(flips, W, f, r_np["n_contrib"].view(np.uint32))
     print(f"  Gaussians under flipped pixels (masked): {int(masked.sum())} of {P}")
     assert masked.sum() <= 0.02 * P + 64
-    _assert_grads("oracle vs reference(nofma)", go, gr, masked)
-    _assert_grads("product vs reference(nofma)", gp, gr, masked)
-    _assert_grads("product vs oracle", gp, go, np.zeros(P, bool))
+    _assert_grads("oracle vs reference(nofma)", go, gr, masked, keys=keys)
+    _assert_grads("product vs reference(nofma)", gp, gr, masked, keys=keys)
+    _assert_grads("product vs oracle", gp, go, np.zeros(P, bool), keys=keys)
 
 
 class _PC:
