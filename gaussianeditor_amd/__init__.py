@@ -85,6 +85,24 @@ def get_depth_grad() -> bool:
     return bool(options.default_flags() & options.FLAG_DEPTH_GRAD)
 
 
+def set_antialiasing(on: bool) -> None:
+    """Opt-in: the default of GSR_FLAG_ANTIALIAS (include/gsr.h) -- the opacity-compensated 2D filter of antialiased
+    3DGS rasterizers.  Every Gaussian is blended with opacity * h, h = sqrt(max(2.5e-5, det(S) / det(S + 0.3 I))) of its
+    undilated screen-space covariance S, so a sub-pixel Gaussian keeps its integrated weight instead of spreading its full
+    opacity over the 0.3 px^2 dilation.  Turn it on for a scene trained with such a rasterizer.  Off (default): the
+    reference's image.  Read once by a render's forward and reused by that render's backward."""
+    from . import options
+
+    f = options.default_flags() & ~options.FLAG_ANTIALIAS
+    options.set_default_flags(f | (options.FLAG_ANTIALIAS if on else 0))
+
+
+def get_antialiasing() -> bool:
+    from . import options
+
+    return bool(options.default_flags() & options.FLAG_ANTIALIAS)
+
+
 def set_view_reuse(on: bool) -> None:
     """View reuse (default on; `GSR_VIEW_REUSE=0` in the environment turns it off): a colour-override render of the view
     the rasterizer rendered last -- the reference's second `render(..., override_color=...)` of every training view and

@@ -350,7 +350,8 @@ extern "C" {
 int gsr_abi_version(void) { return GSR_ABI_VERSION; }
 
 // The flags the forward / trace entry points, gsr_blend_backward and gsr_backward accept: all but GSR_FLAG_DEPTH_GRAD, which
-// only the depth backwards and K8+K9 read (include/gsr.h)
+// only the depth backwards and K8+K9 read (include/gsr.h).  GSR_FLAG_ANTIALIAS is among them: K1 and K8+K9 read it, the blend /
+// trace entry points accept it and ignore it (what they blend is already the effective opacity)
 static constexpr unsigned VIEW_FLAGS = GSR_FLAG_ALL & ~GSR_FLAG_DEPTH_GRAD;
 
 const char* gsr_status_string(int status) {
@@ -445,6 +446,7 @@ int preprocess_begin_impl(hipStream_t s, int P, int D, int M, const float* means
   a.skip_color = skip_color;
   a.forward_only = (flags & GSR_FLAG_FORWARD_ONLY) ? 1 : 0;
   a.tile_bounds = (flags & GSR_FLAG_TILE_BOUNDS_ALPHA) ? 1 : 0;
+  a.antialias = (flags & GSR_FLAG_ANTIALIAS) ? 1 : 0;
   a.radii = radii;
   a.g = carve_geom(geom, P);
   note_geom(geom, a.forward_only != 0);
@@ -726,7 +728,7 @@ static int preprocess_backward_impl(void* stream, int P, int D, int M, int W, in
                                     const void* geom, const float* acc, float* dL_dmeans2D, float* dL_dopacity,
                                     float* dL_dcolors, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
                                     float* dL_drgb, float* dL_dscales, float* dL_drots, uint8_t* row_state = nullptr,
-                                    bool self_clean = false, bool depth = false) {
+                                    bool self_clean = false, bool depth = false, bool antialias = false) {
   if (P == 0) return GSR_OK;
   if (P < 0 || W <= 0 || H <= 0 || D < 0 || D > 3) return GSR_ERR_BAD_ARGUMENT;
   if (!means3D || !viewmatrix || !projmatrix || !radii || !geom) return GSR_ERR_BAD_ARGUMENT;
@@ -758,6 +760,8 @@ static int preprocess_backward_impl(void* stream, int P, int D, int M, int W, in
   pa.row_state = row_state;
   pa.acc_clean = self_clean ? const_cast<float*>(acc) : nullptr;  // (GSR_FLAG_ACC_SELF_CLEAN: the caller's table, writable by contract)
   pa.depth = depth ? 1 : 0;  // (GSR_FLAG_DEPTH_GRAD: column ACC_DEPTH enters dL_dmeans3D)
+  // (GSR_FLAG_ANTIALIAS: where K8+K9 finds rec0 -- carve_geom puts it in front of `clamped`, both sections 256-byte aligned)
+  pa.rec0_lines = antialias ? (uint32_t)(((const char*)g.clamped - (const char*)g.rec0) / 256) : 0u;
   GSR_HIP(launch_preprocess_backward((hipStream_t)stream, pa));
   return GSR_OK;
 }
@@ -796,11 +800,13 @@ int gsr_preprocess_backward(void* stream, int P, int D, int M, int W, int H, con
                             float* dL_dcolors, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
                             float* dL_dscales, float* dL_drots, unsigned flags) {
   if (shs && !dL_dsh) return GSR_ERR_BAD_ARGUMENT;
-  if (flags & ~(GSR_FLAG_ACC_SELF_CLEAN | GSR_FLAG_DEPTH_GRAD)) return GSR_ERR_BAD_ARGUMENT;  // (the two flags this half reads)
+  // (the three flags this half reads)
+  if (flags & ~(GSR_FLAG_ACC_SELF_CLEAN | GSR_FLAG_DEPTH_GRAD | GSR_FLAG_ANTIALIAS)) return GSR_ERR_BAD_ARGUMENT;
   return preprocess_backward_impl(stream, P, D, M, W, H, means3D, shs, scales, scale_modifier, rotations, cov3D_precomp,
                                   viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom, acc, dL_dmeans2D, dL_dopacity,
                                   dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, nullptr, dL_dscales, dL_drots, nullptr,
-                                  (flags & GSR_FLAG_ACC_SELF_CLEAN) != 0, (flags & GSR_FLAG_DEPTH_GRAD) != 0);
+                                  (flags & GSR_FLAG_ACC_SELF_CLEAN) != 0, (flags & GSR_FLAG_DEPTH_GRAD) != 0,
+                                  (flags & GSR_FLAG_ANTIALIAS) != 0);
 }
 
 int gsr_preprocess_backward_rgb(void* stream, int P, int D, int M, int W, int H, const float* means3D, const float* shs,
@@ -811,11 +817,12 @@ int gsr_preprocess_backward_rgb(void* stream, int P, int D, int M, int W, int H,
                                 float* dL_dmeans3D, float* dL_dcov3D, float* dL_drgb,
                                 float* dL_dscales, float* dL_drots, unsigned flags) {
   if (!shs || !dL_drgb) return GSR_ERR_BAD_ARGUMENT;
-  if (flags & ~(GSR_FLAG_ACC_SELF_CLEAN | GSR_FLAG_DEPTH_GRAD)) return GSR_ERR_BAD_ARGUMENT;
+  if (flags & ~(GSR_FLAG_ACC_SELF_CLEAN | GSR_FLAG_DEPTH_GRAD | GSR_FLAG_ANTIALIAS)) return GSR_ERR_BAD_ARGUMENT;
   return preprocess_backward_impl(stream, P, D, M, W, H, means3D, shs, scales, scale_modifier, rotations, cov3D_precomp,
                                   viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom, acc, dL_dmeans2D, dL_dopacity,
                                   nullptr, dL_dmeans3D, dL_dcov3D, nullptr, dL_drgb, dL_dscales, dL_drots, nullptr,
-                                  (flags & GSR_FLAG_ACC_SELF_CLEAN) != 0, (flags & GSR_FLAG_DEPTH_GRAD) != 0);
+                                  (flags & GSR_FLAG_ACC_SELF_CLEAN) != 0, (flags & GSR_FLAG_DEPTH_GRAD) != 0,
+                                  (flags & GSR_FLAG_ANTIALIAS) != 0);
 }
 
 int gsr_preprocess_backward_rows(void* stream, int P, int D, int M, int W, int H, const float* means3D, const float* shs,
@@ -825,11 +832,26 @@ int gsr_preprocess_backward_rows(void* stream, int P, int D, int M, int W, int H
                                  const void* geom, const float* acc, float* dL_dmeans2D, float* dL_dopacity,
                                  float* dL_dcolors, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
                                  float* dL_drgb, float* dL_dscales, float* dL_drots, uint8_t* row_state) {
+  return gsr_preprocess_backward_rows_flags(stream, P, D, M, W, H, means3D, shs, scales, scale_modifier, rotations,
+                                            cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom, acc,
+                                            dL_dmeans2D, dL_dopacity, dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_drgb,
+                                            dL_dscales, dL_drots, row_state, 0u);
+}
+
+int gsr_preprocess_backward_rows_flags(void* stream, int P, int D, int M, int W, int H, const float* means3D, const float* shs,
+                                       const float* scales, float scale_modifier, const float* rotations,
+                                       const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                                       const float* campos, float tan_fovx, float tan_fovy, const int32_t* radii,
+                                       const void* geom, const float* acc, float* dL_dmeans2D, float* dL_dopacity,
+                                       float* dL_dcolors, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
+                                       float* dL_drgb, float* dL_dscales, float* dL_drots, uint8_t* row_state, unsigned flags) {
+  if (flags & ~GSR_FLAG_ANTIALIAS) return GSR_ERR_BAD_ARGUMENT;  // (the one flag this form reads)
   if (!row_state || (dL_dsh && dL_drgb)) return GSR_ERR_BAD_ARGUMENT;
   if (shs && !dL_dsh && !dL_drgb) return GSR_ERR_BAD_ARGUMENT;
   return preprocess_backward_impl(stream, P, D, M, W, H, means3D, shs, scales, scale_modifier, rotations, cov3D_precomp,
                                   viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom, acc, dL_dmeans2D, dL_dopacity,
-                                  dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_drgb, dL_dscales, dL_drots, row_state);
+                                  dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_drgb, dL_dscales, dL_drots, row_state, false,
+                                  false, (flags & GSR_FLAG_ANTIALIAS) != 0);
 }
 
 int gsr_sh_grad_compose(void* stream, int P, int D, int M, int num_views, const float* means3D, const float* campos,
@@ -936,7 +958,7 @@ int gsr_backward(void* stream, int P, int D, int M, int64_t R, int W, int H, con
   return gsr_preprocess_backward(stream, P, D, M, W, H, means3D, shs, scales, scale_modifier, rotations, cov3D_precomp,
                                  viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom, acc, dL_dmeans2D, dL_dopacity,
                                  dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drots,
-                                 self_clean ? GSR_FLAG_ACC_SELF_CLEAN : 0u);
+                                 (self_clean ? GSR_FLAG_ACC_SELF_CLEAN : 0u) | (flags & GSR_FLAG_ANTIALIAS));
 }
 
 int gsr_backward_depth(void* stream, int P, int D, int M, int64_t R, int W, int H, const float* bg, const float* means3D,
@@ -958,7 +980,7 @@ int gsr_backward_depth(void* stream, int P, int D, int M, int64_t R, int W, int 
   return gsr_preprocess_backward(stream, P, D, M, W, H, means3D, shs, scales, scale_modifier, rotations, cov3D_precomp,
                                  viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom, acc, dL_dmeans2D, dL_dopacity,
                                  dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drots,
-                                 (self_clean ? GSR_FLAG_ACC_SELF_CLEAN : 0u) | GSR_FLAG_DEPTH_GRAD);
+                                 (self_clean ? GSR_FLAG_ACC_SELF_CLEAN : 0u) | GSR_FLAG_DEPTH_GRAD | (flags & GSR_FLAG_ANTIALIAS));
 }
 
 int gsr_mark_visible(void* stream, int P, const float* means3D, const float* viewmatrix, const float* projmatrix,

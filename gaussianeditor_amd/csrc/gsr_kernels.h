@@ -7,6 +7,8 @@ namespace gsr {
 // K1 arguments (preprocess_kernel, gsr_preprocess.hip)
 struct PreArgs {
   int P, D, M;
+  int antialias;               // GSR_FLAG_ANTIALIAS: the preprocess_kernel<MAIN, true> instantiations (opacity * h in rec0.w)
+                               // (in the padding in front of the pointers: the struct's size and layout stay what they were)
   const float* means3D;
   const float* scales;
   float scale_modifier;
@@ -39,6 +41,10 @@ struct PreBwdArgs {
   const float* scales;
   const float* rotations;
   float scale_modifier;
+  uint32_t rec0_lines;         // GSR_FLAG_ANTIALIAS: Geom::rec0 (opacity * h in .w) lies this many 256-byte lines in front of
+                               // `clamped`, in the same geometry state; 0 = flag off.  (A 4-byte offset in the padding behind
+                               // scale_modifier instead of a pointer: a larger struct moves the hidden kernel arguments, and
+                               // with them the code of every existing instantiation)
   const float* cov3D_precomp;  // (P,6) or null: then recomputed from scales / rotations as K1 did (never stored)
   const uint8_t* clamped;
   const float* dcol[3];        // Geom::dcol: d(RGB)/d(dir) left by K1, 3 floats per Gaussian each (read instead of the SH record)

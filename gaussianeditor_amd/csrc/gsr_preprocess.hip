@@ -210,7 +210,10 @@ __device__ __forceinline__ void sh_color_dir_derivatives(int D, float x, float y
 // MAIN: the training configuration -- covariance from scales / rotations, colours from SH records of 16 coefficients at degree
 // 3 -- as an instantiation of its own: with the other input modes compiled out there is no second definition of any register
 // at a join, and the waits hipcc inserts sit in front of the first USE of the early SH request instead of right behind it.
-template <bool MAIN>
+// AA (GSR_FLAG_ANTIALIAS): the opacity is scaled by h = sqrt(max(2.5e-5, det(Sigma) / det(Sigma + 0.3 I))), Sigma the
+// undilated 2D covariance: the footprint the 0.3 px^2 dilation widens keeps its integrated weight instead of gaining it.  The
+// effective opacity is what rec0.w holds and what the alpha tile bounds see; conic, radius and rectangle are unchanged.
+template <bool MAIN, bool AA>
 __global__ void __launch_bounds__(GAUSS_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))) preprocess_kernel(const PreArgs a) {
   const float* const cov3D_precomp = MAIN ? nullptr : a.cov3D_precomp;
   const float* const colors_precomp = MAIN ? nullptr : a.colors_precomp;
@@ -241,6 +244,7 @@ __global__ void __launch_bounds__(GAUSS_BLOCK) __attribute__((amdgpu_waves_per_e
   bool sh_loaded = false;
   const bool want_sh = GSR_K1_PREFETCH && !skip_color && colors_precomp == nullptr;
   float sc0 = 0.f, sc1 = 0.f, sc2 = 0.f, my_opacity = 0.f;
+  float aa_h = 1.f;  // (AA) the opacity factor h
   float4 quat = make_float4(0.f, 0.f, 0.f, 0.f);
   if (idx < a.P) {
     if (GSR_K1_PREFETCH) {
@@ -301,6 +305,10 @@ __global__ void __launch_bounds__(GAUSS_BLOCK) __attribute__((amdgpu_waves_per_e
       const float det = (cx * cz - cy * cy);
       if (det == 0.0f) break;
       const float det_inv = 1.f / det;
+      if (AA) {  // r = det(Sigma) / det(Sigma + 0.3 I); the floor also covers a det(Sigma) that rounds to <= 0
+        const float r = (cov.m[0][0] * cov.m[1][1] - cy * cy) * det_inv;
+        aa_h = sqrtf(fmaxf(2.5e-5f, r));
+      }
       conx = cz * det_inv;
       cony = -cy * det_inv;
       conz = cx * det_inv;
@@ -327,7 +335,8 @@ __global__ void __launch_bounds__(GAUSS_BLOCK) __attribute__((amdgpu_waves_per_e
         // (gsr_blend.hip: can_touch_quad), intersected with the reference's square.  An instance dropped here passes
         // `alpha < 1/255 -> continue` (forward.cu:340-344) at every pixel of its tile, so images, radii and gradients
         // do not change; num_rendered, the lists and n_contrib do.  radii keeps the reference's value.
-        const float o = GSR_K1_PREFETCH ? my_opacity : a.opacities[idx];
+        float o = GSR_K1_PREFETCH ? my_opacity : a.opacities[idx];
+        if (AA) o *= aa_h;  // (the opacity the blend kernels see)
         float hx = (float)radius_i, hy = (float)radius_i;
         if (o < 1.0f / 255.0f) {
           ntiles = 0;  // never reaches the threshold (a NaN opacity fails this test and keeps the reference rectangle)
@@ -412,7 +421,9 @@ __global__ void __launch_bounds__(GAUSS_BLOCK) __attribute__((amdgpu_waves_per_e
         }
       }
       // forward.cu:250-255
-      a.g.rec0[idx] = make_float4(conx, cony, conz, GSR_K1_PREFETCH ? my_opacity : a.opacities[idx]);
+      float o = GSR_K1_PREFETCH ? my_opacity : a.opacities[idx];
+      if (AA) o *= aa_h;
+      a.g.rec0[idx] = make_float4(conx, cony, conz, o);
       a.g.rec1[idx] = make_float4(pix, piy, my_depth, my_radius);
       a.g.rec2[idx] = col;
   }
@@ -553,7 +564,11 @@ __device__ __forceinline__ void sh_tile_store_rows(float* __restrict__ dst_rows,
 // DEPTH (GSR_FLAG_DEPTH_GRAD, not with ROWS): column ACC_DEPTH of the row -- dL/dd, d the view-space z of the mean -- adds
 // dL/dd * dd/dmean = dL/dd * (view[2], view[6], view[10]) to dL_dmeans3D (transformPoint4x3, auxiliary.h); and it is one
 // more column that decides whether a row is zero.
-template <bool ROWS, bool DEPTH>
+// AA (GSR_FLAG_ANTIALIAS, every route): K1 blended the opacity o * h, h = sqrt(max(2.5e-5, r)), r = det(Sigma) / det(Sigma + w I),
+// w = 0.3, so column ACC_OPACITY holds g = dL/d(o h).  dL_dopacity = g h; where the floor is not active, dL/dr = g o / (2 h)
+// = g rec0.w / (2 r) -- rec0.w from the geometry state, 4 bytes -- enters dL_da / dL_dc / dL_db through dr/d(x, y, z) =
+// w (y^2 + w y + z^2, x^2 + w x + z^2, -2 z (x + y + w)) / D^2, with x, y, z the undilated entries and D = det(Sigma + w I).
+template <bool ROWS, bool DEPTH, bool AA>
 __global__ void __launch_bounds__(GAUSS_BLOCK) __attribute__((amdgpu_waves_per_eu(3, 3)))
 preprocess_backward_kernel(const PreBwdArgs a) {
   __shared__ float4 sh_tile[GAUSS_BLOCK / 64][SH_TILE_F4];
@@ -573,6 +588,7 @@ preprocess_backward_kernel(const PreBwdArgs a) {
   float4 drot = make_float4(0.f, 0.f, 0.f, 0.f);
   V3 drgb = {0.f, 0.f, 0.f};  // dL_dRGB with the clamped channels zeroed (output of the "rgb" mode)
   bool nonzero_in = false;    // ROWS: some entry of the Gaussian's accumulator row is not zero (NaN != 0: counts)
+  float aa_h = 1.f;           // AA: the opacity factor h of K1 (1 for a Gaussian that is not visible: its row is zero)
   // The Gaussian's accumulator row (round 6: K7 adds into ONE 64-byte row per Gaussian, gsr_common.h ACC_*): requested for
   // every thread, visible or not -- the screen-space and opacity gradients leave through this kernel now (K7 used to add
   // into the caller's arrays directly), and a Gaussian without a pixel has an all-zero row.
@@ -625,6 +641,8 @@ preprocess_backward_kernel(const PreBwdArgs a) {
       sc2 = a.scales[3 * idx + 2];
       quat = reinterpret_cast<const float4*>(a.rotations)[idx];
     }
+    // AA: the effective opacity K1 stored (rec0.w; Geom::rec0 lies rec0_lines 256-byte lines in front of Geom::clamped)
+    const float aa_ow = AA ? reinterpret_cast<const float*>(a.clamped - (size_t)a.rec0_lines * 256u)[4 * (size_t)idx + 3] : 0.f;
     const float4 gc = acc_con;  // (the row's three float4 were requested above, in front of the branch)
     const float g2x = acc_m2d.x, g2y = acc_m2d.y;
     V3 dRGBdx = {0.f, 0.f, 0.f}, dRGBdy = {0.f, 0.f, 0.f}, dRGBdz = {0.f, 0.f, 0.f}, dL_dRGB = {0.f, 0.f, 0.f};
@@ -673,10 +691,23 @@ preprocess_backward_kernel(const PreBwdArgs a) {
     float dL_da = 0, dL_db = 0, dL_dc = 0;
     const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
     const auto& Tm = T.m;
+    float aa_r = 0.f;
+    if (AA) {  // r and h exactly as K1 computed them (same operations on the same covariance)
+      aa_r = (cov2D.m[0][0] * cov2D.m[1][1] - cb * cb) * (1.f / denom);
+      aa_h = sqrtf(fmaxf(2.5e-5f, aa_r));
+    }
     if (denom2inv != 0) {
       dL_da = denom2inv * (-cc * cc * dL_dcon.x + 2 * cb * cc * dL_dcon.y + (denom - ca * cc) * dL_dcon.z);
       dL_dc = denom2inv * (-ca * ca * dL_dcon.z + 2 * ca * cb * dL_dcon.y + (denom - ca * cc) * dL_dcon.x);
       dL_db = denom2inv * 2 * (cb * cc * dL_dcon.x - (denom + 2 * cb * cb) * dL_dcon.y + ca * cb * dL_dcon.z);
+      if (AA && aa_r > 2.5e-5f) {  // (on the floor h is a constant: no r-term)
+        const float x = cov2D.m[0][0], y = cov2D.m[1][1], z = cb, w = 0.3f;
+        const float dL_dr = acc_m2d.w * aa_ow / (2.f * aa_r);
+        const float s = dL_dr * w / (denom * denom);
+        dL_da += s * (y * y + w * y + z * z);
+        dL_dc += s * (x * x + w * x + z * z);
+        dL_db += s * (-2.f * z * (x + y + w));
+      }
       dcov[0] = (Tm[0][0] * Tm[0][0] * dL_da + Tm[0][0] * Tm[1][0] * dL_db + Tm[1][0] * Tm[1][0] * dL_dc);
       dcov[3] = (Tm[0][1] * Tm[0][1] * dL_da + Tm[0][1] * Tm[1][1] * dL_db + Tm[1][1] * Tm[1][1] * dL_dc);
       dcov[5] = (Tm[0][2] * Tm[0][2] * dL_da + Tm[0][2] * Tm[1][2] * dL_db + Tm[1][2] * Tm[1][2] * dL_dc);
@@ -859,7 +890,7 @@ preprocess_backward_kernel(const PreBwdArgs a) {
   K9_ST2(&a.dL_dmean2D[3 * (size_t)idx], acc_m2d.x);
   K9_ST2(&a.dL_dmean2D[3 * (size_t)idx + 1], acc_m2d.y);
   K9_ST2(&a.dL_dmean2D[3 * (size_t)idx + 2], 0.f);
-  K9_ST2(&a.dL_dopacity[idx], acc_m2d.w);
+  K9_ST2(&a.dL_dopacity[idx], AA ? acc_m2d.w * aa_h : acc_m2d.w);
 #undef K9_ST2
   if (a.dL_dcolor != nullptr) {
     K9_ST(&a.dL_dcolor[3 * (size_t)idx], acc_col.x);
@@ -1191,8 +1222,13 @@ __global__ void __launch_bounds__(GAUSS_BLOCK) view_messages_accumulate_kernel(i
 hipError_t launch_preprocess(hipStream_t s, const PreArgs& a) {
   const int nb = (a.P + GAUSS_BLOCK - 1) / GAUSS_BLOCK;
   const bool main_mode = a.cov3D_precomp == nullptr && a.colors_precomp == nullptr && !a.skip_color && a.M == 16 && a.D == 3;
-  if (main_mode) hipLaunchKernelGGL(preprocess_kernel<true>, dim3(nb), dim3(GAUSS_BLOCK), 0, s, a);
-  else hipLaunchKernelGGL(preprocess_kernel<false>, dim3(nb), dim3(GAUSS_BLOCK), 0, s, a);
+  if (a.antialias) {
+    if (main_mode) hipLaunchKernelGGL((preprocess_kernel<true, true>), dim3(nb), dim3(GAUSS_BLOCK), 0, s, a);
+    else hipLaunchKernelGGL((preprocess_kernel<false, true>), dim3(nb), dim3(GAUSS_BLOCK), 0, s, a);
+  } else {
+    if (main_mode) hipLaunchKernelGGL((preprocess_kernel<true, false>), dim3(nb), dim3(GAUSS_BLOCK), 0, s, a);
+    else hipLaunchKernelGGL((preprocess_kernel<false, false>), dim3(nb), dim3(GAUSS_BLOCK), 0, s, a);
+  }
   return hipGetLastError();
 }
 // Test-only introspection: unpack the gather records into the reference's separate arrays.
@@ -1283,9 +1319,15 @@ hipError_t launch_view_messages_accumulate(hipStream_t s, int64_t P, int D, int 
 hipError_t launch_preprocess_backward(hipStream_t s, const PreBwdArgs& a) {
   const int nb = (a.P + GAUSS_BLOCK - 1) / GAUSS_BLOCK;
   if (a.row_state != nullptr && a.depth) return hipErrorInvalidValue;  // (gsr_preprocess_backward_rows takes no depth)
-  if (a.row_state != nullptr) hipLaunchKernelGGL((preprocess_backward_kernel<true, false>), dim3(nb), dim3(GAUSS_BLOCK), 0, s, a);
-  else if (a.depth) hipLaunchKernelGGL((preprocess_backward_kernel<false, true>), dim3(nb), dim3(GAUSS_BLOCK), 0, s, a);
-  else hipLaunchKernelGGL((preprocess_backward_kernel<false, false>), dim3(nb), dim3(GAUSS_BLOCK), 0, s, a);
+  if (a.rec0_lines != 0) {  // GSR_FLAG_ANTIALIAS
+    if (a.row_state != nullptr) hipLaunchKernelGGL((preprocess_backward_kernel<true, false, true>), dim3(nb), dim3(GAUSS_BLOCK), 0, s, a);
+    else if (a.depth) hipLaunchKernelGGL((preprocess_backward_kernel<false, true, true>), dim3(nb), dim3(GAUSS_BLOCK), 0, s, a);
+    else hipLaunchKernelGGL((preprocess_backward_kernel<false, false, true>), dim3(nb), dim3(GAUSS_BLOCK), 0, s, a);
+  } else {
+    if (a.row_state != nullptr) hipLaunchKernelGGL((preprocess_backward_kernel<true, false, false>), dim3(nb), dim3(GAUSS_BLOCK), 0, s, a);
+    else if (a.depth) hipLaunchKernelGGL((preprocess_backward_kernel<false, true, false>), dim3(nb), dim3(GAUSS_BLOCK), 0, s, a);
+    else hipLaunchKernelGGL((preprocess_backward_kernel<false, false, false>), dim3(nb), dim3(GAUSS_BLOCK), 0, s, a);
+  }
   return hipGetLastError();
 }
 

@@ -398,14 +398,14 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                 imageBuffer.data_ptr(), dL_dpix.data_ptr(), acc.data_ptr(), _ptr(touched), bwd_flags))
             if dL_drgb is not None:
                 grad_alloc("after_blend_backward", touched[:P], False)
-            _native.check("gsr_preprocess_backward_rows", L.gsr_preprocess_backward_rows(
+            _native.check("gsr_preprocess_backward_rows_flags", L.gsr_preprocess_backward_rows_flags(
                 _stream(dev), P, int(degree), M, W, H, means3D.data_ptr(), _ptr(sh), _ptr(scales), float(scale_modifier),
                 _ptr(rotations), _ptr(cov3D_precomp), viewmatrix.data_ptr(), projmatrix.data_ptr(), _ptr(campos),
                 float(tan_fovx), float(tan_fovy), radii.data_ptr(), geomBuffer.data_ptr(), acc.data_ptr(),
                 dL_dmeans2D.data_ptr(), dL_dopacity.data_ptr(), col_out, dL_dmeans3D.data_ptr(), _ptr(dL_dcov3D),
                 _ptr(dL_dsh) if dL_drgb is None else None, None if dL_drgb is None else dL_drgb.data_ptr(),
                 dL_dscales.data_ptr() if has_scales else None, dL_drotations.data_ptr() if has_scales else None,
-                row_state.data_ptr()))
+                row_state.data_ptr(), flags & options.FLAG_ANTIALIAS))
         elif dL_drgb is None and dL_ddepth is not None:
             _native.check("gsr_backward_depth", L.gsr_backward_depth(
                 _stream(dev), P, int(degree), M, int(R), W, H, background.data_ptr(), means3D.data_ptr(), _ptr(sh),
@@ -446,7 +446,8 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                 float(tan_fovx), float(tan_fovy), radii.data_ptr(), geomBuffer.data_ptr(), acc.data_ptr(),
                 dL_dmeans2D.data_ptr(), dL_dopacity.data_ptr(), dL_dmeans3D.data_ptr(), _ptr(dL_dcov3D), dL_drgb.data_ptr(),
                 dL_dscales.data_ptr() if has_scales else None, dL_drotations.data_ptr() if has_scales else None,
-                (options.FLAG_ACC_SELF_CLEAN if persist else 0) | (options.FLAG_DEPTH_GRAD if dL_ddepth is not None else 0)))
+                (options.FLAG_ACC_SELF_CLEAN if persist else 0) | (options.FLAG_DEPTH_GRAD if dL_ddepth is not None else 0)
+                | (flags & options.FLAG_ANTIALIAS)))
         if debug:
             torch.cuda.synchronize(dev)
     if persist:  # both halves are enqueued: in stream order the table is all zero again

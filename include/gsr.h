@@ -62,7 +62,8 @@ extern "C" {
  * gsr_debug_blend_backward_profile changed. */
 /* 6 (round 6): adds gsr_preprocess_begin / gsr_preprocess_end (nothing else changed).  Later, purely additive (the number
  * stays): GSR_FLAG_DEPTH_GRAD, the GSR_ACC_DEPTH column, gsr_blend_backward_depth and gsr_backward_depth -- every earlier
- * entry point keeps its signature and its behaviour. */
+ * entry point keeps its signature and its behaviour.  Then, likewise additive: GSR_FLAG_ANTIALIAS and
+ * gsr_preprocess_backward_rows_flags. */
 #define GSR_ABI_VERSION 6
 /* The blend backward's accumulator table: GSR_ACC_ROW floats (one 64-byte line) per Gaussian, 64-byte aligned.  Columns:
  *   [GSR_ACC_MEAN2D] .x [+1] .y of dL_dmean2D      (backward.cu:545-546)
@@ -160,6 +161,16 @@ int gsr_scratch_sizes(int P, int64_t R, int64_t G, int W, int H, size_t sizes[3]
  *                        dL_dmeans3D.  The reference has no such gradient.  Only the backward entry points above accept
  *                        this bit; the forward / trace entry points, gsr_blend_backward and gsr_backward refuse it (a caller
  *                        keeps it to itself until the backward).
+ *   GSR_FLAG_ANTIALIAS   (read by gsr_preprocess / gsr_preprocess_begin and by every K8+K9 entry point: gsr_preprocess_backward,
+ *                        _rgb, _rows_flags, gsr_backward, gsr_backward_depth; accepted and ignored by gsr_blend_forward, _aux,
+ *                        gsr_blend_backward, gsr_blend_backward_depth and gsr_trace_weights) opacity-compensated 2D filter,
+ *                        as the antialiased modes of current 3DGS rasterizers: with Sigma the 2D covariance BEFORE the
+ *                        0.3 px^2 dilation, r = det(Sigma) / det(Sigma + 0.3 I) and h = sqrt(max(2.5e-5, r)), the Gaussian
+ *                        is blended with opacity * h (rec0.w of the geometry state) instead of opacity; conic, radius,
+ *                        means2D, depth and colour are unchanged.  A sub-pixel Gaussian then keeps its integrated weight
+ *                        instead of spreading its full opacity over the dilated footprint.  The backward differentiates h
+ *                        (dL_dopacity = h dL/d(opacity h), plus the share of r in the covariance gradients).  The reference
+ *                        has no such mode.  The calls of one view must all receive the bit or none of them.
  * Unknown bits are rejected with GSR_ERR_BAD_ARGUMENT. */
 #define GSR_FLAG_TILE_BOUNDS_ALPHA 1u
 #define GSR_FLAG_FAST_EXP 2u
@@ -168,7 +179,8 @@ int gsr_scratch_sizes(int P, int64_t R, int64_t G, int W, int H, size_t sizes[3]
 #define GSR_FLAG_SHARED_SIMDS 16u
 #define GSR_FLAG_ACC_SELF_CLEAN 32u
 #define GSR_FLAG_DEPTH_GRAD 64u
-#define GSR_FLAG_ALL 127u
+#define GSR_FLAG_ANTIALIAS 1024u
+#define GSR_FLAG_ALL (127u | GSR_FLAG_ANTIALIAS)
 
 /* Number of sort-key bits, 32 + getHigherMsb(tiles) (rasterizer_impl.cu:36-49, 253). */
 int gsr_sort_key_bits(int W, int H);
@@ -292,7 +304,7 @@ int gsr_preprocess_backward(void* stream, int P, int D, int M, int W, int H, con
                             const void* geom, float* acc, float* dL_dmeans2D, float* dL_dopacity,
                             float* dL_dcolors, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
                             float* dL_dscales, float* dL_drots,
-                            unsigned flags /* 0 | GSR_FLAG_ACC_SELF_CLEAN | GSR_FLAG_DEPTH_GRAD */);
+                            unsigned flags /* 0 | GSR_FLAG_ACC_SELF_CLEAN | GSR_FLAG_DEPTH_GRAD | GSR_FLAG_ANTIALIAS */);
 
 /* Depth gradients (opt-in, GSR_FLAG_DEPTH_GRAD): gsr_blend_backward / gsr_backward with one more input,
  *   dL_ddepth (1,H,W): the gradient of out_depth of gsr_blend_forward.
@@ -328,7 +340,7 @@ int gsr_preprocess_backward_rgb(void* stream, int P, int D, int M, int W, int H,
                                 const void* geom, float* acc, float* dL_dmeans2D, float* dL_dopacity,
                                 float* dL_dmeans3D, float* dL_dcov3D, float* dL_drgb,
                                 float* dL_dscales, float* dL_drots,
-                                unsigned flags /* 0 | GSR_FLAG_ACC_SELF_CLEAN | GSR_FLAG_DEPTH_GRAD */);
+                                unsigned flags /* 0 | GSR_FLAG_ACC_SELF_CLEAN | GSR_FLAG_DEPTH_GRAD | GSR_FLAG_ANTIALIAS */);
 
 /* The same kernel for gradient arrays the caller keeps ACROSS calls (a training loop's gradient bucket).  A view leaves
  * nine Gaussians of ten with all-zero gradients (culled, or blended by no pixel), and rewriting those zeros is most of
@@ -349,6 +361,15 @@ int gsr_preprocess_backward_rows(void* stream, int P, int D, int M, int W, int H
                                  const void* geom, const float* acc, float* dL_dmeans2D, float* dL_dopacity,
                                  float* dL_dcolors, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
                                  float* dL_drgb, float* dL_dscales, float* dL_drots, uint8_t* row_state);
+/* gsr_preprocess_backward_rows with flags: 0 (== gsr_preprocess_backward_rows) or GSR_FLAG_ANTIALIAS, for a view whose
+ * gsr_preprocess ran with that flag; other bits are rejected with GSR_ERR_BAD_ARGUMENT. */
+int gsr_preprocess_backward_rows_flags(void* stream, int P, int D, int M, int W, int H, const float* means3D, const float* shs,
+                                       const float* scales, float scale_modifier, const float* rotations,
+                                       const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                                       const float* campos, float tan_fovx, float tan_fovy, const int32_t* radii,
+                                       const void* geom, const float* acc, float* dL_dmeans2D, float* dL_dopacity,
+                                       float* dL_dcolors, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
+                                       float* dL_drgb, float* dL_dscales, float* dL_drots, uint8_t* row_state, unsigned flags);
 int gsr_sh_grad_compose(void* stream, int P, int D, int M, int num_views, const float* means3D, const float* campos,
                         const float* dL_drgb, float* dL_dsh);
 
