@@ -23,7 +23,7 @@
 //     four entries at a time across their 64 lanes (two v_permlane32_swap, one v_permlane16_swap, four row_shr DPP adds),
 //     add their totals into a per-chunk LDS accumulator (double-buffered by chunk parity: one workgroup barrier per chunk),
 //     and ONE global atomic per (tile, instance, term) leaves the CU -- the reference issues one per pixel.
-#include <stdlib.h>
+#include <limits.h>
 
 #include <type_traits>
 
@@ -195,28 +195,6 @@ __device__ __forceinline__ uint32_t wave_max_u32_dpp(uint32_t v) {
 }
 
 constexpr int GROUP = 4;  // survivors processed per inner-loop iteration
-#ifndef GSR_FWD_SELECT_CHAIN
-#define GSR_FWD_SELECT_CHAIN 1  // 0: the masked (exec-region) serial part for every chunk (A/B builds)
-#endif
-// T / (1 - alpha) of the backward's transmittance chain (backward.cu:503): 0 = T * v_rcp_f32 (1 ulp), 2 = the reciprocal
-// refined by one Newton step (the product since round 5: along a list of thousands of translucent entries the raw
-// reciprocal's error accumulated to 1e-5 of a gradient, tools/fuzz_v2.py seeds 110 / 256), 1 = IEEE division (A/B builds)
-#ifndef GSR_BWD_DIV
-#define GSR_BWD_DIV 2
-#endif
-#ifndef GSR_BWD_HYBRID_EXP
-#define GSR_BWD_HYBRID_EXP 0  // 1 (A/B builds, round 6): hardware 2^x + a rare polynomial fallback next to the alpha threshold -- 34 VALU
-                              // instructions fewer per group and NOT faster: the replay of the group body (tools/microbench/k7_group_replay.py)
-                              // takes 835 cycles per group and SIMD at 4 waves either way (a v_exp_f32 costs a SIMD ~7.6 cycles), K7 219.6 vs
-                              // 216.9-217.4 us same box (profiles/r06_a_k7_limiter.md)
-#endif
-#ifndef GSR_BWD_SLOT_REG
-#define GSR_BWD_SLOT_REG 0
-#endif
-#ifndef GSR_BWD_DEFER_FLUSH
-#define GSR_BWD_DEFER_FLUSH 1  // 0: round 4's loop -- flush at the end of its own chunk, two barriers per chunk (A/B builds)
-#endif
-
 // Sums each of four per-lane values over the 64 lanes of the wave, 10 instructions for all four
 // instead of 4 x 6: two v_permlane32_swap + adds fold the half-waves (a,c | b,d), one
 // v_permlane16_swap + add folds row pairs so that row r of the wave holds 16 partial sums of
@@ -420,7 +398,6 @@ __device__ __forceinline__ void forward_item(const BlendArgs& a, uint32_t tile, 
   //   pair p (entries 2p, 2p+1), FWD_PAIR floats: [0] hA0 hA1 nB0 nB1 | [4] hC0 hC1 op0 op1 | [8] x0 x1 y0 y1 |
   //                                               [12] r0 g0 b0 z0 | [16] r1 g1 b1 z1 | [20] pos0 pos1 - -
   constexpr int FWD_PAIR = 24;
-  constexpr bool SELECT_CHAIN = GSR_FWD_SELECT_CHAIN != 0;
   __shared__ __attribute__((aligned(16))) float sp[(WAVE / 2) * FWD_PAIR];
   const uint64_t lt_mask = (1ull << lane) - 1ull;
   const f32x2 pfx2 = {pfx, pfx}, pfy2 = {pfy, pfy};
@@ -503,7 +480,7 @@ __device__ __forceinline__ void forward_item(const BlendArgs& a, uint32_t tile, 
         tc1 = __builtin_amdgcn_s_memtime();
         prof_cyc[0] += tc1 - tc0;  // chunk start -> staged
       }
-      if (SELECT_CHAIN && !__any(bad_value)) {
+      if (!__any(bad_value)) {
         // Fast path (every staged colour / depth of the chunk is finite): the serial part runs on selects only, in one
         // basic block without a single scalar instruction.  A wave issues one instruction about every 4.7 cycles whatever
         // its type, and a v_cmp -> SALU -> exec -> VALU turn costs ~40 cycles against ~13 for v_mul -> v_cmp -> v_cndmask
@@ -772,7 +749,7 @@ static_assert(BWD_ITEM_TILE + 1u == (uint32_t)GSR_MAX_TILES, "include/gsr.h stat
 // and B_acc, which follows the same linear recurrence, then carries the depth behind as well.  The tenth raw moment
 // alpha T dL_dD is dL/dd_i, flushed into column ACC_DEPTH.  No list segments (SEG): the forward's checkpoints hold the
 // colour behind a segment, not its depth.
-template <int ABLATE, bool FAST, bool SEG, bool DEPTH>  // ABLATE: 0 = product; 1..6 = timing experiments only (wrong results), see launch_blend_backward
+template <bool FAST, bool SEG, bool DEPTH>
 __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint4 item, const float bg0, const float bg1,
                                               const float bg2, float4 (*s0)[WAVE], float4 (*s1)[WAVE], float4 (*s2)[WAVE],
                                               uint32_t (*sid)[WAVE], float4 (*sco)[WAVE],
@@ -873,13 +850,12 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
   // lanes that hit the same 64-byte line travel as one (tools/microbench/atomic_merge.hip: 9 values into each of 4 M random
   // rows -- 1 819 us from four arrays, 37.7 M requests; 206 us into 64-byte rows, 4.2 M requests).  With the nine accumulators
   // of a Gaussian in four arrays every atomic was a request of its own: 47 of K7's 215 us on the headline view, 200 of
-  // 757 us on synth-v2 (GSR_BWD_ABLATE=2).  Now a Gaussian's accumulators are ONE 64-byte row of `acc` (ACC_* columns,
+  // 757 us on synth-v2 (profiles/r06_c_accumulator_rows.md).  Now a Gaussian's accumulators are ONE 64-byte row of `acc` (ACC_* columns,
   // include/gsr.h), and the flush puts the sixteen columns of a row on sixteen adjacent lanes: instruction j of wave w
   // covers the chunk slots 16 w + 4 j .. + 3.  Lane (slot, column) forms its column's term from the slot's raw moments and
   // the entry's conic / opacity (sco) -- backward.cu:545-554 --, skips what is exactly zero, and the lanes of the raw
   // moments' indices put the LDS accumulator back to zero for the buffer's next chunk.
   auto flush = [&](uint32_t fb, uint32_t fsize) __attribute__((always_inline)) {
-    constexpr bool emit = ABLATE != 2 && ABLATE != 3 && ABLATE != 6;  // (experiments: no global atomics)
     const uint32_t col = (uint32_t)lane & 15u, sub = (uint32_t)lane >> 4;
     // raw moments a column reads: dL_dmean2D needs (1, 2); conic x / y / w: 3 / 4 / 5; opacity: 0; colour: 6 / 7 / 8;
     // (DEPTH) depth: 9
@@ -910,8 +886,8 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
         val = conic ? (-0.5f * co.w) * ma : ma;
         nz = ma != 0.f;
       }
-      if (used && nz && emit) unsafeAtomicAdd(&a.acc[(size_t)sid[fb][p] * ACC_ROW + col], val);
-      if (a.touched != nullptr && emit) {  // (wave-uniform) the exchange's row mask, without a pass over the table: lane 15 of a
+      if (used && nz) unsafeAtomicAdd(&a.acc[(size_t)sid[fb][p] * ACC_ROW + col], val);
+      if (a.touched != nullptr) {  // (wave-uniform) the exchange's row mask, without a pass over the table: lane 15 of a
         const uint64_t nzm = __ballot(used && nz);  // group marks the group's Gaussian if any of its columns was added to
         if (col == 15u && p < fsize && ((nzm >> (16u * sub)) & 0xffffull) != 0ull) a.touched[sid[fb][p]] = 1;
       }
@@ -930,9 +906,6 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
   for (; walk.valid(); walk.advance()) {
     const uint32_t csize = walk.chunk_size();
     const uint32_t cb = walk.chunk & 1u;
-#if !GSR_BWD_DEFER_FLUSH
-    __syncthreads();  // (A) the previous chunk's flush is complete: sacc is zero again, sid is free
-#endif
     if (w == 0 && (uint32_t)lane < csize) {
       sid[cb][lane] = walk.cur.id;
       sco[cb][lane] = walk.cur.r0;
@@ -964,10 +937,8 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
       s2[w][lane] = make_float4(0.f, 0.f, 0.f, __uint_as_float(0u));
     }
     wave_lds_sync();
-#if GSR_BWD_DEFER_FLUSH
     if (pend_size != 0u) flush(cb ^ 1u, pend_size);  // (behind barrier (B) of the previous iteration)
     pend_size = csize;
-#endif
 
     for (uint32_t j = 0; j < cnt4; j += GROUP) {
       float G[GROUP], al[GROUP], dxs[GROUP], dys[GROUP];
@@ -975,45 +946,6 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
       float4 cos_[GROUP], cols[GROUP];
       float dep[GROUP];  // (DEPTH) the entries' view-space depths
       bool any = false;
-#if GSR_BWD_HYBRID_EXP
-      // The exponential of the backward (round 6).  The FORWARD's colours are compared bit for bit, so it evaluates the
-      // exactly specified polynomial (12 instructions); here exp(power) enters two things: the decision `alpha < 1/255`,
-      // which must be the forward's, and G / alpha as factors of gradients that are compared at 1e-5.  So: the hardware's
-      // 2^x (v_exp_f32, 1 ulp; with the rounding of power * log2(e) at most 4e-7 relative for the powers that matter,
-      // |power| < 5.6) gives G and alpha, and ONLY a group in which some lane's o * G lies within 2^-18 relative of 1/255
-      // (about one group in 10^4) is evaluated again with the polynomial, wave-uniformly.  A lane further from the
-      // threshold than the two results can differ takes the forward's decision by construction.
-      float pw_[GROUP];
-      bool near = false;
-#pragma unroll
-      for (int u = 0; u < GROUP; ++u) {
-        const float4 g = s1[w][j + u];
-        dep[u] = DEPTH ? g.z : 0.f;
-        cos_[u] = s0[w][j + u];
-        cols[u] = s2[w][j + u];
-        dxs[u] = g.x - pfx;
-        dys[u] = g.y - pfy;
-        pw_[u] = blend_power_prescaled(cos_[u].x, cos_[u].y, cos_[u].z, dxs[u], dys[u]);
-        G[u] = __builtin_amdgcn_exp2f(pw_[u] * 0x1.715476p+0f);
-        const float ao = cos_[u].w * G[u];
-        al[u] = fminf(0.99f, ao);
-        near = near || (!FAST && __builtin_fabsf(ao - 1.0f / 255.0f) <= (1.0f / 255.0f) * 0x1p-18f);
-      }
-      if (!FAST && __any(near)) {  // wave-uniform, rare
-        asm volatile("; polynomial exp: a lane within 2^-18 of the alpha threshold");  // (keeps hipcc from flattening the branch into selects)
-#pragma unroll
-        for (int u = 0; u < GROUP; ++u) {
-          G[u] = gsr_expf_noclamp(pw_[u]);
-          al[u] = fminf(0.99f, cos_[u].w * G[u]);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < GROUP; ++u) {
-        const uint32_t c = __float_as_uint(s1[w][j + u].w);  // 0-based position of this instance in the tile list
-        contrib[u] = (c < last_contributor) && !(pw_[u] > 0.0f) && !(al[u] < 1.0f / 255.0f);
-        any = any || contrib[u];
-      }
-#else
 #pragma unroll
       for (int u = 0; u < GROUP; ++u) {
         const float4 g = s1[w][j + u];
@@ -1029,9 +961,7 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
         contrib[u] = (c < last_contributor) && !(power > 0.0f) && !(al[u] < 1.0f / 255.0f);
         any = any || contrib[u];
       }
-#endif
       if (!__any(any)) continue;  // wave-uniform
-      if (ABLATE == 4) continue;  // experiment: footprint + exp only
 
       float v[NM][GROUP];
       {
@@ -1049,15 +979,12 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
           // and its moments are zero -- three selects per entry instead of six.
           const bool on = contrib[u];
           const float alpha = on ? al[u] : 0.f;
-#if GSR_BWD_DIV == 1  // (A/B builds) IEEE division
-          const float inv_one_m = 1.0f / (1.f - alpha);
-#elif GSR_BWD_DIV == 2  // rcp + one Newton step
+          // 1 / (1 - alpha) of the transmittance chain (backward.cu:503): the reciprocal refined by one Newton step.  Along a
+          // list of thousands of translucent entries the raw v_rcp_f32's error (1 ulp) accumulated to 1e-5 of a gradient
+          // (profiles/r05_d_precision_fuzz.md).
           const float one_m = 1.f - alpha;
           const float r0 = __builtin_amdgcn_rcpf(one_m);
           const float inv_one_m = __builtin_fmaf(r0, __builtin_fmaf(-one_m, r0, 1.0f), r0);
-#else
-          const float inv_one_m = __builtin_amdgcn_rcpf(1.f - alpha);
-#endif
           // (DEPTH: the depth channel joins the collapsed recurrence, d * dL_dD; its background is 0)
           const float cdot = DEPTH ? cols[u].x * dpx[0] + cols[u].y * dpx[1] + cols[u].z * dpx[2] + dep[u] * dpd
                                    : cols[u].x * dpx[0] + cols[u].y * dpx[1] + cols[u].z * dpx[2];
@@ -1090,44 +1017,29 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
       float tot[NM];
 #pragma unroll
       for (int k = 0; k < NM; ++k)
-        tot[k] = (ABLATE == 1 || ABLATE == 3) ? (v[k][0] + v[k][1]) + (v[k][2] + v[k][3])  // experiment: no reduction
-                                              : wave_sum4_to_rows(v[k][0], v[k][1], v[k][2], v[k][3]);
+        tot[k] = wave_sum4_to_rows(v[k][0], v[k][1], v[k][2], v[k][3]);
       // keep the reductions whole in front of the 4-lane tail: otherwise the last row_shr step is sunk into the masked
       // region as v_mov 0 + v_mov_dpp + v_add (3 instructions per term instead of one v_add_f32_dpp)
 #pragma unroll
       for (int k = 0; k < NM; ++k) asm volatile("" : "+v"(tot[k]));
       if ((lane & 15) == 15) {
-#if GSR_BWD_SLOT_REG  // (A/B) the row's accumulator slot from the colour records already in registers: no LDS round trip in the tail
-        const uint32_t row = (uint32_t)lane >> 4;
-        const float sw = row == 0u ? cols[0].w : row == 1u ? cols[1].w : row == 2u ? cols[2].w : cols[3].w;
-        const uint32_t my_slot = __float_as_uint(sw);
-#else
         const uint32_t my_slot = __float_as_uint(s2[w][j + (uint32_t)(lane >> 4)].w);
-#endif
 #pragma unroll
         for (int k = 0; k < NM; ++k) atomicAdd(&sacc[cb][my_slot][k], tot[k]);
       }
     }
-    if (ABLATE != 5 && ABLATE != 6) __syncthreads();  // (B) every quadrant's contribution to this chunk is in sacc[cb]
-#if !GSR_BWD_DEFER_FLUSH
-    flush(cb, csize);
-#endif
+    __syncthreads();  // (B) every quadrant's contribution to this chunk is in sacc[cb]
   }
-#if GSR_BWD_DEFER_FLUSH
   // the last chunk (the next item's first LDS write lies behind barriers).  The walker's last prefetch -- chunks beyond the
   // end, never used -- is drained first: the flush re-uses its registers, and behind the first atomic every such wait
   // would be one for the atomic.
   asm volatile("" ::"v"(walk.nxt.r0.x), "v"(walk.nxt.r1.x), "v"(walk.nxt.r2.x), "v"(walk.id_next), "v"(walk.id_next2));
   if (pend_size != 0u) flush((walk.chunk - 1u) & 1u, pend_size);
-#endif
   return seg_hi - seg_lo;
 }
 
-#ifndef GSR_BWD_WAVES_PER_EU
-#define GSR_BWD_WAVES_PER_EU 4  // (A/B builds: 5 with GSR_BLEND_WAVES_PER_SIMD=5)
-#endif
-template <int ABLATE, bool FAST, bool SEG, bool DEPTH>
-__global__ void __launch_bounds__(WAVE* BWD_WAVES) __attribute__((amdgpu_waves_per_eu(GSR_BWD_WAVES_PER_EU, GSR_BWD_WAVES_PER_EU)))
+template <bool FAST, bool SEG, bool DEPTH>
+__global__ void __launch_bounds__(WAVE* BWD_WAVES) __attribute__((amdgpu_waves_per_eu(4, 4)))
 blend_backward_kernel(const BlendArgs a) {
   constexpr int LDS_ROW = bwd_lds_row<DEPTH>();
   __shared__ float4 s0[BWD_WAVES][WAVE], s1[BWD_WAVES][WAVE], s2[BWD_WAVES][WAVE];
@@ -1168,7 +1080,7 @@ blend_backward_kernel(const BlendArgs a) {
     const uint32_t r01 = max(cmax.x, cmax.y), r23 = max(cmax.z, cmax.w);
     const uint4 item = make_uint4(code, crange.x, (code & BWD_ITEM_HALF) ? ((code & BWD_ITEM_PART) ? r23 : r01) : max(r01, r23), 0u);
     const uint32_t tile = item.x;
-    const uint32_t tmax = backward_tile<ABLATE, FAST, SEG, DEPTH>(a, item, bg0, bg1, bg2, s0, s1, s2, sid, sco, sacc);
+    const uint32_t tmax = backward_tile<FAST, SEG, DEPTH>(a, item, bg0, bg1, bg2, s0, s1, s2, sid, sco, sacc);
     if (prof) {
       const uint64_t d = __builtin_amdgcn_s_memtime() - t_tile;
       if (a.profile_items != nullptr && threadIdx.x == 0 && a.work_est != nullptr) {
@@ -1229,9 +1141,6 @@ blend_backward_kernel(const BlendArgs a) {
 // mask value(s) to weights[id] and C to cnt[id] (the reference increments cnt inside its
 // channel loop, apply_weights.cu:331-339).
 // ----------------------------------------------------------------------------------
-#ifndef GSR_TRACE_ABLATE
-#define GSR_TRACE_ABLATE 0  // A/B builds, timing only (WRONG results): 1 no atomics, 2 no cross-lane reduction, 3 neither
-#endif
 // The inner loop is K6's (round 6; rounds 1-5 walked one survivor per iteration with a ballot, a branch and a 64-lane reduction
 // per entry: 182 -> 122 us per 512 x 512 view at 10^6 Gaussians, profiles/r06_j_trace_weights.md): survivors are staged in pairs
 // and evaluated two per instruction (packed binary32, same roundings), four per iteration; the serial part -- transmittance,
@@ -1333,19 +1242,18 @@ __device__ __forceinline__ void trace_item(const BlendArgs& a, uint32_t tile, ui
       const uint32_t e = j + ((uint32_t)lane >> 4);  // the entry whose totals end up in this lane's row
 #pragma unroll
       for (int ch = 0; ch < C; ++ch) {
-        const float z = (GSR_TRACE_ABLATE & 2) ? h[0] * Cw[ch]
-                                                : wave_sum4_to_rows(h[0] > 0.f ? Cw[ch] : 0.f, h[1] > 0.f ? Cw[ch] : 0.f,
+        const float z = wave_sum4_to_rows(h[0] > 0.f ? Cw[ch] : 0.f, h[1] > 0.f ? Cw[ch] : 0.f,
                                                                     h[2] > 0.f ? Cw[ch] : 0.f, h[3] > 0.f ? Cw[ch] : 0.f);
         if (row_end) sacc[ch][e] = z;
       }
-      const float zc = (GSR_TRACE_ABLATE & 2) ? h[0] : wave_sum4_to_rows(h[0], h[1], h[2], h[3]);
+      const float zc = wave_sum4_to_rows(h[0], h[1], h[2], h[3]);
       if (row_end) scnt[e] = zc;
     }
     __syncthreads();
     // (the groups behind a break wrote nothing: their slots hold an earlier chunk's values)
     if ((uint32_t)lane < min(n, flushed)) {
       const int cn = (int)scnt[lane] * C;
-      if (cn != 0 && (!(GSR_TRACE_ABLATE & 1) || sacc[0][lane] == 12345.678f)) {
+      if (cn != 0) {
         const size_t id = sid[lane];
 #pragma unroll
         for (int ch = 0; ch < C; ++ch) unsafeAtomicAdd(&a.weights[id * C + ch], sacc[ch][lane]);
@@ -1609,58 +1517,47 @@ static int cus_of_stream(hipStream_t s) {
   return cache[dev];
 }
 // Number of persistent waves of a launch: (SIMDs on the device) x (waves per SIMD), 4 by default.
-// GSR_BLEND_WAVES_PER_SIMD overrides the default for all blend kernels, GSR_FWD_WAVES_PER_SIMD for the forward / trace
-// kernels only (the backward is built for exactly 4: amdgpu_waves_per_eu) -- tuning knobs, read once.
-static int waves_per_simd(bool backward, bool shared_simds) {
-  static const int all = [] { const char* e = getenv("GSR_BLEND_WAVES_PER_SIMD"); return e ? atoi(e) : 0; }();
-  static const int fwd = [] { const char* e = getenv("GSR_FWD_WAVES_PER_SIMD"); return e ? atoi(e) : 0; }();
-  // (GSR_FLAG_SHARED_SIMDS: a second stream's kernels run alongside -- 2 waves per SIMD; the environment knobs win)
-  const int v = (!backward && fwd > 0) ? fwd : (all > 0 ? all : (shared_simds ? 2 : 4));
-  return v < 1 ? 1 : (v > 8 ? 8 : v);
+// GSR_BLEND_WAVES_PER_SIMD overrides the default for all blend kernels (the backward is built for exactly 4:
+// amdgpu_waves_per_eu).
+static int waves_per_simd(bool shared_simds) {
+  static const int all = env_knob("GSR_BLEND_WAVES_PER_SIMD", 0, 0, 8);
+  // (GSR_FLAG_SHARED_SIMDS: a second stream's kernels run alongside -- 2 waves per SIMD; the environment knob wins)
+  return all > 0 ? all : (shared_simds ? 2 : 4);
 }
-unsigned blend_grid_size(bool backward, hipStream_t s, bool shared_simds) {
-  // (GSR_FWD_GRID: development knob, any number of persistent forward waves -- tools/microbench, profiles/r02_e)
-  static const unsigned fwd_fixed = [] { const char* e = getenv("GSR_FWD_GRID"); return e && atoi(e) > 0 ? (unsigned)atoi(e) : 0u; }();
-  if (!backward && fwd_fixed != 0u) return fwd_fixed;
-  return (unsigned)cus_of_stream(s) * 4u * (unsigned)waves_per_simd(backward, shared_simds);
+unsigned blend_grid_size(hipStream_t s, bool shared_simds) {
+  return (unsigned)cus_of_stream(s) * 4u * (unsigned)waves_per_simd(shared_simds);
 }
-// Placement units of a launch with `waves_per_wg`-wave workgroups (see first_item_of_block): SIMDs or CUs; 0 turns the
-// assigned first items off (GSR_BLEND_FOLD=0, or a CU count the fold does not divide).
-static unsigned blend_units(unsigned waves_per_wg, hipStream_t s, bool shared_simds) {
-  static const bool fold = [] { const char* e = getenv("GSR_BLEND_FOLD"); return !e || atoi(e) != 0; }();
+// Placement units of a launch of `grid` workgroups of `waves_per_wg` waves (see first_item_of_block): SIMDs or CUs; 0 turns
+// the assigned first items off (a CU count the fold does not divide).
+static unsigned blend_units(unsigned waves_per_wg, unsigned grid, hipStream_t s) {
   const unsigned cus = (unsigned)cus_of_stream(s);
   const unsigned units = waves_per_wg == 1 ? cus * 4u : cus;
-  const unsigned grid = blend_grid_size(waves_per_wg != 1, s, shared_simds) / waves_per_wg;
-  if (!fold || units % 8u != 0u || grid % units != 0u) return 0u;
+  if (units % 8u != 0u || grid % units != 0u) return 0u;
   return units;
 }
-// The cursors are zero on entry (cleared by tile_worklist_kernel, then by every launch's last workgroup).
-// GSR_QUEUE_MEMSET=1 (timing experiments), or a grid too large for the retire counters: clear them with a memset
-// before the launch instead.
+// The cursors are zero on entry (cleared by tile_worklist_kernel, then by every launch's last workgroup).  A grid too
+// large for the retire counters: clear them with a memset before the launch instead.
 static hipError_t prepare_queue(hipStream_t s, BlendArgs& a, unsigned grid) {
-  static const bool env_memset = [] { const char* e = getenv("GSR_QUEUE_MEMSET"); return e && atoi(e) != 0; }();
-  const bool use_memset = env_memset || (grid + 63u) / 64u > (unsigned)QUEUE_GROUPS;
+  const bool use_memset = (grid + 63u) / 64u > (unsigned)QUEUE_GROUPS;
   a.self_reset = use_memset ? 0 : 1;
   return use_memset ? hipMemsetAsync(a.queue, 0, sizeof(uint32_t) * QUEUE_STRIDE * QUEUE_LINES, s) : hipSuccess;
 }
+// Items a quadrant of the forward / trace kernels is cut into (1, 2 or 4): fewer than two quadrant items per persistent
+// wave (bounded by the tile count of the image) and the quadrants are cut.
+// A render that will see a backward cuts later (round 6, profiles/r06_s_forward_split.md): the cut costs the BACKWARD --
+// a quadrant's work estimate is then the largest count among its sub-items, the tile's checkpoint row their sum, and
+// the backward's work list orders and cuts by both -- 5-35 % of K7 on images of 320 x 320 .. 720 x 720, more than the
+// forward gains.  Forward-only renders keep the cut that is best for the forward alone.
+static int forward_split(unsigned grid, unsigned quads, bool for_backward) {
+  if (for_backward) return quads > grid ? 1 : (4u * quads > grid ? 2 : 4);
+  return quads >= 2u * grid ? 1 : (quads >= grid ? 2 : 4);
+}
 hipError_t launch_blend_forward(hipStream_t s, BlendArgs a) {
-  const bool sh = a.shared_simds != 0;
-  hipError_t e = prepare_queue(s, a, blend_grid_size(false, s, sh));
+  const unsigned grid = blend_grid_size(s, a.shared_simds != 0);
+  hipError_t e = prepare_queue(s, a, grid);
   if (e != hipSuccess) return e;
-  a.units = (int)blend_units(1, s, sh);
-  static const bool split_ok = [] { const char* e = getenv("GSR_FWD_SPLIT"); return !e || atoi(e) != 0; }();
-  a.allow_split = split_ok ? 1 : 0;
-  // fewer than two quadrant items per persistent wave (bounded by the tile count of the image): cut the quadrants
-  const unsigned grid = blend_grid_size(false, s, sh), quads = 4u * (unsigned)(a.gx * a.gy);
-  // GSR_FWD_SPLIT_FORCE=1|2|4 (sweeps): the cut of the forward's quadrants whatever the image
-  static const int split_force = [] { const char* e = getenv("GSR_FWD_SPLIT_FORCE"); const int v = e ? atoi(e) : 0; return (v == 1 || v == 2 || v == 4) ? v : 0; }();
-  // A render that will see a backward cuts later (round 6, profiles/r06_s_forward_split.md): the cut costs the BACKWARD --
-  // a quadrant's work estimate is then the largest count among its sub-items, the tile's checkpoint row their sum, and
-  // the backward's work list orders and cuts by both -- 5-35 % of K7 on images of 320 x 320 .. 720 x 720, more than the
-  // forward gains.  Forward-only renders keep the cut that is best for the forward alone.
-  const int split_alone = quads >= 2u * grid ? 1 : (2u * quads >= 2u * grid ? 2 : 4);
-  const int split_train = quads > grid ? 1 : (4u * quads > grid ? 2 : 4);
-  const int split = split_force ? split_force : (!a.allow_split ? 1 : (a.for_backward ? split_train : split_alone));
+  a.units = (int)blend_units(1, grid, s);
+  const int split = forward_split(grid, 4u * (unsigned)(a.gx * a.gy), a.for_backward != 0);
   const dim3 g(grid), b(WAVE);
 #define GSR_FWD_LAUNCH(AUXV, FASTV, CKV)                                                                        \
   do {                                                                                                          \
@@ -1683,13 +1580,11 @@ hipError_t launch_blend_forward(hipStream_t s, BlendArgs a) {
   return hipGetLastError();
 }
 hipError_t launch_blend_backward(hipStream_t s, BlendArgs a) {
-  const bool sh = a.shared_simds != 0;
-  hipError_t e = prepare_queue(s, a, blend_grid_size(true, s, sh) / BWD_WAVES);
+  // #CUs x 4 workgroups of 4 waves: the same 4 waves per SIMD as the forward
+  const unsigned grid = blend_grid_size(s, a.shared_simds != 0) / BWD_WAVES;
+  hipError_t e = prepare_queue(s, a, grid);
   if (e != hipSuccess) return e;
-  a.units = (int)blend_units(BWD_WAVES, s, sh);
-  // GSR_BWD_ABLATE (debug, timing experiments only): 1 no wave reduction, 2 no atomics, 3 neither, 4 footprint only,
-  // 5 no workgroup barrier per chunk (the quadrant waves drift apart), 6 = 5 without the global atomics
-  static const int ablate = [] { const char* e = getenv("GSR_BWD_ABLATE"); return e ? atoi(e) : 0; }();
+  a.units = (int)blend_units(BWD_WAVES, grid, s);
   bool seg_items = false;  // the work list holds list-segment items (views whose forward left checkpoints)
   ClearArgs clear = {{nullptr, nullptr, nullptr, nullptr}, {0, 0, 0, 0}};
   if (a.clear_grads) {
@@ -1702,59 +1597,44 @@ hipError_t launch_blend_backward(hipStream_t s, BlendArgs a) {
   if (a.work_est == nullptr || a.work_maxc == nullptr || a.bwd_order == nullptr) return hipErrorInvalidValue;
   {
     // its own work list, ordered by the work the forward measured
-    static const int halves = [] { const char* e = getenv("GSR_BWD_HALVES"); return e ? atoi(e) : 10; }();  // tiles above 1.25 fair shares: measured best (sweep 6..16)
+    constexpr int halves = 10;  // tiles above 1.25 fair shares are cut in two: measured best (sweep 6..16)
     const unsigned fill_blocks = a.clear_grads ? 2u * (unsigned)cus_of_stream(s) : (a.touched != nullptr ? 16u : 0u);  // (1 .. 8 per CU: the same 14 us)
     // GSR_BWD_SEG: tiles above this many eighths of a fair share are cut into list segments where the forward left
     // checkpoints (0: never; tests use 1)
-    static const int seg_share = [] { const char* e = getenv("GSR_BWD_SEG"); return e ? atoi(e) : 5; }();
+    static const int seg_share = env_knob("GSR_BWD_SEG", 5, 0, INT_MAX);
     // (Merging consecutive strides of a cut tile into items of about equal measured work -- the plan of
     //  profiles/r06_k -- was built and swept over eleven workloads at 2 .. 12 sixteenths of a fair share per item: equal at
     //  best, 8-40 % slower where pixels walk deep; removed: profiles/r06_m_fine_checkpoints.md.)
     // (a depth backward: no segments -- the checkpoints hold no depth behind a segment, backward_tile)
-    seg_items = a.ck_table != nullptr && a.ck_chunks > 0 && seg_share > 0 && ablate == 0 && a.dL_ddepth == nullptr;
+    seg_items = a.ck_table != nullptr && a.ck_chunks > 0 && seg_share > 0 && a.dL_ddepth == nullptr;
     if (seg_items)
       hipLaunchKernelGGL(backward_worklist_kernel<true>, dim3(1u + fill_blocks), dim3(1024), 0, s, a.gx * a.gy, a.work_est,
-                         a.bwd_order, a.bwd_meta, blend_grid_size(true, s, sh) / BWD_WAVES, halves, clear, (const uint32_t*)a.tile_maxc,
+                         a.bwd_order, a.bwd_meta, grid, halves, clear, (const uint32_t*)a.tile_maxc,
                          (const uint32_t*)a.ck_table, (const uint32_t*)a.ck_work, a.ck_pos, (uint32_t)a.ck_slots, seg_share);
     else
       hipLaunchKernelGGL(backward_worklist_kernel<false>, dim3(1u + fill_blocks), dim3(1024), 0, s, a.gx * a.gy, a.work_est,
-                         a.bwd_order, a.bwd_meta, blend_grid_size(true, s, sh) / BWD_WAVES, halves, clear, (const uint32_t*)nullptr,
+                         a.bwd_order, a.bwd_meta, grid, halves, clear, (const uint32_t*)nullptr,
                          (const uint32_t*)nullptr, (const uint32_t*)nullptr, CkTable{}, 0u, 0);
   }
-  // #CUs x 4 workgroups of 4 waves: the same 4 waves per SIMD as the forward
-  const dim3 g(blend_grid_size(true, s, sh) / BWD_WAVES), b(WAVE * BWD_WAVES);
-  if (a.dL_ddepth != nullptr) {  // (the product kernel only: the ablation experiments have no depth variant)
-    if (a.fast_exp) hipLaunchKernelGGL((blend_backward_kernel<0, true, false, true>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((blend_backward_kernel<0, false, false, true>), g, b, 0, s, a);
-    return hipGetLastError();
-  }
-  switch (ablate) {
-    case 1: hipLaunchKernelGGL((blend_backward_kernel<1, false, false, false>), g, b, 0, s, a); break;
-    case 2: hipLaunchKernelGGL((blend_backward_kernel<2, false, false, false>), g, b, 0, s, a); break;
-    case 3: hipLaunchKernelGGL((blend_backward_kernel<3, false, false, false>), g, b, 0, s, a); break;
-    case 4: hipLaunchKernelGGL((blend_backward_kernel<4, false, false, false>), g, b, 0, s, a); break;
-    case 5: hipLaunchKernelGGL((blend_backward_kernel<5, false, false, false>), g, b, 0, s, a); break;
-    case 6: hipLaunchKernelGGL((blend_backward_kernel<6, false, false, false>), g, b, 0, s, a); break;
-    default:
-      if (seg_items) {
-        if (a.fast_exp) hipLaunchKernelGGL((blend_backward_kernel<0, true, true, false>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((blend_backward_kernel<0, false, true, false>), g, b, 0, s, a);
-      } else {
-        if (a.fast_exp) hipLaunchKernelGGL((blend_backward_kernel<0, true, false, false>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((blend_backward_kernel<0, false, false, false>), g, b, 0, s, a);
-      }
-      break;
+  const dim3 g(grid), b(WAVE * BWD_WAVES);
+  if (a.dL_ddepth != nullptr) {
+    if (a.fast_exp) hipLaunchKernelGGL((blend_backward_kernel<true, false, true>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((blend_backward_kernel<false, false, true>), g, b, 0, s, a);
+  } else if (seg_items) {
+    if (a.fast_exp) hipLaunchKernelGGL((blend_backward_kernel<true, true, false>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((blend_backward_kernel<false, true, false>), g, b, 0, s, a);
+  } else {
+    if (a.fast_exp) hipLaunchKernelGGL((blend_backward_kernel<true, false, false>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((blend_backward_kernel<false, false, false>), g, b, 0, s, a);
   }
   return hipGetLastError();
 }
 hipError_t launch_trace_weights(hipStream_t s, BlendArgs a) {
-  const bool sh = a.shared_simds != 0;
-  hipError_t e = prepare_queue(s, a, blend_grid_size(false, s, sh));
+  const unsigned grid = blend_grid_size(s, a.shared_simds != 0);
+  hipError_t e = prepare_queue(s, a, grid);
   if (e != hipSuccess) return e;
-  a.units = (int)blend_units(1, s, sh);
-  const unsigned grid = blend_grid_size(false, s, sh), quads = 4u * (unsigned)(a.gx * a.gy);
-  static const bool split_ok = [] { const char* e = getenv("GSR_FWD_SPLIT"); return !e || atoi(e) != 0; }();
-  const int split = !split_ok || quads >= 2u * grid ? 1 : (2u * quads >= 2u * grid ? 2 : 4);  // as the forward
+  a.units = (int)blend_units(1, grid, s);
+  const int split = forward_split(grid, 4u * (unsigned)(a.gx * a.gy), false);
   const dim3 g(grid), b(WAVE);
 #define GSR_TRACE_LAUNCH2(CC, FASTV)                                                                    \
   do {                                                                                                  \

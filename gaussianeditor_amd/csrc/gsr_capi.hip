@@ -209,10 +209,7 @@ inline bool geom_is_forward_only(const void* geom) {
 // Which binning path an image takes (gsr_binning.hip): a function of the image size only, so that gsr_scratch_sizes,
 // gsr_preprocess, gsr_bin and the blend entry points of one view agree.  GSR_BIN_LEGACY=1 (tests) forces the pair sort.
 inline int bin_legacy(int W, int H) {
-  static const bool forced = [] {
-    const char* e = getenv("GSR_BIN_LEGACY");
-    return e != nullptr && e[0] == '1';
-  }();
+  static const bool forced = env_knob("GSR_BIN_LEGACY", 0, 0, 1) == 1;
   // (the grouped path packs a tile rectangle into 32 bits: images of up to RECT32_EDGE tiles per side)
   const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
   return (forced || group_count(W, H) > GROUP_MAX || gx > RECT32_EDGE || gy > RECT32_EDGE) ? 1 : 0;
@@ -230,14 +227,15 @@ inline int bin_legacy(int W, int H) {
 // difference of two binary32 accumulators of the forward -- they cost precision (profiles/r04_d_segments.md; since round 5
 // the forward accumulates every segment's colour separately, gsr_blend.hip): the override is clamped to >= 4 unless
 // GSR_CK_DEBUG=1 says the caller knows (the tolerance tests segment small scenes at stride 64).
-inline int checkpoint_chunks(int64_t R, int W, int H) {
+inline int checkpoint_chunks_knob() {  // GSR_CK_CHUNKS as the library takes it; -1: not set
   static const int env = [] {
-    const char* e = getenv("GSR_CK_CHUNKS");
-    const char* d = getenv("GSR_CK_DEBUG");
-    int c = e != nullptr ? atoi(e) : -1;
-    if (c > 0 && c < 4 && !(d != nullptr && d[0] == '1')) c = 4;
-    return c > 1024 ? 1024 : c;
+    const int c = env_knob("GSR_CK_CHUNKS", -1, -1, 1024);
+    return (c > 0 && c < 4 && env_knob("GSR_CK_DEBUG", 0, 0, 1) != 1) ? 4 : c;
   }();
+  return env;
+}
+inline int checkpoint_chunks(int64_t R, int W, int H) {
+  const int env = checkpoint_chunks_knob();
   if (env >= 0) return env;
   // Round 6, second half (profiles/r06_m_fine_checkpoints.md, r06_n_checkpoint_table.md): what the stride sweeps of r06_k had
   // charged to "fine strides" was the REACH of 8 slots; and what a tile needs is fine cuts where its work is -- in front,
@@ -245,59 +243,32 @@ inline int checkpoint_chunks(int64_t R, int W, int H) {
   // CK_MAX slots at the positions of `checkpoint_table`: 256 apart in front, 4 096 apart at the end, 16 384 of reach.
   // Images of up to 4 096 tiles (few tiles per workgroup of the backward: a tile must be cut to fill the chip) turn
   // checkpoints on from a mean list of 1 200 entries, larger ones from 2 048 (the 1080p synth-v2 view at 1 143 loses
-  // 18 % of its backward with them).  GSR_CK_MIN_LIST overrides the threshold (tuning knob).
-  static const int64_t env_min_list = [] {
-    const char* e = getenv("GSR_CK_MIN_LIST");
-    return (int64_t)(e != nullptr && atoi(e) > 0 ? atoi(e) : 0);
-  }();
+  // 18 % of its backward with them).
   const int64_t T = (int64_t)((W + TILE - 1) / TILE) * ((H + TILE - 1) / TILE);
-  const int64_t min_list = env_min_list > 0 ? env_min_list : (T <= 4096 ? 1200 : 2048);
+  const int64_t min_list = T <= 4096 ? 1200 : 2048;
   return R < min_list * T ? 0 : CK_CHUNKS_DEFAULT;
 }
 // Checkpoint slots in use per tile: all CK_MAX (the pool and ck_work are laid out with the count in use as their stride).
 // GSR_CK_SLOTS overrides (2 .. CK_MAX; tests).
 inline int checkpoint_slots(int64_t R, int W, int H) {
-  static const int env = [] {
-    const char* e = getenv("GSR_CK_SLOTS");
-    const int v = e != nullptr ? atoi(e) : 0;
-    return v < 2 ? 0 : (v > CK_MAX ? CK_MAX : v);
-  }();
+  static const int env = env_knob("GSR_CK_SLOTS", 0, 0, CK_MAX);
   (void)R; (void)W; (void)H;
-  return env > 0 ? env : CK_MAX;
+  return env >= 2 ? env : CK_MAX;
 }
 // The positions of a view's checkpoints (CkTable, gsr_common.h): 256 positions apart in front, then 512, 1 024, 2 048 and
 // 4 096 -- 16 384 of reach with 16 slots, the first 1 536 positions cut as finely as a uniform stride of 256 cuts them.
 // Measured against uniform tables of every stride on twenty views (profiles/r06_n_checkpoint_table.md): equal where lists
 // are short, 1.2-3x faster backward where they are long (a 512 x 512 view of 6 M Gaussians: K7 778 -> 247 us).
-// GSR_CK_CHUNKS (tests, sweeps) or GSR_CK_GEOM=0: uniform, k * stride.
+// GSR_CK_CHUNKS (tests): uniform, k * stride.
 inline CkTable checkpoint_table(int64_t R, int W, int H) {
-  static const bool env_chunks = getenv("GSR_CK_CHUNKS") != nullptr;
-  static const bool geom = [] { const char* e = getenv("GSR_CK_GEOM"); return !(e && e[0] == '0'); }();
+  const bool use_fine = checkpoint_chunks_knob() < 0;
   static const uint16_t fine[CK_MAX] = {0, 4, 8, 12, 16, 20, 24, 32, 40, 48, 64, 80, 96, 128, 192, 256};
   static_assert(CK_MAX == 16 && CK_CHUNKS_DEFAULT == 4, "the table above is written for 16 slots, the first 4 chunks in");
-  // GSR_CK_TABLE="c1,c2,...,c15" (sweeps): the checkpoints' positions in 64-entry chunks, ascending
-  static const CkTable env_table = [] {
-    CkTable e;
-    memset(&e, 0, sizeof(e));
-    const char* p = getenv("GSR_CK_TABLE");
-    for (int k = 1; p != nullptr && *p && k < CK_MAX; ++k) {
-      const long v = strtol(p, const_cast<char**>(&p), 10);
-      e.chunk[k] = (uint16_t)(v > e.chunk[k - 1] ? (v > 65535 ? 65535 : v) : e.chunk[k - 1] + 1);
-      if (*p == ',') ++p;
-      if (k == CK_MAX - 1) e.chunk[0] = 1;  // (marks a complete table; put back to 0 below)
-    }
-    return e;
-  }();
   CkTable t;
   const int c = checkpoint_chunks(R, W, H);
-  const bool use_fine = geom && !env_chunks;
   for (int k = 0; k < CK_MAX; ++k) {
     const int u = k * c;
     t.chunk[k] = use_fine ? fine[k] : (uint16_t)(u > 65535 ? 65535 : u);
-  }
-  if (use_fine && env_table.chunk[0] == 1) {
-    t = env_table;
-    t.chunk[0] = 0;
   }
   return t;
 }
@@ -654,7 +625,7 @@ int gsr_debug_blend_forward_profile(void* stream, int P, int64_t R, int W, int H
                                     const void* binning, void* image, float* out_color, float* out_depth,
                                     uint64_t* records, int64_t max_records, int64_t* n_records_host) {
   if (!records || !n_records_host) return GSR_ERR_BAD_ARGUMENT;
-  const int64_t n = (int64_t)blend_grid_size(false, (hipStream_t)stream);
+  const int64_t n = (int64_t)blend_grid_size((hipStream_t)stream);
   *n_records_host = n;
   if (max_records < n) return GSR_ERR_BAD_ARGUMENT;
   if (P < 0 || R < 0 || W <= 0 || H <= 0 || !bg || !image || !out_color || !out_depth) return GSR_ERR_BAD_ARGUMENT;
@@ -770,7 +741,7 @@ int gsr_debug_blend_backward_profile(void* stream, int P, int64_t R, int W, int 
                                      const void* binning, const void* image, const float* dL_dpix, float* acc,
                                      uint64_t* records, int64_t max_records, int64_t* n_records_host) {
   if (!records || !n_records_host) return GSR_ERR_BAD_ARGUMENT;
-  const int64_t n = (int64_t)blend_grid_size(true, (hipStream_t)stream) / 4;
+  const int64_t n = (int64_t)blend_grid_size((hipStream_t)stream) / 4;
   *n_records_host = n;
   if (max_records < n) return GSR_ERR_BAD_ARGUMENT;
   if (P < 0 || R <= 0 || W <= 0 || H <= 0 || !bg || !geom || !binning || !image || !dL_dpix) return GSR_ERR_BAD_ARGUMENT;

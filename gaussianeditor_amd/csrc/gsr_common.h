@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "../../include/gsr.h"
 
@@ -265,10 +266,7 @@ __host__ __device__ inline uint32_t rect32_groups(uint32_t r) {
 // Group instances per chunk: 1, 2, 4 or 8 batches of 64.  A chunk is one wave and one row of the per-chunk count tables.
 // A chunk wave's time is the sum of its memory and LDS round trips (measured: the kernels are latency bound at any
 // occupancy they reach), so chunks are short while the launch stays within ~16 waves per SIMD.
-#ifndef GSR_GROUP_CHUNKS_TARGET
-#define GSR_GROUP_CHUNKS_TARGET 16384  // (A/B builds override it)
-#endif
-constexpr int GROUP_CHUNKS_TARGET = GSR_GROUP_CHUNKS_TARGET;
+constexpr int GROUP_CHUNKS_TARGET = 16384;
 __host__ __device__ inline int group_chunk_items(int64_t G) {
   const int64_t batches = (G + 63) / 64;
   int per = 1;
@@ -466,5 +464,21 @@ __device__ __forceinline__ uint32_t block_excl_scan_u32(uint32_t v, uint32_t* bl
   return smem[w] + incl - v;
 }
 #endif  // __HIPCC__
+
+// The library's environment knobs, all of them (tests and bench.py set them; none is needed in normal use).  Each is read
+// once per process, at its first use:
+//   GSR_BIN_LEGACY=1            the two-pass pair sort for every image size (gsr_capi.hip: bin_legacy)
+//   GSR_CK_CHUNKS=n             checkpoint stride in 64-entry chunks, uniform table; 0 = no checkpoints; unset: by list length
+//   GSR_CK_DEBUG=1              lets GSR_CK_CHUNKS go below 4 (gsr_capi.hip: checkpoint_chunks)
+//   GSR_CK_SLOTS=n              checkpoint slots in use per tile, 2 .. CK_MAX (default CK_MAX)
+//   GSR_BWD_SEG=n               tiles above n eighths of a fair share are cut into list segments (default 5; 0 = never)
+//   GSR_BLEND_WAVES_PER_SIMD=n  persistent waves per SIMD of the blend kernels, 1 .. 8 (default 4)
+// Returns `unset` where the variable is not set, its integer value clamped to [lo, hi] otherwise.
+inline int env_knob(const char* name, int unset, int lo, int hi) {
+  const char* e = getenv(name);
+  if (e == nullptr) return unset;
+  const int v = atoi(e);
+  return v < lo ? lo : (v > hi ? hi : v);
+}
 
 }  // namespace gsr

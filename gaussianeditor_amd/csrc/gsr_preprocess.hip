@@ -7,9 +7,6 @@
 // integer outputs (radii, tiles_touched) are bit-identical to the CPU oracle.
 #include "gsr_kernels.h"
 
-#ifndef GSR_K1_PREFETCH
-#define GSR_K1_PREFETCH 1  // (A/B builds: 0 = the loads where the reference has them)
-#endif
 
 namespace gsr {
 
@@ -242,20 +239,18 @@ __global__ void __launch_bounds__(GAUSS_BLOCK) __attribute__((amdgpu_waves_per_e
   // request fetches it where it always did; one that is culled after it wasted the fetch: the 1.5x screen margin keeps both rare).
   V3 sh[16];
   bool sh_loaded = false;
-  const bool want_sh = GSR_K1_PREFETCH && !skip_color && colors_precomp == nullptr;
+  const bool want_sh = !skip_color && colors_precomp == nullptr;
   float sc0 = 0.f, sc1 = 0.f, sc2 = 0.f, my_opacity = 0.f;
   float aa_h = 1.f;  // (AA) the opacity factor h
   float4 quat = make_float4(0.f, 0.f, 0.f, 0.f);
   if (idx < a.P) {
-    if (GSR_K1_PREFETCH) {
-      if (cov3D_precomp == nullptr) {
-        sc0 = a.scales[3 * idx + 0];
-        sc1 = a.scales[3 * idx + 1];
-        sc2 = a.scales[3 * idx + 2];
-        quat = reinterpret_cast<const float4*>(a.rotations)[idx];
-      }
-      my_opacity = a.opacities[idx];
+    if (cov3D_precomp == nullptr) {
+      sc0 = a.scales[3 * idx + 0];
+      sc1 = a.scales[3 * idx + 1];
+      sc2 = a.scales[3 * idx + 2];
+      quat = reinterpret_cast<const float4*>(a.rotations)[idx];
     }
+    my_opacity = a.opacities[idx];
     do {
       p = {a.means3D[3 * idx], a.means3D[3 * idx + 1], a.means3D[3 * idx + 2]};
       // in_frustum, auxiliary.h:139-164: only the near test survives
@@ -282,8 +277,7 @@ __global__ void __launch_bounds__(GAUSS_BLOCK) __attribute__((amdgpu_waves_per_e
 #pragma unroll
         for (int i = 0; i < 6; ++i) c3[i] = cov3D_precomp[6 * (size_t)idx + i];
       } else {
-        if (GSR_K1_PREFETCH) cov3d_from_values(sc0, sc1, sc2, a.scale_modifier, quat, c3);
-        else cov3d_from_scale_rot(a.scales, a.scale_modifier, a.rotations, idx, c3);
+        cov3d_from_values(sc0, sc1, sc2, a.scale_modifier, quat, c3);
       }
       // (not stored: the backward recomputes it from the same inputs, bit for bit, instead of reading 24 B back)
 
@@ -335,7 +329,7 @@ __global__ void __launch_bounds__(GAUSS_BLOCK) __attribute__((amdgpu_waves_per_e
         // (gsr_blend.hip: can_touch_quad), intersected with the reference's square.  An instance dropped here passes
         // `alpha < 1/255 -> continue` (forward.cu:340-344) at every pixel of its tile, so images, radii and gradients
         // do not change; num_rendered, the lists and n_contrib do.  radii keeps the reference's value.
-        float o = GSR_K1_PREFETCH ? my_opacity : a.opacities[idx];
+        float o = my_opacity;
         if (AA) o *= aa_h;  // (the opacity the blend kernels see)
         float hx = (float)radius_i, hy = (float)radius_i;
         if (o < 1.0f / 255.0f) {
@@ -421,7 +415,7 @@ __global__ void __launch_bounds__(GAUSS_BLOCK) __attribute__((amdgpu_waves_per_e
         }
       }
       // forward.cu:250-255
-      float o = GSR_K1_PREFETCH ? my_opacity : a.opacities[idx];
+      float o = my_opacity;
       if (AA) o *= aa_h;
       a.g.rec0[idx] = make_float4(conx, cony, conz, o);
       a.g.rec1[idx] = make_float4(pix, piy, my_depth, my_radius);
@@ -592,22 +586,11 @@ preprocess_backward_kernel(const PreBwdArgs a) {
   // The Gaussian's accumulator row (round 6: K7 adds into ONE 64-byte row per Gaussian, gsr_common.h ACC_*): requested for
   // every thread, visible or not -- the screen-space and opacity gradients leave through this kernel now (K7 used to add
   // into the caller's arrays directly), and a Gaussian without a pixel has an all-zero row.
-  // (GSR_K9_NT_ACC=1, A/B builds: streaming loads of the rows and streaming stores of the two copied-out gradients, to keep
-  //  them out of the memory-side cache that holds the parameters K1 streams again next -- measured: K1 does not notice either
-  //  way once the table is no longer cleared per backward, and this kernel is 3-4 us SLOWER with them, 10 us on synth-v2,
-  //  profiles/r06_e_accumulator_rows.md)
-#ifndef GSR_K9_NT_ACC
-#define GSR_K9_NT_ACC 0
-#endif
+  // (Plain loads and stores: streaming ones, to keep the rows out of the memory-side cache that holds the parameters K1
+  //  streams again next, made this kernel 3-4 us slower and K1 no faster, profiles/r06_c_accumulator_rows.md)
   typedef float acc_f4 __attribute__((ext_vector_type(4)));
   const acc_f4* const acc_row = reinterpret_cast<const acc_f4*>(a.acc + (size_t)idx * ACC_ROW);
-#if GSR_K9_NT_ACC
-#define K9_ACC_LD(i) __builtin_nontemporal_load(acc_row + (i))
-#else
-#define K9_ACC_LD(i) acc_row[i]
-#endif
-  const acc_f4 acc_m2d_ = K9_ACC_LD(ACC_MEAN2D / 4), acc_col_ = K9_ACC_LD(ACC_COLOR / 4), acc_con_ = K9_ACC_LD(ACC_CONIC / 4);
-#undef K9_ACC_LD
+  const acc_f4 acc_m2d_ = acc_row[ACC_MEAN2D / 4], acc_col_ = acc_row[ACC_COLOR / 4], acc_con_ = acc_row[ACC_CONIC / 4];
   const float4 acc_m2d = make_float4(acc_m2d_.x, acc_m2d_.y, acc_m2d_.z, acc_m2d_.w);  // dL_dmean2D.x, .y, (0), dL_dopacity
   const float4 acc_col = make_float4(acc_col_.x, acc_col_.y, acc_col_.z, acc_col_.w);  // dL_dcolor r, g, b, (0 | DEPTH: dL_ddepth)
   const float4 acc_con = make_float4(acc_con_.x, acc_con_.y, acc_con_.z, acc_con_.w);  // dL_dconic x, y, (0), w
@@ -872,35 +855,24 @@ preprocess_backward_kernel(const PreBwdArgs a) {
     }
   }
   if (!live) return;
-#if defined(GSR_K9_NT_GRADS) && GSR_K9_NT_GRADS
-#define K9_ST(p, v) __builtin_nontemporal_store((v), (p))  // (A/B build)
-#else
-#define K9_ST(p, v) (*(p) = (v))
-#endif
-  K9_ST(&a.dL_dmeans3D[3 * (size_t)idx], dmean.x);
-  K9_ST(&a.dL_dmeans3D[3 * (size_t)idx + 1], dmean.y);
-  K9_ST(&a.dL_dmeans3D[3 * (size_t)idx + 2], dmean.z);
+  a.dL_dmeans3D[3 * (size_t)idx] = dmean.x;
+  a.dL_dmeans3D[3 * (size_t)idx + 1] = dmean.y;
+  a.dL_dmeans3D[3 * (size_t)idx + 2] = dmean.z;
   // the two gradients K7 accumulates for the caller (backward.cu:545-546, 554) and, with precomputed colours, the colour's
   // (:523): copied out of the accumulator row (a Gaussian that is not visible has a zero row: K7 never touched it)
-#if GSR_K9_NT_ACC
-#define K9_ST2(p, v) __builtin_nontemporal_store((v), (p))
-#else
-#define K9_ST2(p, v) K9_ST(p, v)
-#endif
-  K9_ST2(&a.dL_dmean2D[3 * (size_t)idx], acc_m2d.x);
-  K9_ST2(&a.dL_dmean2D[3 * (size_t)idx + 1], acc_m2d.y);
-  K9_ST2(&a.dL_dmean2D[3 * (size_t)idx + 2], 0.f);
-  K9_ST2(&a.dL_dopacity[idx], AA ? acc_m2d.w * aa_h : acc_m2d.w);
-#undef K9_ST2
+  a.dL_dmean2D[3 * (size_t)idx] = acc_m2d.x;
+  a.dL_dmean2D[3 * (size_t)idx + 1] = acc_m2d.y;
+  a.dL_dmean2D[3 * (size_t)idx + 2] = 0.f;
+  a.dL_dopacity[idx] = AA ? acc_m2d.w * aa_h : acc_m2d.w;
   if (a.dL_dcolor != nullptr) {
-    K9_ST(&a.dL_dcolor[3 * (size_t)idx], acc_col.x);
-    K9_ST(&a.dL_dcolor[3 * (size_t)idx + 1], acc_col.y);
-    K9_ST(&a.dL_dcolor[3 * (size_t)idx + 2], acc_col.z);
+    a.dL_dcolor[3 * (size_t)idx] = acc_col.x;
+    a.dL_dcolor[3 * (size_t)idx + 1] = acc_col.y;
+    a.dL_dcolor[3 * (size_t)idx + 2] = acc_col.z;
   }
   if (!ROWS) {
 #pragma unroll
     for (int i = 0; i < 6; ++i)
-      if (a.dL_dcov3D != nullptr) K9_ST(&a.dL_dcov3D[6 * (size_t)idx + i], dcov[i]);  // (null: no precomputed covariance to take a gradient)
+      if (a.dL_dcov3D != nullptr) a.dL_dcov3D[6 * (size_t)idx + i] = dcov[i];  // (null: no precomputed covariance to take a gradient)
   }
   if (a.dL_drgb != nullptr) {
     a.dL_drgb[3 * (size_t)idx] = drgb.x;
@@ -908,12 +880,11 @@ preprocess_backward_kernel(const PreBwdArgs a) {
     a.dL_drgb[3 * (size_t)idx + 2] = drgb.z;
   }
   if (a.dL_dscale != nullptr) {
-    K9_ST(&a.dL_dscale[3 * (size_t)idx], dscale.x);
-    K9_ST(&a.dL_dscale[3 * (size_t)idx + 1], dscale.y);
-    K9_ST(&a.dL_dscale[3 * (size_t)idx + 2], dscale.z);
+    a.dL_dscale[3 * (size_t)idx] = dscale.x;
+    a.dL_dscale[3 * (size_t)idx + 1] = dscale.y;
+    a.dL_dscale[3 * (size_t)idx + 2] = dscale.z;
   }
   if (a.dL_drot != nullptr) reinterpret_cast<float4*>(a.dL_drot)[idx] = drot;
-#undef K9_ST
 }
 
 // ----------------------------------------------------------------------------------

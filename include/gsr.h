@@ -28,7 +28,7 @@
  *     call as `flags`); the only thing it owns is a small pool of 8 KiB pinned host buffers, one checked out per host
  *     thread and device, through which gsr_preprocess receives its counts (the device writes them, the host polls).
  *   - tuning / experiment knobs are environment variables read ONCE per process, none of which changes any result
- *     (launch geometry of the persistent blend kernels, work-list ordering, ablation switches, and GSR_BIN_LEGACY=1,
+ *     (launch geometry of the persistent blend kernels, work-list ordering, and GSR_BIN_LEGACY=1,
  *     which sends every image down the tile-pair sort that otherwise only images beyond 131 072 tiles take); they are
  *     listed in DESIGN.md section 3.3 and are not part of this ABI.
  *   - an absent optional input is a NULL pointer (the reference uses empty

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Stage times of ONE view of the editor's loop shape (BASELINE configs[2]: 1 M Gaussians through a 512 x 512 image) under the
-launch-shape knobs the environment carries (GSR_BWD_SEG, GSR_BWD_HALVES, GSR_CK_CHUNKS, GSR_FWD_SPLIT ...): one process per
+launch-shape knobs the environment carries (GSR_BWD_SEG, GSR_CK_CHUNKS, GSR_CK_SLOTS, GSR_BLEND_WAVES_PER_SIMD): one process per
 setting (the library reads them once).   python tools/c3_knobs.py [--width 512 --height 512]"""
 import argparse
 import math

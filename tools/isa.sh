@@ -1,6 +1,7 @@
 #!/bin/bash
 # Development tool: device ISA of one translation unit with the product's flags, and the register / LDS / scratch figures of
-# every kernel whose mangled name contains PATTERN.   tools/isa.sh gsr_blend blend_backward_kernelILi0ELb0ELb0  [-> /tmp/isa/<file>.s]
+# every kernel whose mangled name contains PATTERN.   tools/isa.sh gsr_blend blend_backward_kernelILb0ELb0ELb0E  [-> /tmp/isa/<file>.s]
+# (tools/isa_diff.py compares two source trees kernel by kernel.)
 set -euo pipefail
 cd "$(dirname "$0")/.."
 F=${1:?translation unit without .hip}; PAT=${2:-.}

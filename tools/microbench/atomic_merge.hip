@@ -1,6 +1,7 @@
 // Development tool: do memory-side float atomics of ONE wave instruction that fall into the same 32- / 64-byte piece of memory
-// travel as one request?  (Round 6: K7's global atomics cost 47 of 215 us on the headline view and 200 of 757 us on synth-v2,
-// GSR_BWD_ABLATE=2; its nine accumulators per Gaussian live in four arrays, so every atomic is a request of its own.)
+// travel as one request?  (Round 6, before the accumulator rows: K7's global atomics were measured at 47 of 215 us on the headline
+// view and 200 of 757 us on synth-v2, profiles/r06_c_accumulator_rows.md; its nine accumulators per Gaussian lived in four arrays,
+// so every atomic was a request of its own.)
 //   hipcc --offload-arch=gfx950 -O2 -munsafe-fp-atomics tools/microbench/atomic_merge.hip -o build_variants/atomic_merge
 // Every variant adds nine values to each of M random rows (the same pseudo-random row sequence), rows of a table of N rows:
 //   soa     nine instructions per 64 rows, lane = row, four arrays (3 + 4 + 1 + 3 floats per row): K7's flush today

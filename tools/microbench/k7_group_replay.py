@@ -1,13 +1,13 @@
 """Development tool: the issue ceiling of K7's OWN instruction mix.
 
-Takes the 4-entry group body of `blend_backward_kernel<0, false, false>` exactly as hipcc emits it for the product
+Takes the 4-entry group body of `blend_backward_kernel<false, false, false>` (FAST, SEG, DEPTH) exactly as hipcc emits it for the product
 (`gaussianeditor_amd/csrc/gsr_blend.hip`, the inner loop of backward_tile: footprints + exp of four entries, the
 transmittance / colour recurrences, the nine moments, the 4-entry transposed wave reduction and the nine ds_add_f32),
 strips its control flow (the `no lane contributes` skip and the loop's own back edge), and replays it REP times per wave
 from zero-initialised registers and LDS -- no global memory, no barrier, no list walk.  Launched as 4-wave workgroups (one
 wave per SIMD, like the product) with 1 .. 4 workgroups per CU on every CU, it measures how many cycles a SIMD needs per
-group when 1 .. 4 waves share it: THAT, not a per-instruction figure, is the ceiling K7's `valu_issue_frac` is quoted against
-(bench.py: K7_GROUP_CYCLES_PER_SIMD).  Variants: `full` (as compiled), `nolds` (every ds_* instruction and the waits for
+group when 1 .. 4 waves share it: THAT, not a per-instruction figure, is the ceiling of K7's instruction mix (round 6: 835
+cycles per group and SIMD at four waves, profiles/r06_b_k7_limiter.md).  Variants: `full` (as compiled), `nolds` (every ds_* instruction and the waits for
 them removed: the VALU/SALU stream alone), `noxlane` (additionally without the permlane / DPP reduction steps).
 
     python tools/microbench/k7_group_replay.py            # writes build_variants/k7_group_replay.hip and builds it (no GPU needed)
@@ -20,7 +20,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 OUT = os.path.join(ROOT, "build_variants")
-KERNEL = "_ZN3gsr21blend_backward_kernelILi0ELb0ELb0EEEvNS_9BlendArgsE"
+KERNEL = "_ZN3gsr21blend_backward_kernelILb0ELb0ELb0EEEvNS_9BlendArgsE"
 FLAGS = ("--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -munsafe-fp-atomics -fno-gpu-rdc -fno-slp-vectorize "
          "-fvisibility=hidden -mllvm -amdgpu-sched-strategy=max-ilp -mllvm -amdgpu-atomic-optimizer-strategy=None").split()
 
@@ -60,23 +60,9 @@ def group_body(isa: str):
     raise SystemExit("group loop not found in the ISA")
 
 
-RARE_MARK = "polynomial exp"  # the asm comment inside the backward's rarely taken exact-exponential block (gsr_blend.hip)
-
-
-def drop_rare_blocks(lines):
-    """Removes the fall-through block that holds RARE_MARK (from the `; %bb.N:` comment that opens it to the `s_branch`
-    that closes it): the replay takes the common path, on which the conditional branch in front of it is taken."""
-    marks = [i for i, ln in enumerate(lines) if RARE_MARK in ln]
-    for m in reversed(marks):
-        a = max(i for i in range(m) if lines[i].lstrip().startswith("; %bb."))
-        b = next(i for i in range(m, len(lines)) if lines[i].split(";")[0].strip().startswith("s_branch"))
-        lines = lines[:a] + lines[b + 1:]
-    return lines
-
-
 def clean(lines, variant):
     out = []
-    for ln in drop_rare_blocks(list(lines)):
+    for ln in lines:
         t = ln.split(";")[0].rstrip()
         if not t.strip() or t.strip().startswith("."):
             continue
@@ -191,7 +177,7 @@ int main(int argc, char** argv) {
 
 
 def main():
-    # optional: NAME followed by extra compiler flags for the product source, e.g. `poly -DGSR_BWD_HYBRID_EXP=0` (A/B builds)
+    # optional: NAME followed by extra compiler flags for the product source, e.g. `noilp -mllvm -amdgpu-sched-strategy=max-occupancy`
     name = "k7_group_replay" + ("_" + sys.argv[1] if len(sys.argv) > 1 else "")
     isa = product_isa(sys.argv[2:])
     hip = os.path.join(OUT, name + ".hip")
