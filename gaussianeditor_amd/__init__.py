@@ -85,6 +85,25 @@ def get_depth_grad() -> bool:
     return bool(options.default_flags() & options.FLAG_DEPTH_GRAD)
 
 
+def set_abs_grad(on: bool) -> None:
+    """Opt-in: the default of GSR_FLAG_ABS_GRAD (include/gsr.h) -- the backward of a render also leaves the ABSOLUTE
+    screen-space gradient on the `means2D` tensor the rasterizer was given (`render()`'s `viewspace_points`), as
+    `means2D.absgrad`: (P,3) float32, per Gaussian the sums over pixels of the absolute values of the per-pixel terms of
+    `means2D.grad[:, :2]`, z = 0 -- the densification statistic of AbsGS (gsplat's `absgrad`), which does not cancel for a
+    large splat that straddles an edge.  A new tensor per backward, assigned, never accumulated.  Off (default): the
+    attribute is neither set nor cleared.  Images and every other gradient are the same either way."""
+    from . import options
+
+    f = options.default_flags() & ~options.FLAG_ABS_GRAD
+    options.set_default_flags(f | (options.FLAG_ABS_GRAD if on else 0))
+
+
+def get_abs_grad() -> bool:
+    from . import options
+
+    return bool(options.default_flags() & options.FLAG_ABS_GRAD)
+
+
 def set_antialiasing(on: bool) -> None:
     """Opt-in: the default of GSR_FLAG_ANTIALIAS (include/gsr.h) -- the opacity-compensated 2D filter of antialiased
     3DGS rasterizers.  Every Gaussian is blended with opacity * h, h = sqrt(max(2.5e-5, det(S) / det(S + 0.3 I))) of its

@@ -18,7 +18,7 @@ GSR_ABI_VERSION = 6
 
 _P = c_void_p
 #: floats per row of the blend backward's accumulator table and its columns (include/gsr.h: GSR_ACC_*)
-ACC_ROW, ACC_MEAN2D, ACC_OPACITY, ACC_CONIC, ACC_COLOR, ACC_DEPTH = 16, 0, 3, 4, 8, 11
+ACC_ROW, ACC_MEAN2D, ACC_OPACITY, ACC_CONIC, ACC_COLOR, ACC_DEPTH, ACC_ABS2D = 16, 0, 3, 4, 8, 11, 12
 
 
 class AdamTensor(ctypes.Structure):
@@ -67,6 +67,8 @@ SIGNATURES = {
     "gsr_backward_depth": (c_int, [_P, c_int, c_int, c_int, c_int64, c_int, c_int, _P, _P, _P, _P, _P, c_float, _P, _P, _P,
                                    _P, _P, c_float, c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                    c_uint]),
+    # absolute screen-space gradients (GSR_FLAG_ABS_GRAD), between the two halves: (stream, P, acc, touched, absgrad (P,3))
+    "gsr_abs_grad_take": (c_int, [_P, c_int, _P, _P, _P]),
     # (... radii, geom, acc, dL_dmeans2D, dL_dopacity, dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drots, flags)
     "gsr_preprocess_backward": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_float, _P, _P, _P, _P, _P,
                                         c_float, c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_uint]),

@@ -719,8 +719,10 @@ constexpr int BWD_WAVES = 4;  // one workgroup = the four quadrants of one tile 
 constexpr int ACC_LDS_ROW = 9;  // floats per chunk slot of the backward's LDS accumulators: the nine raw moments
 // ... of a DEPTH backward (gsr_blend_backward_depth): ten raw moments (the tenth: alpha T dL_ddepth) in rows of 11 floats
 // (odd, as 9: the slots of the tail's four ds_add lanes and the four rows of a flush instruction spread over the banks)
-template <bool DEPTH> constexpr int bwd_moments() { return DEPTH ? 10 : 9; }
-template <bool DEPTH> constexpr int bwd_lds_row() { return DEPTH ? 11 : ACC_LDS_ROW; }
+// ... of an ABS backward (GSR_FLAG_ABS_GRAD): two more raw moments behind those, |A qx + B qy| and |B qx + C qy|, in rows of
+// 11 floats, with DEPTH 13 (odd again)
+template <bool DEPTH, bool ABS = false> constexpr int bwd_moments() { return (DEPTH ? 10 : 9) + (ABS ? 2 : 0); }
+template <bool DEPTH, bool ABS = false> constexpr int bwd_lds_row() { return ABS ? (DEPTH ? 13 : 11) : DEPTH ? 11 : ACC_LDS_ROW; }
 constexpr uint32_t BWD_ITEM_HALF = 0x80000000u;   // item code: the workgroup handles one half of the tile ...
 constexpr uint32_t BWD_ITEM_PART = 0x40000000u;   // ... quadrants {2,3} instead of {0,1}
 // ... or (round 4) A RUN OF LIST SEGMENTS of a deep tile: the segments lo .. hi between its checkpoints, i.e. positions
@@ -749,13 +751,22 @@ static_assert(BWD_ITEM_TILE + 1u == (uint32_t)GSR_MAX_TILES, "include/gsr.h stat
 // and B_acc, which follows the same linear recurrence, then carries the depth behind as well.  The tenth raw moment
 // alpha T dL_dD is dL/dd_i, flushed into column ACC_DEPTH.  No list segments (SEG): the forward's checkpoints hold the
 // colour behind a segment, not its depth.
-template <bool FAST, bool SEG, bool DEPTH>
+//
+// ABS (GSR_FLAG_ABS_GRAD): next to the signed screen-space gradient the sum over pixels of the ABSOLUTE values of its
+// per-pixel terms (backward.cu:545-546) is accumulated, into the columns ACC_ABS2D, + 1.  The per-pixel term of the x
+// component is -o (A qx + B qy) 0.5 W: o, 0.5 W and 0.5 H are per-entry constants, so the lane forms |A qx + B qy| and
+// |B qx + C qy| from the conic it already holds (pre-scaled: A = -2 cos_.x, B = -cos_.y, C = -2 cos_.z; the common sign
+// drops out of the absolute value), the two moments are reduced and added to the chunk's LDS row like the others, and the
+// flush multiplies by |o| 0.5 W, |o| 0.5 H.  Every item shape takes it as it is: an entry is seen once by every pixel of an
+// item, whole tile, half tile or list segment, and absolute sums add over any partition of the pixels.
+template <bool FAST, bool SEG, bool DEPTH, bool ABS>
 __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint4 item, const float bg0, const float bg1,
                                               const float bg2, float4 (*s0)[WAVE], float4 (*s1)[WAVE], float4 (*s2)[WAVE],
                                               uint32_t (*sid)[WAVE], float4 (*sco)[WAVE],
-                                              float (*sacc)[WAVE][bwd_lds_row<DEPTH>()]) {
+                                              float (*sacc)[WAVE][bwd_lds_row<DEPTH, ABS>()]) {
   static_assert(!(DEPTH && SEG), "depth backwards walk whole lists: the checkpoints hold no depth");
-  constexpr int NM = bwd_moments<DEPTH>();  // raw moments per entry
+  constexpr int NM = bwd_moments<DEPTH, ABS>();  // raw moments per entry
+  constexpr int IABS = bwd_moments<DEPTH>();     // (ABS) index of the first of the two absolute moments
   const int w = (int)(threadIdx.x >> 6), lane = lane_id();
   // The item's descriptor (assembled by the caller from three scalar loads): x = code -- a whole tile, wave w = quadrant w; or
   // half a tile, waves (0,1) and (2,3) = the upper / lower 8x4 pixels of its two quadrants; or one list segment --, y = first
@@ -858,12 +869,14 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
   auto flush = [&](uint32_t fb, uint32_t fsize) __attribute__((always_inline)) {
     const uint32_t col = (uint32_t)lane & 15u, sub = (uint32_t)lane >> 4;
     // raw moments a column reads: dL_dmean2D needs (1, 2); conic x / y / w: 3 / 4 / 5; opacity: 0; colour: 6 / 7 / 8;
-    // (DEPTH) depth: 9
+    // (DEPTH) depth: 9; (ABS) the absolute screen-space sums: IABS, IABS + 1
     const uint32_t ia = col == ACC_MEAN2D || col == ACC_MEAN2D + 1u ? 1u
                         : col == ACC_OPACITY ? 0u
                         : col == ACC_CONIC ? 3u : col == ACC_CONIC + 1u ? 4u : col == ACC_CONIC + 3u ? 5u
                         : col >= ACC_COLOR && col < ACC_COLOR + 3u ? 6u + (col - ACC_COLOR)
-                        : DEPTH && col == ACC_DEPTH ? 9u : (uint32_t)NM;  // NM: the column is not used
+                        : DEPTH && col == ACC_DEPTH ? 9u
+                        : ABS && (col == ACC_ABS2D || col == ACC_ABS2D + 1u) ? (uint32_t)IABS + (col - ACC_ABS2D)
+                        : (uint32_t)NM;  // NM: the column is not used
 #pragma unroll
     for (uint32_t jj = 0; jj < 4u; ++jj) {
       const uint32_t p = 16u * (uint32_t)w + 4u * jj + sub;
@@ -881,6 +894,10 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
         const float scale = xcol ? ddelx_dx : ddely_dy, c1 = xcol ? co.x : co.y, c2 = xcol ? co.y : co.z;
         val = -(scale * co.w) * (c1 * ma + c2 * mb);
         nz = ma != 0.f || mb != 0.f;
+      } else if (ABS && ia >= (uint32_t)IABS) {
+        // the per-pixel terms of dL_dmean2D in absolute value: |o| 0.5 W sum |A qx + B qy|, |o| 0.5 H sum |B qx + C qy|
+        val = ((col == ACC_ABS2D ? ddelx_dx : ddely_dy) * __builtin_fabsf(co.w)) * ma;
+        nz = ma != 0.f;
       } else {
         const bool conic = ia >= 3u && ia <= 5u;  // backward.cu:549-551: -0.5 o t; opacity (:554), colour (:523), depth: the moment itself
         val = conic ? (-0.5f * co.w) * ma : ma;
@@ -1009,6 +1026,10 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
           v[7][u] = mD * dpx[1];
           v[8][u] = mD * dpx[2];
           if constexpr (DEPTH) v[9][u] = mD * dpd;  // dL/dd of the entry
+          if constexpr (ABS) {  // |A qx + B qy|, |B qx + C qy| (cos_ = (-0.5 A, -B, -0.5 C): both signs flipped, exact scaling)
+            v[IABS][u] = __builtin_fabsf(2.f * cos_[u].x * qx + cos_[u].y * qy);
+            v[IABS + 1][u] = __builtin_fabsf(cos_[u].y * qx + 2.f * cos_[u].z * qy);
+          }
         }
       }
       // 4-entry transposed wave reduction: afterwards lane 15 of row r holds the wave totals of entry j + r and adds the
@@ -1038,14 +1059,14 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
   return seg_hi - seg_lo;
 }
 
-template <bool FAST, bool SEG, bool DEPTH>
+template <bool FAST, bool SEG, bool DEPTH, bool ABS>
 __global__ void __launch_bounds__(WAVE* BWD_WAVES) __attribute__((amdgpu_waves_per_eu(4, 4)))
 blend_backward_kernel(const BlendArgs a) {
-  constexpr int LDS_ROW = bwd_lds_row<DEPTH>();
+  constexpr int LDS_ROW = bwd_lds_row<DEPTH, ABS>();
   __shared__ float4 s0[BWD_WAVES][WAVE], s1[BWD_WAVES][WAVE], s2[BWD_WAVES][WAVE];
   __shared__ uint32_t sid[2][WAVE];  // (sid, sco, sacc: double-buffered by chunk parity, see backward_tile)
   __shared__ float4 sco[2][WAVE];
-  __shared__ float sacc[2][WAVE][LDS_ROW];  // raw moments 0..8 (DEPTH: 0..9) of every chunk slot (row stride 9 / 11: odd, the four rows of a flush instruction spread over the banks)
+  __shared__ float sacc[2][WAVE][LDS_ROW];  // raw moments 0..8 (DEPTH: 0..9; ABS: two more) of every chunk slot (row stride 9 / 11 / 13: odd, the four rows of a flush instruction spread over the banks)
   __shared__ uint32_t s_item;
   for (int i = threadIdx.x; i < 2 * WAVE * LDS_ROW; i += WAVE * BWD_WAVES) (&sacc[0][0][0])[i] = 0.f;
   // (element i was zeroed by thread i % 256, i.e. by any wave: with the deferred flush the placement-assigned first item
@@ -1080,7 +1101,7 @@ blend_backward_kernel(const BlendArgs a) {
     const uint32_t r01 = max(cmax.x, cmax.y), r23 = max(cmax.z, cmax.w);
     const uint4 item = make_uint4(code, crange.x, (code & BWD_ITEM_HALF) ? ((code & BWD_ITEM_PART) ? r23 : r01) : max(r01, r23), 0u);
     const uint32_t tile = item.x;
-    const uint32_t tmax = backward_tile<FAST, SEG, DEPTH>(a, item, bg0, bg1, bg2, s0, s1, s2, sid, sco, sacc);
+    const uint32_t tmax = backward_tile<FAST, SEG, DEPTH, ABS>(a, item, bg0, bg1, bg2, s0, s1, s2, sid, sco, sacc);
     if (prof) {
       const uint64_t d = __builtin_amdgcn_s_memtime() - t_tile;
       if (a.profile_items != nullptr && threadIdx.x == 0 && a.work_est != nullptr) {
@@ -1617,16 +1638,43 @@ hipError_t launch_blend_backward(hipStream_t s, BlendArgs a) {
                          (const uint32_t*)nullptr, (const uint32_t*)nullptr, CkTable{}, 0u, 0);
   }
   const dim3 g(grid), b(WAVE * BWD_WAVES);
+#define GSR_BWD_LAUNCH(SEGV, DEPTHV, ABSV)                                                                    \
+  do {                                                                                                        \
+    if (a.fast_exp) hipLaunchKernelGGL((blend_backward_kernel<true, SEGV, DEPTHV, ABSV>), g, b, 0, s, a);      \
+    else hipLaunchKernelGGL((blend_backward_kernel<false, SEGV, DEPTHV, ABSV>), g, b, 0, s, a);                \
+  } while (0)
+  // (abs_grad: GSR_FLAG_ABS_GRAD -- the ABS twins of the three routes, nothing else is instantiated)
   if (a.dL_ddepth != nullptr) {
-    if (a.fast_exp) hipLaunchKernelGGL((blend_backward_kernel<true, false, true>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((blend_backward_kernel<false, false, true>), g, b, 0, s, a);
+    if (a.abs_grad) GSR_BWD_LAUNCH(false, true, true); else GSR_BWD_LAUNCH(false, true, false);
   } else if (seg_items) {
-    if (a.fast_exp) hipLaunchKernelGGL((blend_backward_kernel<true, true, false>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((blend_backward_kernel<false, true, false>), g, b, 0, s, a);
+    if (a.abs_grad) GSR_BWD_LAUNCH(true, false, true); else GSR_BWD_LAUNCH(true, false, false);
   } else {
-    if (a.fast_exp) hipLaunchKernelGGL((blend_backward_kernel<true, false, false>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((blend_backward_kernel<false, false, false>), g, b, 0, s, a);
+    if (a.abs_grad) GSR_BWD_LAUNCH(false, false, true); else GSR_BWD_LAUNCH(false, false, false);
   }
+#undef GSR_BWD_LAUNCH
+  return hipGetLastError();
+}
+// GSR_FLAG_ABS_GRAD: the way of K7's absolute sums out of the accumulator table (gsr_abs_grad_take), between K7 and K8+K9.
+// One thread per Gaussian: a row K7 marked gives up its columns ACC_ABS2D, + 1 and gets zeros back -- K8+K9 then finds the
+// table of a backward without the flag (its `dirty` test does not look at these columns: left in the row they would stay
+// behind whenever the signed sums cancel) --, every other Gaussian gets three zeros without its row being read.
+__global__ void __launch_bounds__(256) abs_grad_take_kernel(int P, float* acc, const uint8_t* touched, float* absgrad) {
+  const int g = (int)(blockIdx.x * 256u + threadIdx.x);
+  if (g >= P) return;
+  float ax = 0.f, ay = 0.f;
+  if (touched == nullptr || touched[g] != 0) {
+    float2* const p = reinterpret_cast<float2*>(acc + (size_t)g * ACC_ROW + ACC_ABS2D);  // (8-byte aligned: the row is 64-byte aligned)
+    const float2 v = *p;
+    ax = v.x;
+    ay = v.y;
+    if (ax != 0.f || ay != 0.f) *p = make_float2(0.f, 0.f);
+  }
+  absgrad[3 * (size_t)g] = ax;
+  absgrad[3 * (size_t)g + 1] = ay;
+  absgrad[3 * (size_t)g + 2] = 0.f;
+}
+hipError_t launch_abs_grad_take(hipStream_t s, int P, float* acc, const uint8_t* touched, float* absgrad) {
+  hipLaunchKernelGGL(abs_grad_take_kernel, dim3(((unsigned)P + 255u) / 256u), dim3(256), 0, s, P, acc, touched, absgrad);
   return hipGetLastError();
 }
 hipError_t launch_trace_weights(hipStream_t s, BlendArgs a) {

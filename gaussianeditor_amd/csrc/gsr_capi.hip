@@ -321,7 +321,8 @@ extern "C" {
 int gsr_abi_version(void) { return GSR_ABI_VERSION; }
 
 // The flags the forward / trace entry points, gsr_blend_backward and gsr_backward accept: all but GSR_FLAG_DEPTH_GRAD, which
-// only the depth backwards and K8+K9 read (include/gsr.h).  GSR_FLAG_ANTIALIAS is among them: K1 and K8+K9 read it, the blend /
+// only the depth backwards and K8+K9 read (include/gsr.h), and GSR_FLAG_ABS_GRAD (not in GSR_FLAG_ALL), which the blend
+// backwards alone take.  GSR_FLAG_ANTIALIAS is among them: K1 and K8+K9 read it, the blend /
 // trace entry points accept it and ignore it (what they blend is already the effective opacity)
 static constexpr unsigned VIEW_FLAGS = GSR_FLAG_ALL & ~GSR_FLAG_DEPTH_GRAD;
 
@@ -647,7 +648,8 @@ static int blend_backward_impl(void* stream, int P, int64_t R, int W, int H, con
                                const void* binning, const void* image, const float* dL_dpix, const float* dL_ddepth,
                                float* acc, uint8_t* touched, unsigned flags) {
   // (a backward of a view whose forward was declared forward-only: the flags of one view travel together)
-  if ((flags & ~GSR_FLAG_ALL) || (flags & (GSR_FLAG_FORWARD_ONLY | GSR_FLAG_ACC_SELF_CLEAN))) return GSR_ERR_BAD_ARGUMENT;
+  // (GSR_FLAG_ABS_GRAD: read here and nowhere else -- VIEW_FLAGS, the mask of every other entry point, does not hold it)
+  if ((flags & ~GSR_FLAG_KNOWN) || (flags & (GSR_FLAG_FORWARD_ONLY | GSR_FLAG_ACC_SELF_CLEAN))) return GSR_ERR_BAD_ARGUMENT;
   if (P == 0) return GSR_OK;
   if (P < 0 || !acc || ((uintptr_t)acc & 63u)) return GSR_ERR_BAD_ARGUMENT;  // (a row must not straddle two 64-byte lines)
   if (touched != nullptr && ((uintptr_t)touched & 15u)) return GSR_ERR_BAD_ARGUMENT;
@@ -672,7 +674,15 @@ static int blend_backward_impl(void* stream, int P, int64_t R, int W, int H, con
   a.shared_simds = (flags & GSR_FLAG_SHARED_SIMDS) ? 1 : 0;
   a.P = P;
   a.clear_grads = (flags & GSR_FLAG_CLEAR_GRADS) ? 1 : 0;
+  a.abs_grad = (flags & GSR_FLAG_ABS_GRAD) ? 1 : 0;
   GSR_HIP(launch_blend_backward((hipStream_t)stream, a));
+  return GSR_OK;
+}
+
+int gsr_abs_grad_take(void* stream, int P, float* acc, const uint8_t* touched, float* absgrad) {
+  if (P == 0) return GSR_OK;
+  if (P < 0 || !acc || ((uintptr_t)acc & 63u) || !absgrad) return GSR_ERR_BAD_ARGUMENT;
+  GSR_HIP(launch_abs_grad_take((hipStream_t)stream, P, acc, touched, absgrad));
   return GSR_OK;
 }
 
@@ -921,6 +931,7 @@ int gsr_backward(void* stream, int P, int D, int M, int64_t R, int W, int H, con
                  float* dL_dscales, float* dL_drots, unsigned flags) {
   (void)colors_precomp;  // the blend kernels read the colour copy held in the geometry records
   if (P == 0) return GSR_OK;
+  if (flags & GSR_FLAG_ABS_GRAD) return GSR_ERR_BAD_ARGUMENT;  // (no output for it here: the halves, with gsr_abs_grad_take between them)
   if (R > 0 && !binning) return GSR_ERR_BAD_ARGUMENT;
   const bool self_clean = (flags & GSR_FLAG_ACC_SELF_CLEAN) != 0;
   if (self_clean && (flags & GSR_FLAG_CLEAR_GRADS)) return GSR_ERR_BAD_ARGUMENT;
@@ -942,6 +953,7 @@ int gsr_backward_depth(void* stream, int P, int D, int M, int64_t R, int W, int 
                        unsigned flags) {
   (void)colors_precomp;
   if (P == 0) return GSR_OK;
+  if (flags & GSR_FLAG_ABS_GRAD) return GSR_ERR_BAD_ARGUMENT;  // (no output for it here: the halves, with gsr_abs_grad_take between them)
   if (R > 0 && !binning) return GSR_ERR_BAD_ARGUMENT;
   const bool self_clean = (flags & GSR_FLAG_ACC_SELF_CLEAN) != 0;
   if (self_clean && (flags & GSR_FLAG_CLEAR_GRADS)) return GSR_ERR_BAD_ARGUMENT;

@@ -22,8 +22,9 @@ constexpr int GAUSS_BLOCK = 256;  // Gaussians per block in the per-Gaussian ker
 // [0] [1] dL_dmean2D.xy  [3] dL_dopacity  [4] [5] [7] dL_dconic.x .y .w  [8..10] dL_dcolor  [11] dL_ddepth (depth backwards
 // only); 2, 6, 12..15 stay zero.
 constexpr uint32_t ACC_ROW = GSR_ACC_ROW, ACC_MEAN2D = GSR_ACC_MEAN2D, ACC_OPACITY = GSR_ACC_OPACITY, ACC_CONIC = GSR_ACC_CONIC,
-                   ACC_COLOR = GSR_ACC_COLOR, ACC_DEPTH = GSR_ACC_DEPTH;
+                   ACC_COLOR = GSR_ACC_COLOR, ACC_DEPTH = GSR_ACC_DEPTH, ACC_ABS2D = GSR_ACC_ABS2D;
 static_assert(ACC_ROW == 16 && ACC_MEAN2D == 0 && ACC_OPACITY == 3 && ACC_CONIC == 4 && ACC_COLOR == 8, "float4-aligned column groups");
+static_assert(ACC_ABS2D == 12, "the absolute sums are .x / .y of the row's last float4, which K8+K9 neither reads nor tests");
 static_assert(ACC_DEPTH == ACC_COLOR + 3, "the depth column is the .w of the colour group: K8+K9 reads it with the colour");
 // Binning works on GROUPS of 8 x 8 tiles (128 x 128 pixels): a Gaussian's tile rectangle inside one group is a 64-bit
 // mask, one bit per tile, bit = (tile_y & 7) * 8 + (tile_x & 7) (gsr_binning.hip).

@@ -107,7 +107,8 @@ struct BlendArgs {
   int fast_exp;    // GSR_FLAG_FAST_EXP: hardware 2^x instead of the specified polynomial (gsr_blend.hip: blend_exp)
   int shared_simds;  // GSR_FLAG_SHARED_SIMDS: 2 persistent waves per SIMD instead of 4 (another stream's kernels run alongside)
   int self_reset;  // the last workgroup to retire clears the queue cursors (default)
-  int reserved;    // (not read: keeps the offsets of the fields behind it)
+  int abs_grad;    // GSR_FLAG_ABS_GRAD: the backward's ABS instantiations (read by launch_blend_backward alone, never by a kernel;
+                   // the slot of a field that went away: the struct, and every kernel's argument layout, keeps its size)
   int for_backward; // forward: the render's state will be read by a backward (not GSR_FLAG_FORWARD_ONLY, not an auxiliary render)
   int units;       // placement units (SIMDs or CUs) for the assigned first items, 0 = none; gsr_blend.hip: first_item_of_block
   // forward checkpoints / backward list segments (Image::ck_*); ck_table == null: none (auxiliary render, tracing)
@@ -172,6 +173,8 @@ hipError_t launch_adam_step(hipStream_t s, int nt, const gsr_adam_tensor* tensor
 hipError_t launch_blend_forward(hipStream_t s, BlendArgs a);
 unsigned blend_grid_size(hipStream_t s, bool shared_simds = false);  // persistent waves of a blend launch on the device of stream s
 hipError_t launch_blend_backward(hipStream_t s, BlendArgs a);
+// GSR_FLAG_ABS_GRAD: columns ACC_ABS2D, + 1 of the accumulator rows -> absgrad (P,3), and back to zero (gsr_blend.hip)
+hipError_t launch_abs_grad_take(hipStream_t s, int P, float* acc, const uint8_t* touched, float* absgrad);
 hipError_t launch_trace_weights(hipStream_t s, BlendArgs a);
 
 }  // namespace gsr

@@ -36,8 +36,9 @@ def attach_grad_allocator(output: torch.Tensor, fn) -> None:
 
 
 def _flags(flags) -> int:
-    # (FLAG_DEPTH_GRAD never reaches the library as a bit: a backward with a depth gradient calls the _depth entry points)
-    return (options.current_flags() if flags is None else int(flags)) & ~options.FLAG_DEPTH_GRAD
+    # (FLAG_DEPTH_GRAD never reaches the library as a bit: a backward with a depth gradient calls the _depth entry points;
+    #  FLAG_ABS_GRAD only from a backward that was given `abs_grad_out`, and then only to its blend half)
+    return (options.current_flags() if flags is None else int(flags)) & ~(options.FLAG_DEPTH_GRAD | options.FLAG_ABS_GRAD)
 
 
 def _require_cuda(t: torch.Tensor, name: str) -> None:
@@ -288,7 +289,7 @@ def _alloc(fn, name: str, shape, zero: bool, dev) -> torch.Tensor:
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
                                  viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
                                  geomBuffer, R, binningBuffer, imageBuffer, debug, flags=None, grad_allocator=None,
-                                 dL_dout_depth=None):
+                                 dL_dout_depth=None, abs_grad_out=None):
     """RasterizeGaussiansBackwardCUDA, rasterize_points.cu:97-157 ->
     (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D | None, dL_dsh, dL_dscales, dL_drotations).
     `flags` (extension, keyword): the flags the forward of this view ran with; None = options.current_flags().
@@ -310,10 +311,23 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                            hold the zeros of an earlier call are not rewritten.
     `dL_dout_depth` (extension, keyword): (1,H,W) gradient of the depth output, or None (the reference: the depth image
     carries no gradient).  Given, the backward also differentiates the depth image (include/gsr.h: GSR_FLAG_DEPTH_GRAD,
-    gsr_backward_depth); not with the "row_state" mode (gsr_preprocess_backward_rows takes no depth gradient)."""
+    gsr_backward_depth); not with the "row_state" mode (gsr_preprocess_backward_rows takes no depth gradient).
+    `abs_grad_out` (extension, keyword): a contiguous (P,3) float32 tensor on the device of `means3D`, or None.  Given, it is
+    fully written with the absolute screen-space gradient (include/gsr.h: GSR_FLAG_ABS_GRAD) -- the backward then always runs
+    as its two halves with gsr_abs_grad_take between them; the eight returned gradients are what they are without it."""
     flags = _flags(flags)
     dev = means3D.device
     P = int(means3D.size(0))
+    if abs_grad_out is not None:
+        if not isinstance(abs_grad_out, torch.Tensor) or abs_grad_out.dtype != torch.float32:
+            raise RuntimeError("diff_gaussian_rasterization: `abs_grad_out` must be a float32 tensor")
+        if tuple(abs_grad_out.shape) != (P, 3) or not abs_grad_out.is_contiguous():
+            raise RuntimeError(f"diff_gaussian_rasterization: `abs_grad_out` must be a contiguous ({P}, 3) tensor, got "
+                               f"{tuple(abs_grad_out.shape)}")
+        if abs_grad_out.device != dev:
+            raise RuntimeError(
+                f"diff_gaussian_rasterization: `abs_grad_out` is on {abs_grad_out.device} but `means3D` is on {dev}; every "
+                "tensor of a call must live on the device of `means3D` (the native library receives raw device pointers)")
     H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
     M = int(sh.size(1)) if sh.size(0) != 0 else 0
     if P == 0:
@@ -388,14 +402,26 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
         dL_dcolors = acc[:, _native.ACC_COLOR:_native.ACC_COLOR + NUM_CHANNELS] if not persist else \
             torch.zeros((0, NUM_CHANNELS), dtype=torch.float32, device=dev)
     L = _native.lib()
+    # absolute screen-space gradients: the blend half takes the bit and a row mask, and gsr_abs_grad_take moves the two
+    # columns out of the table (and zeroes them) in front of K8+K9, whichever entry point that is
+    abs_bit = options.FLAG_ABS_GRAD if abs_grad_out is not None else 0
+
+    def new_touched():  # K7 clears it and marks the rows it adds to
+        return torch.empty(((P + 15) // 16) * 16, dtype=torch.uint8, device=dev)
+
+    def take_abs_grad(touched):
+        if abs_grad_out is not None:
+            _native.check("gsr_abs_grad_take", L.gsr_abs_grad_take(_stream(dev), P, acc.data_ptr(), touched.data_ptr(),
+                                                                   abs_grad_out.data_ptr()))
     with torch.cuda.device(dev):
         col_out = dL_dcolors.data_ptr() if has_colors else None
         if row_state is not None:  # gradient arrays kept across calls: only the rows that change are written
             # (also when nothing was rendered: the call then only clears the accumulator table)
-            touched = torch.empty(((P + 15) // 16) * 16, dtype=torch.uint8, device=dev) if dL_drgb is not None else None
+            touched = new_touched() if (dL_drgb is not None or abs_grad_out is not None) else None
             _native.check("gsr_blend_backward", L.gsr_blend_backward(
                 _stream(dev), P, int(R), W, H, background.data_ptr(), geomBuffer.data_ptr(), _ptr(binningBuffer),
-                imageBuffer.data_ptr(), dL_dpix.data_ptr(), acc.data_ptr(), _ptr(touched), bwd_flags))
+                imageBuffer.data_ptr(), dL_dpix.data_ptr(), acc.data_ptr(), _ptr(touched), bwd_flags | abs_bit))
+            take_abs_grad(touched)
             if dL_drgb is not None:
                 grad_alloc("after_blend_backward", touched[:P], False)
             _native.check("gsr_preprocess_backward_rows_flags", L.gsr_preprocess_backward_rows_flags(
@@ -406,6 +432,29 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                 _ptr(dL_dsh) if dL_drgb is None else None, None if dL_drgb is None else dL_drgb.data_ptr(),
                 dL_dscales.data_ptr() if has_scales else None, dL_drotations.data_ptr() if has_scales else None,
                 row_state.data_ptr(), flags & options.FLAG_ANTIALIAS))
+        elif dL_drgb is None and abs_grad_out is not None:
+            # gsr_backward / gsr_backward_depth as their halves (the fused calls have no output for the absolute sums)
+            touched = new_touched()
+            blend_flags = (bwd_flags & ~options.FLAG_ACC_SELF_CLEAN) | abs_bit
+            if dL_ddepth is None:
+                _native.check("gsr_blend_backward", L.gsr_blend_backward(
+                    _stream(dev), P, int(R), W, H, background.data_ptr(), geomBuffer.data_ptr(), _ptr(binningBuffer),
+                    imageBuffer.data_ptr(), dL_dpix.data_ptr(), acc.data_ptr(), touched.data_ptr(), blend_flags))
+            else:
+                _native.check("gsr_blend_backward_depth", L.gsr_blend_backward_depth(
+                    _stream(dev), P, int(R), W, H, background.data_ptr(), geomBuffer.data_ptr(), _ptr(binningBuffer),
+                    imageBuffer.data_ptr(), dL_dpix.data_ptr(), dL_ddepth.data_ptr(), acc.data_ptr(), touched.data_ptr(),
+                    blend_flags))
+            take_abs_grad(touched)
+            _native.check("gsr_preprocess_backward", L.gsr_preprocess_backward(
+                _stream(dev), P, int(degree), M, W, H, means3D.data_ptr(), _ptr(sh), _ptr(scales), float(scale_modifier),
+                _ptr(rotations), _ptr(cov3D_precomp), viewmatrix.data_ptr(), projmatrix.data_ptr(), _ptr(campos),
+                float(tan_fovx), float(tan_fovy), radii.data_ptr(), geomBuffer.data_ptr(), acc.data_ptr(),
+                dL_dmeans2D.data_ptr(), dL_dopacity.data_ptr(), col_out, dL_dmeans3D.data_ptr(), _ptr(dL_dcov3D),
+                _ptr(dL_dsh), dL_dscales.data_ptr() if has_scales else None,
+                dL_drotations.data_ptr() if has_scales else None,
+                (options.FLAG_ACC_SELF_CLEAN if persist else 0) | (options.FLAG_DEPTH_GRAD if dL_ddepth is not None else 0)
+                | (flags & options.FLAG_ANTIALIAS)))
         elif dL_drgb is None and dL_ddepth is not None:
             _native.check("gsr_backward_depth", L.gsr_backward_depth(
                 _stream(dev), P, int(degree), M, int(R), W, H, background.data_ptr(), means3D.data_ptr(), _ptr(sh),
@@ -426,17 +475,18 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                 dL_drotations.data_ptr() if has_scales else None, bwd_flags))
         else:
             # (also when nothing was rendered: the call then only clears the accumulator table)
-            touched = torch.empty(((P + 15) // 16) * 16, dtype=torch.uint8, device=dev)  # K7 clears it and marks the rows it adds to
+            touched = new_touched()
             if dL_ddepth is None:
                 _native.check("gsr_blend_backward", L.gsr_blend_backward(
                     _stream(dev), P, int(R), W, H, background.data_ptr(), geomBuffer.data_ptr(), _ptr(binningBuffer),
                     imageBuffer.data_ptr(), dL_dpix.data_ptr(), acc.data_ptr(), touched.data_ptr(),
-                    bwd_flags & ~options.FLAG_ACC_SELF_CLEAN))
+                    (bwd_flags & ~options.FLAG_ACC_SELF_CLEAN) | abs_bit))
             else:
                 _native.check("gsr_blend_backward_depth", L.gsr_blend_backward_depth(
                     _stream(dev), P, int(R), W, H, background.data_ptr(), geomBuffer.data_ptr(), _ptr(binningBuffer),
                     imageBuffer.data_ptr(), dL_dpix.data_ptr(), dL_ddepth.data_ptr(), acc.data_ptr(), touched.data_ptr(),
-                    bwd_flags & ~options.FLAG_ACC_SELF_CLEAN))
+                    (bwd_flags & ~options.FLAG_ACC_SELF_CLEAN) | abs_bit))
+            take_abs_grad(touched)
             # notification (no allocation): K7 is enqueued, K8+K9 not yet -- multiview.py starts the exchange of the
             # touched-row counts here (from K7's row mask), so that it and the host's wait for it run underneath K8+K9
             grad_alloc("after_blend_backward", touched[:P], False)

@@ -80,6 +80,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.raster_settings = rs
         ctx.gsr_flags = flags
         ctx.num_rendered = num_rendered
+        if flags & _options.FLAG_ABS_GRAD:
+            ctx.gsr_means2D = means2D  # the caller's screen-space tensor: the backward assigns its `.absgrad`
         # view reuse (_reuse.py): a following colour-override render of this view runs the blend kernel on this state
         _reuse.remember(rs, flags, means3D, scales, rotations, opacities, cov3Ds_precomp, num_rendered, geomBuffer,
                         binningBuffer, imgBuffer, radii, depth)
@@ -106,6 +108,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
          imgBuffer) = ctx.saved_tensors
         depth_grad = _depth_grad(ctx.gsr_flags, grad_depth)
+        abs_grad = _abs_grad_out(ctx.gsr_flags, means3D)
         if grad_out_color is None:  # only the depth output was used downstream
             grad_out_color = torch.zeros((3, rs.image_height, rs.image_width), dtype=torch.float32, device=means3D.device)
         # argument order of _C.rasterize_gaussians_backward (rasterize_points.h:38-60)
@@ -116,9 +119,11 @@ class _RasterizeGaussians(torch.autograd.Function):
          grad_rotations) = _call_native(
              lambda *a: _C.rasterize_gaussians_backward(*a, flags=ctx.gsr_flags,
                                                         grad_allocator=getattr(ctx, "gsr_grad_allocator", None),
-                                                        **_depth_kw(depth_grad)),
+                                                        **_depth_kw(depth_grad), **_abs_kw(abs_grad)),
              args, rs.debug, "snapshot_bw.dump",
              "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
+        if abs_grad is not None:
+            ctx.gsr_means2D.absgrad = abs_grad
         # one slot per forward() input (:213-225)
         return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
                 grad_cov3Ds_precomp, None, None)
@@ -132,6 +137,19 @@ def _depth_grad(flags, grad_depth):
 def _depth_kw(depth_grad):
     # (the keyword only where there is a depth gradient: without one the call is today's, to any `_C` backend)
     return {} if depth_grad is None else {"dL_dout_depth": depth_grad}
+
+
+def _abs_grad_out(flags, means3D):
+    """The tensor a backward fills with the absolute screen-space gradient (and then assigns to `means2D.absgrad`): a new
+    (P,3) one per backward of a render that ran with FLAG_ABS_GRAD (gaussianeditor_amd.set_abs_grad), None otherwise."""
+    if not flags & _options.FLAG_ABS_GRAD:
+        return None
+    return torch.empty((means3D.shape[0], 3), dtype=torch.float32, device=means3D.device)
+
+
+def _abs_kw(abs_grad):
+    # (the keyword only under the flag, as _depth_kw: any `_C` backend without it keeps working with the flag off)
+    return {} if abs_grad is None else {"abs_grad_out": abs_grad}
 
 
 class _ReusedRender(torch.autograd.Function):
@@ -151,6 +169,8 @@ class _ReusedRender(torch.autograd.Function):
         radii, depth = entry.radii.clone(), entry.depth.clone()
         ctx.raster_settings = rs
         ctx.gsr_flags = flags
+        if flags & _options.FLAG_ABS_GRAD:
+            ctx.gsr_means2D = means2D
         ctx.save_for_backward(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
         ctx.mark_non_differentiable(radii)
         ctx.set_materialize_grads(False)
@@ -161,6 +181,7 @@ class _ReusedRender(torch.autograd.Function):
         rs, flags = ctx.raster_settings, ctx.gsr_flags
         means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp = ctx.saved_tensors
         depth_grad = _depth_grad(flags, grad_depth)
+        abs_grad = _abs_grad_out(flags, means3D)
         if grad_out_color is None:
             grad_out_color = torch.zeros((3, rs.image_height, rs.image_width), dtype=torch.float32, device=means3D.device)
         fwd = _C.rasterize_gaussians(rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier,
@@ -171,7 +192,9 @@ class _ReusedRender(torch.autograd.Function):
          grad_rotations) = _C.rasterize_gaussians_backward(
              rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
              rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, sh, rs.sh_degree, rs.campos, geomBuffer, num_rendered,
-             binningBuffer, imgBuffer, rs.debug, flags=flags, **_depth_kw(depth_grad))
+             binningBuffer, imgBuffer, rs.debug, flags=flags, **_depth_kw(depth_grad), **_abs_kw(abs_grad))
+        if abs_grad is not None:
+            ctx.gsr_means2D.absgrad = abs_grad
         return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
                 grad_cov3Ds_precomp, None, None)
 

@@ -63,7 +63,8 @@ extern "C" {
 /* 6 (round 6): adds gsr_preprocess_begin / gsr_preprocess_end (nothing else changed).  Later, purely additive (the number
  * stays): GSR_FLAG_DEPTH_GRAD, the GSR_ACC_DEPTH column, gsr_blend_backward_depth and gsr_backward_depth -- every earlier
  * entry point keeps its signature and its behaviour.  Then, likewise additive: GSR_FLAG_ANTIALIAS and
- * gsr_preprocess_backward_rows_flags. */
+ * gsr_preprocess_backward_rows_flags.  Then, likewise additive: GSR_FLAG_ABS_GRAD, the GSR_ACC_ABS2D columns and
+ * gsr_abs_grad_take. */
 #define GSR_ABI_VERSION 6
 /* The blend backward's accumulator table: GSR_ACC_ROW floats (one 64-byte line) per Gaussian, 64-byte aligned.  Columns:
  *   [GSR_ACC_MEAN2D] .x [+1] .y of dL_dmean2D      (backward.cu:545-546)
@@ -72,6 +73,9 @@ extern "C" {
  *   [GSR_ACC_COLOR .. +2] dL_dcolor                (backward.cu:523)
  *   [GSR_ACC_DEPTH] dL_ddepth, the gradient of the Gaussian's view-space depth: sum over pixels of alpha T dL_dout_depth
  *       (written by gsr_blend_backward_depth only; no reference counterpart)
+ *   [GSR_ACC_ABS2D] .x [+1] .y of the ABSOLUTE screen-space gradient: the sums over pixels of the absolute values of the
+ *       per-pixel terms of dL_dmean2D (written under GSR_FLAG_ABS_GRAD only, taken out again by gsr_abs_grad_take; no
+ *       reference counterpart)
  * every other column stays zero.  Why one row: float atomics execute at the memory side on this chip and cost per REQUEST;
  * the lanes of a wave instruction that fall into one 64-byte line travel as one request, so the (up to nine) adds of a
  * (tile, Gaussian) pair leave as one instead of nine (tools/microbench/atomic_merge.hip: 8.8x). */
@@ -81,6 +85,7 @@ extern "C" {
 #define GSR_ACC_CONIC 4
 #define GSR_ACC_COLOR 8
 #define GSR_ACC_DEPTH 11
+#define GSR_ACC_ABS2D 12
 /* Largest image the blend BACKWARD accepts, in 16 x 16 tiles (its work items carry the tile id in 20 bits). */
 #define GSR_MAX_TILES (1 << 20)
 
@@ -171,6 +176,17 @@ int gsr_scratch_sizes(int P, int64_t R, int64_t G, int W, int H, size_t sizes[3]
  *                        instead of spreading its full opacity over the dilated footprint.  The backward differentiates h
  *                        (dL_dopacity = h dL/d(opacity h), plus the share of r in the covariance gradients).  The reference
  *                        has no such mode.  The calls of one view must all receive the bit or none of them.
+ *   GSR_FLAG_ABS_GRAD    (read by gsr_blend_backward and gsr_blend_backward_depth, and by nothing else) K7 also accumulates
+ *                        the absolute screen-space gradient ("absgrad", the densification statistic of AbsGS): for every
+ *                        Gaussian the sums over the pixels p that blend it of |t_x(p)| and |t_y(p)|, t(p) the term pixel p
+ *                        adds into dL_dmean2D (backward.cu:545-546, with the 0.5 W / 0.5 H factors; under
+ *                        gsr_blend_backward_depth with the depth image's share of dL/dalpha in it), into the columns
+ *                        GSR_ACC_ABS2D, + 1 of the accumulator row.  Hence >= |dL_dmean2D| per component, equal where a
+ *                        Gaussian's terms share a sign.  gsr_abs_grad_take, called between the two halves, moves the sums
+ *                        out and leaves the columns zero; every other column, and with it every other gradient, is what it
+ *                        is without the flag.  The forward / trace entry points, gsr_backward and gsr_backward_depth (which
+ *                        have no output for it) and the K8+K9 entry points refuse the bit: like GSR_FLAG_DEPTH_GRAD it is
+ *                        a backward-only bit a caller keeps to itself until gsr_blend_backward[_depth].
  * Unknown bits are rejected with GSR_ERR_BAD_ARGUMENT. */
 #define GSR_FLAG_TILE_BOUNDS_ALPHA 1u
 #define GSR_FLAG_FAST_EXP 2u
@@ -181,6 +197,9 @@ int gsr_scratch_sizes(int P, int64_t R, int64_t G, int W, int H, size_t sizes[3]
 #define GSR_FLAG_DEPTH_GRAD 64u
 #define GSR_FLAG_ANTIALIAS 1024u
 #define GSR_FLAG_ALL (127u | GSR_FLAG_ANTIALIAS)
+#define GSR_FLAG_ABS_GRAD 4096u
+/* every bit the library knows: GSR_FLAG_ALL is what the view-wide entry points take, GSR_FLAG_ABS_GRAD only the blend backwards */
+#define GSR_FLAG_KNOWN (GSR_FLAG_ALL | GSR_FLAG_ABS_GRAD)
 
 /* Number of sort-key bits, 32 + getHigherMsb(tiles) (rasterizer_impl.cu:36-49, 253). */
 int gsr_sort_key_bits(int W, int H);
@@ -324,6 +343,15 @@ int gsr_backward_depth(void* stream, int P, int D, int M, int64_t R, int W, int 
                        const float* dL_ddepth, float* acc, float* dL_dmeans2D, float* dL_dopacity, float* dL_dcolors,
                        float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drots,
                        unsigned flags);
+
+/* Absolute screen-space gradients (opt-in, GSR_FLAG_ABS_GRAD): after gsr_blend_backward[_depth] with the flag and BEFORE the
+ * K8+K9 entry point of the view, on the same stream.  One thread per Gaussian g: where touched[g] != 0 (touched == NULL:
+ * everywhere) absgrad[g] = (acc[g][GSR_ACC_ABS2D], acc[g][GSR_ACC_ABS2D + 1], 0) and the two columns are put back to zero;
+ * elsewhere absgrad[g] = (0, 0, 0) and the row is not read.  absgrad (P,3) is fully written.  `touched` is the row mask the
+ * blend backward of this view wrote (a row it did not mark holds zeros in these columns).  Afterwards the table is what a
+ * backward without the flag leaves, so K8+K9 -- whichever entry point, GSR_FLAG_ACC_SELF_CLEAN included -- runs unchanged.
+ * acc: 64-byte aligned, as for gsr_blend_backward.  P == 0 is an empty call. */
+int gsr_abs_grad_take(void* stream, int P, float* acc, const uint8_t* touched, float* absgrad);
 
 /* Multi-GPU exchange support (gaussianeditor_amd/multiview.py).  Per view the SH gradient is
  * rank one, dL_dsh[k] = c_k(dir) * dL_dRGB with dir = normalize(mean - campos) (backward.cu:44-98), so ranks exchange
