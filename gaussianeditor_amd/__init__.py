@@ -104,6 +104,25 @@ def get_abs_grad() -> bool:
     return bool(options.default_flags() & options.FLAG_ABS_GRAD)
 
 
+def set_alpha_output(on: bool) -> None:
+    """Opt-in: the default of FLAG_ALPHA_OUT (options.py; a bit of the binding, the library has none) -- `render()` also
+    returns the alpha image, `out["alpha"]`: (1,H,W) float32, per pixel the accumulated opacity A = 1 - prod (1 - alpha_i)
+    over the Gaussians the pixel blended, i.e. 1 - the final transmittance.  It carries a gradient (a mask / silhouette loss
+    reaches means3D, scales, rotations and opacities), and `depth_3dgs / alpha.clamp_min(eps)` is the normalised depth.
+    `render(..., return_alpha=True)` and `GaussianRasterizer.forward(..., return_alpha=True)` ask for it per call whatever
+    the flag says.  Off (default): the dict has no such key and nothing else changes."""
+    from . import options
+
+    f = options.default_flags() & ~options.FLAG_ALPHA_OUT
+    options.set_default_flags(f | (options.FLAG_ALPHA_OUT if on else 0))
+
+
+def get_alpha_output() -> bool:
+    from . import options
+
+    return bool(options.default_flags() & options.FLAG_ALPHA_OUT)
+
+
 def set_antialiasing(on: bool) -> None:
     """Opt-in: the default of GSR_FLAG_ANTIALIAS (include/gsr.h) -- the opacity-compensated 2D filter of antialiased
     3DGS rasterizers.  Every Gaussian is blended with opacity * h, h = sqrt(max(2.5e-5, det(S) / det(S + 0.3 I))) of its

@@ -69,6 +69,10 @@ SIGNATURES = {
                                    c_uint]),
     # absolute screen-space gradients (GSR_FLAG_ABS_GRAD), between the two halves: (stream, P, acc, touched, absgrad (P,3))
     "gsr_abs_grad_take": (c_int, [_P, c_int, _P, _P, _P]),
+    # alpha image: (stream, W, H, image, out_alpha (1,H,W)); its backward: gsr_blend_backward with dL_ddepth | NULL and
+    # dL_dalpha (1,H,W) behind dL_dpix
+    "gsr_alpha_image": (c_int, [_P, c_int, c_int, _P, _P]),
+    "gsr_blend_backward_alpha": (c_int, [_P, c_int, c_int64, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_uint]),
     # (... radii, geom, acc, dL_dmeans2D, dL_dopacity, dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drots, flags)
     "gsr_preprocess_backward": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_float, _P, _P, _P, _P, _P,
                                         c_float, c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_uint]),

@@ -759,7 +759,12 @@ static_assert(BWD_ITEM_TILE + 1u == (uint32_t)GSR_MAX_TILES, "include/gsr.h stat
 // drops out of the absolute value), the two moments are reduced and added to the chunk's LDS row like the others, and the
 // flush multiplies by |o| 0.5 W, |o| 0.5 H.  Every item shape takes it as it is: an entry is seen once by every pixel of an
 // item, whole tile, half tile or list segment, and absolute sums add over any partition of the pixels.
-template <bool FAST, bool SEG, bool DEPTH, bool ABS>
+//
+// ALPHA (gsr_blend_backward_alpha): the alpha image A = 1 - T_final of the pixel carries a gradient gA.  dA/dalpha_i =
+// T_final / (1 - alpha_i) for every blended entry: the shape of the background's share, with the opposite sign -- so gA is
+// subtracted from bg . dL_dpixel, once per pixel, and everything behind dL/dalpha moves with it (the ABS sums included).  A
+// list segment takes it as it is: the term is applied per entry from the pixel's own T_final, whatever lies behind the run.
+template <bool FAST, bool SEG, bool DEPTH, bool ABS, bool ALPHA>
 __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint4 item, const float bg0, const float bg1,
                                               const float bg2, float4 (*s0)[WAVE], float4 (*s1)[WAVE], float4 (*s2)[WAVE],
                                               uint32_t (*sid)[WAVE], float4 (*sco)[WAVE],
@@ -802,6 +807,7 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
   const uint32_t n_contrib_ld = a.n_contrib[pix];
   const float dpx_ld[3] = {a.dL_dpix[pix], a.dL_dpix[HW + pix], a.dL_dpix[2 * HW + pix]};
   const float dpd_ld = DEPTH ? a.dL_ddepth[pix] : 0.f;
+  const float dpa_ld = ALPHA ? a.dL_dalpha[pix] : 0.f;
   // back to front over the item's positions [seg_lo, seg_hi) of the tile's list, all four waves in the same chunks
   ChunkWalker<false> walk(a, list_base + seg_lo, seg_hi - seg_lo);
 
@@ -811,7 +817,9 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
   const uint32_t maxc = wave_max_u32_dpp(last_contributor);  // (this wave's pixels; the item's is tile_max)
   const float dpx[3] = {live ? dpx_ld[0] : 0.f, live ? dpx_ld[1] : 0.f, live ? dpx_ld[2] : 0.f};
   const float dpd = live ? dpd_ld : 0.f;  // (DEPTH) dL_dout_depth of the pixel
-  const float bg_dot_dpixel = (0.f + bg0 * dpx[0]) + bg1 * dpx[1] + bg2 * dpx[2];
+  const float dpa = live ? dpa_ld : 0.f;  // (ALPHA) dL_dout_alpha of the pixel
+  const float bg_dot_dpixel = ALPHA ? ((0.f + bg0 * dpx[0]) + bg1 * dpx[1] + bg2 * dpx[2]) - dpa
+                                    : (0.f + bg0 * dpx[0]) + bg1 * dpx[1] + bg2 * dpx[2];
   const float neg_Tfinal_bg = -T_final * bg_dot_dpixel;  // the background's share of dL/dalpha is this times 1 / (1 - alpha)
   const float ddelx_dx = 0.5f * a.W, ddely_dy = 0.5f * a.H;
 
@@ -1059,7 +1067,7 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
   return seg_hi - seg_lo;
 }
 
-template <bool FAST, bool SEG, bool DEPTH, bool ABS>
+template <bool FAST, bool SEG, bool DEPTH, bool ABS, bool ALPHA>
 __global__ void __launch_bounds__(WAVE* BWD_WAVES) __attribute__((amdgpu_waves_per_eu(4, 4)))
 blend_backward_kernel(const BlendArgs a) {
   constexpr int LDS_ROW = bwd_lds_row<DEPTH, ABS>();
@@ -1101,7 +1109,7 @@ blend_backward_kernel(const BlendArgs a) {
     const uint32_t r01 = max(cmax.x, cmax.y), r23 = max(cmax.z, cmax.w);
     const uint4 item = make_uint4(code, crange.x, (code & BWD_ITEM_HALF) ? ((code & BWD_ITEM_PART) ? r23 : r01) : max(r01, r23), 0u);
     const uint32_t tile = item.x;
-    const uint32_t tmax = backward_tile<FAST, SEG, DEPTH, ABS>(a, item, bg0, bg1, bg2, s0, s1, s2, sid, sco, sacc);
+    const uint32_t tmax = backward_tile<FAST, SEG, DEPTH, ABS, ALPHA>(a, item, bg0, bg1, bg2, s0, s1, s2, sid, sco, sacc);
     if (prof) {
       const uint64_t d = __builtin_amdgcn_s_memtime() - t_tile;
       if (a.profile_items != nullptr && threadIdx.x == 0 && a.work_est != nullptr) {
@@ -1638,10 +1646,16 @@ hipError_t launch_blend_backward(hipStream_t s, BlendArgs a) {
                          (const uint32_t*)nullptr, (const uint32_t*)nullptr, CkTable{}, 0u, 0);
   }
   const dim3 g(grid), b(WAVE * BWD_WAVES);
+#define GSR_BWD_LAUNCH2(SEGV, DEPTHV, ABSV, ALPHAV)                                                                   \
+  do {                                                                                                                \
+    if (a.fast_exp) hipLaunchKernelGGL((blend_backward_kernel<true, SEGV, DEPTHV, ABSV, ALPHAV>), g, b, 0, s, a);      \
+    else hipLaunchKernelGGL((blend_backward_kernel<false, SEGV, DEPTHV, ABSV, ALPHAV>), g, b, 0, s, a);                \
+  } while (0)
+  // (dL_dalpha: gsr_blend_backward_alpha -- the ALPHA twin of whatever the call would launch without it)
 #define GSR_BWD_LAUNCH(SEGV, DEPTHV, ABSV)                                                                    \
   do {                                                                                                        \
-    if (a.fast_exp) hipLaunchKernelGGL((blend_backward_kernel<true, SEGV, DEPTHV, ABSV>), g, b, 0, s, a);      \
-    else hipLaunchKernelGGL((blend_backward_kernel<false, SEGV, DEPTHV, ABSV>), g, b, 0, s, a);                \
+    if (a.dL_dalpha != nullptr) GSR_BWD_LAUNCH2(SEGV, DEPTHV, ABSV, true);                                    \
+    else GSR_BWD_LAUNCH2(SEGV, DEPTHV, ABSV, false);                                                          \
   } while (0)
   // (abs_grad: GSR_FLAG_ABS_GRAD -- the ABS twins of the three routes, nothing else is instantiated)
   if (a.dL_ddepth != nullptr) {
@@ -1652,6 +1666,7 @@ hipError_t launch_blend_backward(hipStream_t s, BlendArgs a) {
     if (a.abs_grad) GSR_BWD_LAUNCH(false, false, true); else GSR_BWD_LAUNCH(false, false, false);
   }
 #undef GSR_BWD_LAUNCH
+#undef GSR_BWD_LAUNCH2
   return hipGetLastError();
 }
 // GSR_FLAG_ABS_GRAD: the way of K7's absolute sums out of the accumulator table (gsr_abs_grad_take), between K7 and K8+K9.
@@ -1675,6 +1690,28 @@ __global__ void __launch_bounds__(256) abs_grad_take_kernel(int P, float* acc, c
 }
 hipError_t launch_abs_grad_take(hipStream_t s, int P, float* acc, const uint8_t* touched, float* absgrad) {
   hipLaunchKernelGGL(abs_grad_take_kernel, dim3(((unsigned)P + 255u) / 256u), dim3(256), 0, s, P, acc, touched, absgrad);
+  return hipGetLastError();
+}
+// The alpha image A = 1 - T_final (gsr_alpha_image) from the image state a forward left: one thread per pixel, or per four
+// pixels where the pixel count allows whole float4s (the state's arrays are 256-byte aligned; `out` is the caller's).  A
+// kernel of its own and not a K6 twin: the auxiliary render and a render served by view reuse get the image from the
+// remembered state without a K6 of theirs, and K6's instantiations stay what they are.
+__global__ void __launch_bounds__(256) alpha_image_kernel(size_t n, int vec4, const float* __restrict__ final_T,
+                                                          float* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;  // (n: float4s if vec4 -- uniform --, else pixels)
+  if (i >= n) return;
+  if (vec4) {
+    const float4 t = reinterpret_cast<const float4*>(final_T)[i];
+    reinterpret_cast<float4*>(out)[i] = make_float4(1.0f - t.x, 1.0f - t.y, 1.0f - t.z, 1.0f - t.w);
+  } else {
+    out[i] = 1.0f - final_T[i];
+  }
+}
+hipError_t launch_alpha_image(hipStream_t s, int W, int H, const float* final_T, float* out_alpha) {
+  const size_t N = (size_t)W * H;
+  const int vec4 = ((N & 3u) == 0 && (((uintptr_t)final_T | (uintptr_t)out_alpha) & 15u) == 0) ? 1 : 0;
+  const size_t n = vec4 ? N / 4 : N;
+  hipLaunchKernelGGL(alpha_image_kernel, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, s, n, vec4, final_T, out_alpha);
   return hipGetLastError();
 }
 hipError_t launch_trace_weights(hipStream_t s, BlendArgs a) {

@@ -643,10 +643,11 @@ int gsr_debug_blend_forward_profile(void* stream, int P, int64_t R, int W, int H
   return GSR_OK;
 }
 
-// gsr_blend_backward and gsr_blend_backward_depth (dL_ddepth != null: the DEPTH kernels)
+// gsr_blend_backward, gsr_blend_backward_depth (dL_ddepth != null: the DEPTH kernels) and gsr_blend_backward_alpha (dL_dalpha
+// != null: the ALPHA kernels)
 static int blend_backward_impl(void* stream, int P, int64_t R, int W, int H, const float* bg, const void* geom,
                                const void* binning, const void* image, const float* dL_dpix, const float* dL_ddepth,
-                               float* acc, uint8_t* touched, unsigned flags) {
+                               float* acc, uint8_t* touched, unsigned flags, const float* dL_dalpha = nullptr) {
   // (a backward of a view whose forward was declared forward-only: the flags of one view travel together)
   // (GSR_FLAG_ABS_GRAD: read here and nowhere else -- VIEW_FLAGS, the mask of every other entry point, does not hold it)
   if ((flags & ~GSR_FLAG_KNOWN) || (flags & (GSR_FLAG_FORWARD_ONLY | GSR_FLAG_ACC_SELF_CLEAN))) return GSR_ERR_BAD_ARGUMENT;
@@ -668,6 +669,7 @@ static int blend_backward_impl(void* stream, int P, int64_t R, int W, int H, con
   BlendArgs a = make_blend_args(W, H, g, b, im, bg, 1, R);
   a.dL_dpix = dL_dpix;
   a.dL_ddepth = dL_ddepth;
+  a.dL_dalpha = dL_dalpha;  // (the slot of out_color, which no backward kernel reads)
   a.acc = acc;
   a.touched = touched;
   a.fast_exp = (flags & GSR_FLAG_FAST_EXP) ? 1 : 0;
@@ -700,6 +702,24 @@ int gsr_blend_backward_depth(void* stream, int P, int64_t R, int W, int H, const
   if (P > 0 && R > 0 && !dL_ddepth) return GSR_ERR_BAD_ARGUMENT;
   return blend_backward_impl(stream, P, R, W, H, bg, geom, binning, image, dL_dpix, dL_ddepth, acc, touched,
                              flags & ~GSR_FLAG_DEPTH_GRAD);
+}
+
+int gsr_blend_backward_alpha(void* stream, int P, int64_t R, int W, int H, const float* bg, const void* geom,
+                             const void* binning, const void* image, const float* dL_dpix, const float* dL_ddepth,
+                             const float* dL_dalpha, float* acc, uint8_t* touched, unsigned flags) {
+  // (dL_dalpha is what the entry point is for: required whatever P and R are; dL_ddepth is optional, and the bit that
+  //  announces it is refused without it)
+  if (!dL_dalpha) return GSR_ERR_BAD_ARGUMENT;
+  if ((flags & GSR_FLAG_DEPTH_GRAD) && !dL_ddepth) return GSR_ERR_BAD_ARGUMENT;
+  return blend_backward_impl(stream, P, R, W, H, bg, geom, binning, image, dL_dpix, dL_ddepth, acc, touched,
+                             flags & ~GSR_FLAG_DEPTH_GRAD, dL_dalpha);
+}
+
+int gsr_alpha_image(void* stream, int W, int H, const void* image, float* out_alpha) {
+  if (W <= 0 || H <= 0 || !image || misaligned(image) || !out_alpha || ((uintptr_t)out_alpha & 3u)) return GSR_ERR_BAD_ARGUMENT;
+  const Image im = carve_image(const_cast<void*>(image), W, H);
+  GSR_HIP(launch_alpha_image((hipStream_t)stream, W, H, im.final_T, out_alpha));
+  return GSR_OK;
 }
 
 static int preprocess_backward_impl(void* stream, int P, int D, int M, int W, int H, const float* means3D, const float* shs,

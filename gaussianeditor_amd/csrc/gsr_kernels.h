@@ -87,7 +87,11 @@ struct BlendArgs {
   float* final_T;
   uint32_t* n_contrib;
   // forward outputs
-  float* out_color;
+  union {
+    float* out_color;
+    const float* dL_dalpha;  // backward: (1,H,W) gradient of the alpha image 1 - final_T (gsr_blend_backward_alpha), or null --
+                             // as dL_ddepth below, in the slot of an output only the forward writes
+  };
   union {
     float* out_depth;
     const float* dL_ddepth;  // backward: (1,H,W) gradient of out_depth (gsr_blend_backward_depth), or null -- the slot of the
@@ -175,6 +179,8 @@ unsigned blend_grid_size(hipStream_t s, bool shared_simds = false);  // persiste
 hipError_t launch_blend_backward(hipStream_t s, BlendArgs a);
 // GSR_FLAG_ABS_GRAD: columns ACC_ABS2D, + 1 of the accumulator rows -> absgrad (P,3), and back to zero (gsr_blend.hip)
 hipError_t launch_abs_grad_take(hipStream_t s, int P, float* acc, const uint8_t* touched, float* absgrad);
+// the alpha image (accumulated opacity) 1 - final_T of the image state a forward left (gsr_blend.hip)
+hipError_t launch_alpha_image(hipStream_t s, int W, int H, const float* final_T, float* out_alpha);
 hipError_t launch_trace_weights(hipStream_t s, BlendArgs a);
 
 }  // namespace gsr

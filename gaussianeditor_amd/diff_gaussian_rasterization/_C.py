@@ -37,8 +37,10 @@ def attach_grad_allocator(output: torch.Tensor, fn) -> None:
 
 def _flags(flags) -> int:
     # (FLAG_DEPTH_GRAD never reaches the library as a bit: a backward with a depth gradient calls the _depth entry points;
-    #  FLAG_ABS_GRAD only from a backward that was given `abs_grad_out`, and then only to its blend half)
-    return (options.current_flags() if flags is None else int(flags)) & ~(options.FLAG_DEPTH_GRAD | options.FLAG_ABS_GRAD)
+    #  FLAG_ABS_GRAD only from a backward that was given `abs_grad_out`, and then only to its blend half; FLAG_ALPHA_OUT
+    #  never: the library has no such bit, alpha_image / `dL_dout_alpha` say what is asked)
+    return (options.current_flags() if flags is None else int(flags)) & ~(options.FLAG_DEPTH_GRAD | options.FLAG_ABS_GRAD
+                                                                          | options.FLAG_ALPHA_OUT)
 
 
 def _require_cuda(t: torch.Tensor, name: str) -> None:
@@ -262,6 +264,23 @@ def rasterize_gaussians_aux(background, colors, num_rendered, geomBuffer, binnin
     return out
 
 
+def alpha_image(imgBuffer, image_height, image_width):
+    """Extension (no reference counterpart; include/gsr.h gsr_alpha_image): the alpha image (1,H,W) float32 of the view whose
+    image state `imgBuffer` a rasterize_gaussians() call returned -- accumulated opacity, 1 - final_T.  One small kernel; the
+    state is only read.  An empty buffer (a scene without Gaussians) gives zeros."""
+    if not isinstance(imgBuffer, torch.Tensor) or imgBuffer.dtype != torch.uint8:
+        raise RuntimeError("diff_gaussian_rasterization: `imgBuffer` must be a torch.uint8 tensor")
+    H, W = int(image_height), int(image_width)
+    dev = imgBuffer.device
+    if imgBuffer.numel() == 0:
+        return torch.zeros((1, H, W), dtype=torch.float32, device=dev)
+    _require_cuda(imgBuffer, "imgBuffer")
+    out = torch.empty((1, H, W), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _native.check("gsr_alpha_image", _native.lib().gsr_alpha_image(_stream(dev), W, H, imgBuffer.data_ptr(), out.data_ptr()))
+    return out
+
+
 #: The blend backward's accumulator table kept ACROSS backwards (GSR_FLAG_ACC_SELF_CLEAN, include/gsr.h): one zeroed (P,16)
 #: buffer per (device, stream), checked out for the duration of a backward's two native calls and put back only when both were
 #: enqueued -- K8+K9 leaves it all zero again in stream order, so the next backward on that stream needs no clear (64 MB in
@@ -289,7 +308,7 @@ def _alloc(fn, name: str, shape, zero: bool, dev) -> torch.Tensor:
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
                                  viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
                                  geomBuffer, R, binningBuffer, imageBuffer, debug, flags=None, grad_allocator=None,
-                                 dL_dout_depth=None, abs_grad_out=None):
+                                 dL_dout_depth=None, abs_grad_out=None, dL_dout_alpha=None):
     """RasterizeGaussiansBackwardCUDA, rasterize_points.cu:97-157 ->
     (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D | None, dL_dsh, dL_dscales, dL_drotations).
     `flags` (extension, keyword): the flags the forward of this view ran with; None = options.current_flags().
@@ -314,10 +333,25 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     gsr_backward_depth); not with the "row_state" mode (gsr_preprocess_backward_rows takes no depth gradient).
     `abs_grad_out` (extension, keyword): a contiguous (P,3) float32 tensor on the device of `means3D`, or None.  Given, it is
     fully written with the absolute screen-space gradient (include/gsr.h: GSR_FLAG_ABS_GRAD) -- the backward then always runs
-    as its two halves with gsr_abs_grad_take between them; the eight returned gradients are what they are without it."""
+    as its two halves with gsr_abs_grad_take between them; the eight returned gradients are what they are without it.
+    `dL_dout_alpha` (extension, keyword): (1,H,W) float32 gradient of the alpha image (alpha_image()), or None.  Given, the
+    blend half is gsr_blend_backward_alpha (with `dL_dout_depth` too, if that is given) and the backward runs as its two
+    halves; the K8+K9 half is the one the route uses without it."""
     flags = _flags(flags)
     dev = means3D.device
     P = int(means3D.size(0))
+    if dL_dout_alpha is not None:
+        hw = tuple(dL_dout_color.shape[1:]) if isinstance(dL_dout_color, torch.Tensor) and dL_dout_color.dim() == 3 else None
+        if not isinstance(dL_dout_alpha, torch.Tensor) or dL_dout_alpha.dtype != torch.float32:
+            raise RuntimeError("diff_gaussian_rasterization: `dL_dout_alpha` must be a float32 tensor, got "
+                               f"{getattr(dL_dout_alpha, 'dtype', type(dL_dout_alpha).__name__)}")
+        if hw is None or tuple(dL_dout_alpha.shape) != (1,) + hw:
+            raise RuntimeError(f"diff_gaussian_rasterization: `dL_dout_alpha` must be a {(1,) + (hw or ('H', 'W'))} tensor, "
+                               f"got {tuple(dL_dout_alpha.shape)}")
+        if dL_dout_alpha.device != dev:
+            raise RuntimeError(
+                f"diff_gaussian_rasterization: `dL_dout_alpha` is on {dL_dout_alpha.device} but `means3D` is on {dev}; every "
+                "tensor of a call must live on the device of `means3D` (the native library receives raw device pointers)")
     if abs_grad_out is not None:
         if not isinstance(abs_grad_out, torch.Tensor) or abs_grad_out.dtype != torch.float32:
             raise RuntimeError("diff_gaussian_rasterization: `abs_grad_out` must be a float32 tensor")
@@ -347,6 +381,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
         if dL_ddepth.numel() != H * W or dL_ddepth.device != dev:
             raise RuntimeError(f"diff_gaussian_rasterization: `dL_dout_depth` must be a (1, {H}, {W}) tensor on {dev}, "
                                f"got {tuple(dL_ddepth.shape)} on {dL_ddepth.device}")
+    dL_dalpha = None if dL_dout_alpha is None else _f32(dL_dout_alpha, "dL_dout_alpha", dev)
     _on_device(radii, "radii", dev, torch.int32)
     for name, buf in (("geomBuffer", geomBuffer), ("binningBuffer", binningBuffer), ("imageBuffer", imageBuffer)):
         _on_device(buf, name, dev, torch.uint8)
@@ -413,14 +448,24 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
         if abs_grad_out is not None:
             _native.check("gsr_abs_grad_take", L.gsr_abs_grad_take(_stream(dev), P, acc.data_ptr(), touched.data_ptr(),
                                                                    abs_grad_out.data_ptr()))
+
+    def blend_half(touched, blend_flags):  # K7 through the entry point that takes the pixel gradients this backward was given
+        head = (_stream(dev), P, int(R), W, H, background.data_ptr(), geomBuffer.data_ptr(), _ptr(binningBuffer),
+                imageBuffer.data_ptr(), dL_dpix.data_ptr())
+        tail = (acc.data_ptr(), _ptr(touched), blend_flags)
+        if dL_dalpha is not None:
+            _native.check("gsr_blend_backward_alpha", L.gsr_blend_backward_alpha(
+                *head, None if dL_ddepth is None else dL_ddepth.data_ptr(), dL_dalpha.data_ptr(), *tail))
+        elif dL_ddepth is not None:
+            _native.check("gsr_blend_backward_depth", L.gsr_blend_backward_depth(*head, dL_ddepth.data_ptr(), *tail))
+        else:
+            _native.check("gsr_blend_backward", L.gsr_blend_backward(*head, *tail))
     with torch.cuda.device(dev):
         col_out = dL_dcolors.data_ptr() if has_colors else None
         if row_state is not None:  # gradient arrays kept across calls: only the rows that change are written
             # (also when nothing was rendered: the call then only clears the accumulator table)
             touched = new_touched() if (dL_drgb is not None or abs_grad_out is not None) else None
-            _native.check("gsr_blend_backward", L.gsr_blend_backward(
-                _stream(dev), P, int(R), W, H, background.data_ptr(), geomBuffer.data_ptr(), _ptr(binningBuffer),
-                imageBuffer.data_ptr(), dL_dpix.data_ptr(), acc.data_ptr(), _ptr(touched), bwd_flags | abs_bit))
+            blend_half(touched, bwd_flags | abs_bit)
             take_abs_grad(touched)
             if dL_drgb is not None:
                 grad_alloc("after_blend_backward", touched[:P], False)
@@ -432,19 +477,11 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                 _ptr(dL_dsh) if dL_drgb is None else None, None if dL_drgb is None else dL_drgb.data_ptr(),
                 dL_dscales.data_ptr() if has_scales else None, dL_drotations.data_ptr() if has_scales else None,
                 row_state.data_ptr(), flags & options.FLAG_ANTIALIAS))
-        elif dL_drgb is None and abs_grad_out is not None:
-            # gsr_backward / gsr_backward_depth as their halves (the fused calls have no output for the absolute sums)
-            touched = new_touched()
-            blend_flags = (bwd_flags & ~options.FLAG_ACC_SELF_CLEAN) | abs_bit
-            if dL_ddepth is None:
-                _native.check("gsr_blend_backward", L.gsr_blend_backward(
-                    _stream(dev), P, int(R), W, H, background.data_ptr(), geomBuffer.data_ptr(), _ptr(binningBuffer),
-                    imageBuffer.data_ptr(), dL_dpix.data_ptr(), acc.data_ptr(), touched.data_ptr(), blend_flags))
-            else:
-                _native.check("gsr_blend_backward_depth", L.gsr_blend_backward_depth(
-                    _stream(dev), P, int(R), W, H, background.data_ptr(), geomBuffer.data_ptr(), _ptr(binningBuffer),
-                    imageBuffer.data_ptr(), dL_dpix.data_ptr(), dL_ddepth.data_ptr(), acc.data_ptr(), touched.data_ptr(),
-                    blend_flags))
+        elif dL_drgb is None and (abs_grad_out is not None or dL_dalpha is not None):
+            # gsr_backward / gsr_backward_depth as their halves (the fused calls have no output for the absolute sums and no
+            # input for the alpha image's gradient); the row mask only where gsr_abs_grad_take reads it
+            touched = new_touched() if abs_grad_out is not None else None
+            blend_half(touched, (bwd_flags & ~options.FLAG_ACC_SELF_CLEAN) | abs_bit)
             take_abs_grad(touched)
             _native.check("gsr_preprocess_backward", L.gsr_preprocess_backward(
                 _stream(dev), P, int(degree), M, W, H, means3D.data_ptr(), _ptr(sh), _ptr(scales), float(scale_modifier),
@@ -476,16 +513,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
         else:
             # (also when nothing was rendered: the call then only clears the accumulator table)
             touched = new_touched()
-            if dL_ddepth is None:
-                _native.check("gsr_blend_backward", L.gsr_blend_backward(
-                    _stream(dev), P, int(R), W, H, background.data_ptr(), geomBuffer.data_ptr(), _ptr(binningBuffer),
-                    imageBuffer.data_ptr(), dL_dpix.data_ptr(), acc.data_ptr(), touched.data_ptr(),
-                    (bwd_flags & ~options.FLAG_ACC_SELF_CLEAN) | abs_bit))
-            else:
-                _native.check("gsr_blend_backward_depth", L.gsr_blend_backward_depth(
-                    _stream(dev), P, int(R), W, H, background.data_ptr(), geomBuffer.data_ptr(), _ptr(binningBuffer),
-                    imageBuffer.data_ptr(), dL_dpix.data_ptr(), dL_ddepth.data_ptr(), acc.data_ptr(), touched.data_ptr(),
-                    (bwd_flags & ~options.FLAG_ACC_SELF_CLEAN) | abs_bit))
+            blend_half(touched, (bwd_flags & ~options.FLAG_ACC_SELF_CLEAN) | abs_bit)
             take_abs_grad(touched)
             # notification (no allocation): K7 is enqueued, K8+K9 not yet -- multiview.py starts the exchange of the
             # touched-row counts here (from K7's row mask), so that it and the host's wait for it run underneath K8+K9

@@ -62,7 +62,7 @@ def _call_native(fn, args, debug: bool, dump_path: str, message: str):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, aux_colors=None):
+                raster_settings, aux_colors=None, return_alpha=False):
         rs = raster_settings
         # behaviour flags (include/gsr.h: GSR_FLAG_*) are fixed per render: read once here, reused by the backward
         flags = _options.current_flags()
@@ -90,26 +90,30 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.mark_non_differentiable(radii)
         # radii / depth never carry a gradient: do not let autograd fill zero tensors for them on every backward
         ctx.set_materialize_grads(False)
+        # extension: the alpha image 1 - final_T out of the image state K6 just left, a differentiable last output
+        ctx.gsr_alpha = return_alpha
+        alpha = (_C.alpha_image(imgBuffer, rs.image_height, rs.image_width),) if return_alpha else ()
         if aux_colors is None:
-            return color, radii, depth
+            return (color, radii, depth, alpha[0]) if return_alpha else (color, radii, depth)
         # extension: a second, gradient-free image of the same view with other colours (K6 only)
         aux = _call_native(run(_C.rasterize_gaussians_aux),
                            (rs.bg, aux_colors.detach(), num_rendered, geomBuffer, binningBuffer, imgBuffer, rs.image_height,
                             rs.image_width, rs.debug), rs.debug, "snapshot_fw.dump",
                            "\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
         ctx.mark_non_differentiable(radii, aux)
-        return color, radii, depth, aux
+        return (color, radii, depth, aux) + alpha
 
     @staticmethod
-    def backward(ctx, grad_out_color, grad_radii, grad_depth, grad_aux=None):
+    def backward(ctx, grad_out_color, grad_radii, grad_depth, *grad_rest):  # (grad_rest: of aux and / or alpha, in that order)
         # grad_radii is ignored exactly as in the reference (:137, :155-177); so is grad_depth -- depth is a forward-only
         # output -- unless this render ran with FLAG_DEPTH_GRAD (gaussianeditor_amd.set_depth_grad)
         rs = ctx.raster_settings
         (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
          imgBuffer) = ctx.saved_tensors
         depth_grad = _depth_grad(ctx.gsr_flags, grad_depth)
+        alpha_grad = grad_rest[-1] if ctx.gsr_alpha else None
         abs_grad = _abs_grad_out(ctx.gsr_flags, means3D)
-        if grad_out_color is None:  # only the depth output was used downstream
+        if grad_out_color is None:  # only the depth and / or alpha output was used downstream
             grad_out_color = torch.zeros((3, rs.image_height, rs.image_width), dtype=torch.float32, device=means3D.device)
         # argument order of _C.rasterize_gaussians_backward (rasterize_points.h:38-60)
         args = (rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
@@ -119,14 +123,15 @@ class _RasterizeGaussians(torch.autograd.Function):
          grad_rotations) = _call_native(
              lambda *a: _C.rasterize_gaussians_backward(*a, flags=ctx.gsr_flags,
                                                         grad_allocator=getattr(ctx, "gsr_grad_allocator", None),
-                                                        **_depth_kw(depth_grad), **_abs_kw(abs_grad)),
+                                                        **_depth_kw(depth_grad), **_abs_kw(abs_grad),
+                                                        **_alpha_kw(alpha_grad)),
              args, rs.debug, "snapshot_bw.dump",
              "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
         if abs_grad is not None:
             ctx.gsr_means2D.absgrad = abs_grad
         # one slot per forward() input (:213-225)
         return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
-                grad_cov3Ds_precomp, None, None)
+                grad_cov3Ds_precomp, None, None, None)
 
 
 def _depth_grad(flags, grad_depth):
@@ -152,6 +157,11 @@ def _abs_kw(abs_grad):
     return {} if abs_grad is None else {"abs_grad_out": abs_grad}
 
 
+def _alpha_kw(alpha_grad):
+    # (the keyword only where the alpha image was returned AND used: every other backward is today's call, to any `_C` backend)
+    return {} if alpha_grad is None else {"dL_dout_alpha": alpha_grad}
+
+
 class _ReusedRender(torch.autograd.Function):
     """A colour-override render served from the state of the preceding full render of the same view (_reuse.py): the
     blend kernel alone.  Same outputs as `_RasterizeGaussians`; differentiable like it -- a backward through this image
@@ -159,7 +169,7 @@ class _ReusedRender(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings,
-                entry):
+                entry, return_alpha=False):
         rs = raster_settings
         flags = _options.current_flags()
         color = _call_native(lambda *a: _C.rasterize_gaussians_aux(*a, flags=flags),
@@ -174,13 +184,17 @@ class _ReusedRender(torch.autograd.Function):
         ctx.save_for_backward(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
         ctx.mark_non_differentiable(radii)
         ctx.set_materialize_grads(False)
+        ctx.gsr_alpha = bool(return_alpha)
+        if return_alpha:  # the remembered state holds the full render's final_T: no K6 of this render's own wrote it
+            return color, radii, depth, _C.alpha_image(entry.img, rs.image_height, rs.image_width)
         return color, radii, depth
 
     @staticmethod
-    def backward(ctx, grad_out_color, grad_radii, grad_depth):
+    def backward(ctx, grad_out_color, grad_radii, grad_depth, grad_alpha=None):
         rs, flags = ctx.raster_settings, ctx.gsr_flags
         means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp = ctx.saved_tensors
         depth_grad = _depth_grad(flags, grad_depth)
+        alpha_grad = grad_alpha if ctx.gsr_alpha else None
         abs_grad = _abs_grad_out(flags, means3D)
         if grad_out_color is None:
             grad_out_color = torch.zeros((3, rs.image_height, rs.image_width), dtype=torch.float32, device=means3D.device)
@@ -192,31 +206,36 @@ class _ReusedRender(torch.autograd.Function):
          grad_rotations) = _C.rasterize_gaussians_backward(
              rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
              rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, sh, rs.sh_degree, rs.campos, geomBuffer, num_rendered,
-             binningBuffer, imgBuffer, rs.debug, flags=flags, **_depth_kw(depth_grad), **_abs_kw(abs_grad))
+             binningBuffer, imgBuffer, rs.debug, flags=flags, **_depth_kw(depth_grad), **_abs_kw(abs_grad),
+             **_alpha_kw(alpha_grad))
         if abs_grad is not None:
             ctx.gsr_means2D.absgrad = abs_grad
         return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
-                grad_cov3Ds_precomp, None, None)
+                grad_cov3Ds_precomp, None, None, None)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings):
+                        raster_settings, return_alpha=False):
+    # (return_alpha: the alpha image as an additional last value; the extra arguments only then, so that a call without it
+    #  is the call it always was)
+    with_alpha = (True,) if return_alpha else ()
     if colors_precomp.numel() != 0 and sh.numel() == 0 and means3D.is_cuda:
         # a colour-override render: is it the view the rasterizer rendered last (the reference's second render() of every
         # training view / GUI frame)?  Then the blend kernel alone, on that render's state (_reuse.py)
         entry = _reuse.lookup(raster_settings, _options.current_flags(), means3D, scales, rotations, opacities, cov3Ds_precomp)
         if entry is not None:
             return _ReusedRender.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                                       raster_settings, entry)
+                                       raster_settings, entry, *with_alpha)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings)
+                                     cov3Ds_precomp, raster_settings, *((None, True) if return_alpha else ()))
 
 
 def rasterize_gaussians_with_aux(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                                 raster_settings, aux_colors):
-    """rasterize_gaussians plus a second image blended with `aux_colors` (P,3): (color, radii, depth, aux_color)."""
+                                 raster_settings, aux_colors, return_alpha=False):
+    """rasterize_gaussians plus a second image blended with `aux_colors` (P,3): (color, radii, depth, aux_color), with
+    `return_alpha` (color, radii, depth, aux_color, alpha)."""
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, raster_settings, aux_colors)
+                                     cov3Ds_precomp, raster_settings, aux_colors, *((True,) if return_alpha else ()))
 
 
 def _absent(like: torch.Tensor) -> torch.Tensor:
@@ -237,10 +256,13 @@ class GaussianRasterizer(nn.Module):
             return _C.mark_visible(positions, rs.viewmatrix, rs.projmatrix)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, aux_colors=None):
-        """Reference signature (:258-309) plus one extension: with `aux_colors` (P,3) a second image of the same
+                cov3D_precomp=None, aux_colors=None, return_alpha=False):
+        """Reference signature (:258-309) plus two extensions.  With `aux_colors` (P,3) a second image of the same
         view, blended with those colours instead, is returned as a fourth value (forward only, no gradient).  It is
-        what a second call with colors_precomp=aux_colors would render, at the cost of the blend kernel alone."""
+        what a second call with colors_precomp=aux_colors would render, at the cost of the blend kernel alone.
+        With `return_alpha=True` the alpha image (1,H,W) -- accumulated opacity, 1 - the final transmittance -- is an
+        additional LAST value, (color, radii, depth, alpha) or (color, radii, depth, aux, alpha), differentiable like the
+        colour.  The arity depends on these two arguments alone, never on process state."""
         if (shs is None) == (colors_precomp is None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")  # sic, :271-276
         has_sr = scales is not None or rotations is not None
@@ -254,9 +276,9 @@ class GaussianRasterizer(nn.Module):
         cov3D_precomp = _absent(means3D) if cov3D_precomp is None else cov3D_precomp
         if aux_colors is not None:
             return rasterize_gaussians_with_aux(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                                cov3D_precomp, self.raster_settings, aux_colors)
+                                                cov3D_precomp, self.raster_settings, aux_colors, return_alpha)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                   self.raster_settings)
+                                   self.raster_settings, return_alpha)
 
     def apply_weights(self, means3D, means2D, opacities, shs=None, weights=None, scales=None, rotations=None,
                       cov3Ds_precomp=None, cnt=None, image_weights=None):

@@ -13,6 +13,7 @@ import math
 
 import torch
 
+from . import options as _options
 from .diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer
 
 _SH_C0 = 0.28209479177387814
@@ -67,12 +68,16 @@ def camera2rasterizer(viewpoint_camera, bg_color: torch.Tensor, sh_degree: int =
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
-           semantic_color=None):
+           semantic_color=None, return_alpha=None):
     """gaussian_renderer/__init__.py:45-150.  Background tensor must be on the GPU.
 
     Extension: `semantic_color` (P,3) adds out["semantic"], the image the reference obtains from a SECOND
     render(..., override_color=semantic_color) of the same camera (threestudio/systems/GassuianEditor.py:183-191,
-    webui.py:705-713); here it reuses the preprocessing, sort and tile ranges of this call."""
+    webui.py:705-713); here it reuses the preprocessing, sort and tile ranges of this call.
+    Extension: `return_alpha` adds out["alpha"], the (1,H,W) accumulated opacity 1 - final transmittance, with a gradient
+    (None: as FLAG_ALPHA_OUT of the calling thread says, gaussianeditor_amd.set_alpha_output; off by default)."""
+    if return_alpha is None:
+        return_alpha = bool(_options.current_flags() & _options.FLAG_ALPHA_OUT)
     xyz = pc.get_xyz
     # dummy (P,3) tensor whose .grad receives the screen-space mean gradient (:60-69).  The reference builds it as
     # `zeros_like(..., requires_grad=True) + 0` and retains the gradient of that non-leaf: an add kernel per render and a
@@ -112,6 +117,7 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         rotations=None if rotations is None else rotations.float(),
         cov3D_precomp=cov3D_precomp,
         **({} if semantic_color is None else {"aux_colors": semantic_color.float()}),
+        **({"return_alpha": True} if return_alpha else {}),
     )
     rendered_image, radii, depth = outs[:3]
     out = {
@@ -123,6 +129,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     }
     if semantic_color is not None:
         out["semantic"] = outs[3]
+    if return_alpha:
+        out["alpha"] = outs[-1]
     return out
 
 

@@ -64,7 +64,7 @@ extern "C" {
  * stays): GSR_FLAG_DEPTH_GRAD, the GSR_ACC_DEPTH column, gsr_blend_backward_depth and gsr_backward_depth -- every earlier
  * entry point keeps its signature and its behaviour.  Then, likewise additive: GSR_FLAG_ANTIALIAS and
  * gsr_preprocess_backward_rows_flags.  Then, likewise additive: GSR_FLAG_ABS_GRAD, the GSR_ACC_ABS2D columns and
- * gsr_abs_grad_take. */
+ * gsr_abs_grad_take.  Then, likewise additive: gsr_alpha_image and gsr_blend_backward_alpha (no new flag bit). */
 #define GSR_ABI_VERSION 6
 /* The blend backward's accumulator table: GSR_ACC_ROW floats (one 64-byte line) per Gaussian, 64-byte aligned.  Columns:
  *   [GSR_ACC_MEAN2D] .x [+1] .y of dL_dmean2D      (backward.cu:545-546)
@@ -352,6 +352,27 @@ int gsr_backward_depth(void* stream, int P, int D, int M, int64_t R, int W, int 
  * backward without the flag leaves, so K8+K9 -- whichever entry point, GSR_FLAG_ACC_SELF_CLEAN included -- runs unchanged.
  * acc: 64-byte aligned, as for gsr_blend_backward.  P == 0 is an empty call. */
 int gsr_abs_grad_take(void* stream, int P, float* acc, const uint8_t* touched, float* absgrad);
+
+/* Alpha image (accumulated opacity, opt-in; no flag bit: the pointers say what is asked).
+ * gsr_alpha_image: out_alpha (1,H,W) = 1 - final_T of the image state a gsr_blend_forward left (every forward that is not
+ * an auxiliary render writes final_T, GSR_FLAG_FORWARD_ONLY included), i.e. A = 1 - prod_i (1 - alpha_i) over the entries
+ * the pixel blended.  One small kernel on `stream`, after the forward; the state is only read, so an auxiliary render of
+ * the same view, or a later caller that kept the state, gets the same image.  image: as gsr_blend_forward received it.
+ * gsr_blend_backward_alpha: gsr_blend_backward with two more inputs behind dL_dpix,
+ *   dL_ddepth (1,H,W) | NULL: as gsr_blend_backward_depth (given, GSR_ACC_DEPTH is written and the work list has no list
+ *                     segments; NULL, the call keeps them -- the alpha image needs nothing the checkpoints do not hold);
+ *   dL_dalpha (1,H,W), required: the gradient of out_alpha.  dA/dalpha_i = final_T / (1 - alpha_i) for every blended entry,
+ *                     so it enters K7 as bg . dL_dpix - dL_dalpha in the place of the background term and reaches every
+ *                     gradient through dL/dalpha_i (the GSR_FLAG_ABS_GRAD sums included); no new accumulator column, and
+ *                     the K8+K9 entry point of the view runs as it would without it (with GSR_FLAG_DEPTH_GRAD iff
+ *                     dL_ddepth was given).
+ * flags: as gsr_blend_backward_depth (GSR_FLAG_ABS_GRAD included); GSR_FLAG_DEPTH_GRAD only with a non-NULL dL_ddepth.
+ * P == 0 / R == 0: as gsr_blend_backward (nothing is launched but the clears it documents).  There is no fused
+ * gsr_backward_alpha: call the halves. */
+int gsr_alpha_image(void* stream, int W, int H, const void* image, float* out_alpha);
+int gsr_blend_backward_alpha(void* stream, int P, int64_t R, int W, int H, const float* bg, const void* geom,
+                             const void* binning, const void* image, const float* dL_dpix, const float* dL_ddepth,
+                             const float* dL_dalpha, float* acc, uint8_t* touched, unsigned flags);
 
 /* Multi-GPU exchange support (gaussianeditor_amd/multiview.py).  Per view the SH gradient is
  * rank one, dL_dsh[k] = c_k(dir) * dL_dRGB with dir = normalize(mean - campos) (backward.cu:44-98), so ranks exchange
