@@ -115,6 +115,12 @@ SIGNATURES = {
     "gsr_debug_blend_forward_profile": (c_int, [_P, c_int, c_int64, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_int64,
                                                 POINTER(c_int64)]),
     "gsr_debug_export_image": (c_int, [_P, c_int, c_int, _P, _P, _P, _P]),
+    # the fused L1 + SSIM loss (gaussianeditor_amd/losses.py): (planes, H, W, bytes);
+    # (stream, planes, H, W, img, gt, w_l1, w_ssim, c, maps | NULL, workspace, out3);
+    # (stream, planes, H, W, img, gt, maps, w_l1, w_ssim, dL_dloss, dL_dimg)
+    "gsr_loss_workspace_size": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
+    "gsr_photometric_loss_forward": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_float, c_float, c_float, _P, _P, _P]),
+    "gsr_photometric_loss_backward": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_float, c_float, _P, _P]),
 }
 
 _lib = None

@@ -64,7 +64,9 @@ extern "C" {
  * stays): GSR_FLAG_DEPTH_GRAD, the GSR_ACC_DEPTH column, gsr_blend_backward_depth and gsr_backward_depth -- every earlier
  * entry point keeps its signature and its behaviour.  Then, likewise additive: GSR_FLAG_ANTIALIAS and
  * gsr_preprocess_backward_rows_flags.  Then, likewise additive: GSR_FLAG_ABS_GRAD, the GSR_ACC_ABS2D columns and
- * gsr_abs_grad_take.  Then, likewise additive: gsr_alpha_image and gsr_blend_backward_alpha (no new flag bit). */
+ * gsr_abs_grad_take.  Then, likewise additive: gsr_alpha_image and gsr_blend_backward_alpha (no new flag bit).  Then,
+ * likewise additive: gsr_loss_workspace_size, gsr_photometric_loss_forward and gsr_photometric_loss_backward (the fused
+ * L1 + SSIM loss; nothing of the rasterizer changed). */
 #define GSR_ABI_VERSION 6
 /* The blend backward's accumulator table: GSR_ACC_ROW floats (one 64-byte line) per Gaussian, 64-byte aligned.  Columns:
  *   [GSR_ACC_MEAN2D] .x [+1] .y of dL_dmean2D      (backward.cu:545-546)
@@ -587,6 +589,33 @@ typedef struct gsr_append_tensor {
   int64_t row_bytes;
 } gsr_append_tensor;
 int gsr_append_rows(void* stream, int64_t P, int64_t n, int num_tensors, const gsr_append_tensor* tensors);
+
+/* ---- the training loss: fused L1 + SSIM of two images, and its gradient ----
+ * Replaces l1_loss / ssim of gaussiansplatting/utils/loss_utils.py:17-63 and the loss line of the reference's trainers,
+ * (1 - lambda) * l1_loss + lambda * (1 - ssim) (gaussiansplatting/train.py:89, train_from_mesh.py:136): five grouped
+ * 11 x 11 conv2d calls, some fifteen elementwise kernels, and autograd's backward through all of them.
+ *   loss = w_l1 * L1 + w_ssim * SSIM + c,   L1 = mean |img - gt|,   SSIM = mean of the SSIM map
+ * over `planes` (= batch x channels) planes of H x W pixels, N = planes * H * W values in all; the SSIM window is the
+ * reference's: 11 taps, sigma 1.5, normalised, zero padding of 5.  (1 - lambda, -lambda, lambda) gives the trainers' loss,
+ * (0, 1, 0) ssim(), (1, 0, 0) l1_loss().  With w_ssim == 0 the SSIM is NOT evaluated: no convolution work, `maps` is neither
+ * written nor read, out3[2] is NaN.
+ *   img, gt (planes,H,W) f32 in; workspace: gsr_loss_workspace_size bytes of device scratch, 8-byte aligned (two partial
+ *       sums per 16 x 64 tile, added in a fixed order: no float atomics, the same bits on every run);
+ *   out3: three device floats, (loss, L1, SSIM);
+ *   maps (3,planes,H,W) f32: three per-pixel derivative maps the forward writes for the backward, NULL when no backward
+ *       follows (the metric path: 12 N bytes less traffic).  The backward requires them (NULL: GSR_ERR_BAD_ARGUMENT; with
+ *       w_ssim == 0 any non-NULL pointer, e.g. img, serves);
+ *   dL_dloss: ONE device float, the upstream gradient, read by the kernel (the host neither waits nor reads anything back);
+ *   dL_dimg (planes,H,W) f32 out, fully written: dL_dloss * d loss / d img, with sign(0) = 0 in the L1 term.  gt gets no
+ *       gradient.
+ * img / gt / w_l1 / w_ssim of the backward are those of the forward that wrote `maps`.  At most 2^24 - 1 tiles of 16 x 64
+ * pixels (more: GSR_ERR_BAD_ARGUMENT).  A failed launch is reported as GSR_ERR_HIP, but gsr_last_hip_error() is NOT updated
+ * by these three entry points (it may hold an earlier call's code): rely on the return value alone. */
+int gsr_loss_workspace_size(int planes, int H, int W, size_t* bytes);
+int gsr_photometric_loss_forward(void* stream, int planes, int H, int W, const float* img, const float* gt, float w_l1,
+                                 float w_ssim, float c, float* maps, void* workspace, float* out3);
+int gsr_photometric_loss_backward(void* stream, int planes, int H, int W, const float* img, const float* gt,
+                                  const float* maps, float w_l1, float w_ssim, const float* dL_dloss, float* dL_dimg);
 
 /* ---- introspection used by the parity tests (not needed by the drop-in) ----
  * Copy internal per-Gaussian / per-instance / per-pixel state out of the opaque

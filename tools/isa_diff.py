@@ -20,11 +20,12 @@ CSRC = "gaussianeditor_amd/csrc"
 
 def unit_commands(tree):
     """{unit: argv} from the Makefile's own compile lines, '-c X.hip -o X.o' taken off."""
-    objs = sorted(f[:-4] + ".o" for f in os.listdir(os.path.join(tree, CSRC)) if f.endswith(".hip"))
-    out = subprocess.run(["make", "-n", "-B", "-C", os.path.join(tree, CSRC)] + objs, check=True, capture_output=True, text=True).stdout
+    base = os.path.join(tree, CSRC)  # (units in subdirectories too, named by their path: loss/gsr_loss)
+    objs = sorted(os.path.relpath(os.path.join(d, f), base)[:-4] + ".o" for d, _, fs in os.walk(base) for f in fs if f.endswith(".hip"))
+    out = subprocess.run(["make", "-n", "-B", "-C", base] + objs, check=True, capture_output=True, text=True).stdout
     cmds = {}
     for line in out.splitlines():
-        m = re.search(r"^(.*\S)\s+-c (\w+)\.hip -o \2\.o\s*$", line)
+        m = re.search(r"^(.*\S)\s+-c ([\w/]+)\.hip -o \2\.o\s*$", line)
         if m:
             cmds[m.group(2)] = shlex.split(m.group(1))
     return cmds
@@ -50,7 +51,7 @@ def functions(asm, renames):
 
 
 def compile_unit(tree, unit, argv, renames, workdir):
-    asm = os.path.join(workdir, unit + ".s")
+    asm = os.path.join(workdir, unit.replace("/", "_") + ".s")
     subprocess.run(argv + ["-w", "--cuda-device-only", "-S", unit + ".hip", "-o", asm], check=True, cwd=os.path.join(tree, CSRC))
     with open(asm) as f:
         return functions(f.read(), renames)
