@@ -42,6 +42,11 @@ class CompactTensor(ctypes.Structure):
     _fields_ = [("src", _P), ("dst", _P), ("row_bytes", c_int64)]
 
 
+class DensifyResult(ctypes.Structure):
+    """gsr_densify_result (include/gsr.h)."""
+    _fields_ = [("nonzero", c_int64), ("n_clone", c_int64), ("n_split", c_int64), ("threshold", c_float)]
+
+
 #: every symbol include/gsr.h declares, with (restype, argtypes)
 SIGNATURES = {
     "gsr_abi_version": (c_int, []),
@@ -101,6 +106,18 @@ SIGNATURES = {
     "gsr_compact_plan": (c_int, [_P, c_int64, _P, _P, POINTER(c_int64)]),
     "gsr_compact_apply": (c_int, [_P, c_int64, _P, _P, c_int, POINTER(CompactTensor)]),
     "gsr_append_rows": (c_int, [_P, c_int64, c_int64, c_int, POINTER(AppendTensor)]),
+    # the densification policy (gaussianeditor_amd/densify.py): (stream, P, V, grads[V], radii[V], accum, denom, max_radii2D);
+    # (stream, P, accum, denom, mask, scaling, max_grad, max_densify_percent, percent_dense, extent, workspace, clone_sel,
+    #  split_sel, result); (workspace, P, &clone_plan, &split_plan);
+    # (stream, P, xyz, scaling, rotation, split_sel, split_plan, n_split, N, noise, new_xyz);
+    # (stream, P, opacity, scaling, max_radii2D | NULL, mask, drop | NULL, min_opacity, max_screen_size, extent, keep)
+    "gsr_densify_stats": (c_int, [_P, c_int64, c_int, POINTER(_P), POINTER(_P), _P, _P, _P]),
+    "gsr_densify_workspace_size": (c_int, [c_int64, POINTER(c_size_t)]),
+    "gsr_densify_select": (c_int, [_P, c_int64, _P, _P, _P, _P, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                   ctypes.c_double, _P, _P, _P, POINTER(DensifyResult)]),
+    "gsr_densify_plans": (c_int, [_P, c_int64, POINTER(_P), POINTER(_P)]),
+    "gsr_densify_split_xyz": (c_int, [_P, c_int64, _P, _P, _P, _P, _P, c_int64, c_int, _P, _P]),
+    "gsr_densify_keep": (c_int, [_P, c_int64, _P, _P, _P, _P, _P, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P]),
     "gsr_adam_step": (c_int, [_P, c_int, POINTER(AdamTensor), c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P,
                             _P]),
     "gsr_adam_step_rows": (c_int, [_P, c_int, POINTER(AdamTensor), c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P,

@@ -1108,6 +1108,70 @@ int gsr_append_rows(void* stream, int64_t P, int64_t n, int num_tensors, const g
   return GSR_OK;
 }
 
+int gsr_densify_stats(void* stream, int64_t P, int num_views, const float* const* grads, const int32_t* const* radii,
+                      float* xyz_gradient_accum, float* denom, float* max_radii2D) {
+  if (P < 0 || P > 0x7fffffffll || num_views < 1 || num_views > 8) return GSR_ERR_BAD_ARGUMENT;
+  if (P == 0) return GSR_OK;
+  if (!grads || !radii || !xyz_gradient_accum || !denom || !max_radii2D) return GSR_ERR_BAD_ARGUMENT;
+  for (int v = 0; v < num_views; ++v)
+    if (!grads[v] || !radii[v]) return GSR_ERR_BAD_ARGUMENT;
+  GSR_HIP(launch_densify_stats((hipStream_t)stream, P, num_views, grads, radii, xyz_gradient_accum, denom, max_radii2D));
+  return GSR_OK;
+}
+
+int gsr_densify_workspace_size(int64_t P, size_t* bytes) {
+  if (P < 0 || P > (1ll << 24) || !bytes) return GSR_ERR_BAD_ARGUMENT;
+  *bytes = densify_workspace_bytes(P);
+  return GSR_OK;
+}
+
+int gsr_densify_plans(void* workspace, int64_t P, void** clone_plan, void** split_plan) {
+  if (P < 0 || P > (1ll << 24) || !workspace || !clone_plan || !split_plan) return GSR_ERR_BAD_ARGUMENT;
+  densify_plans(workspace, P, clone_plan, split_plan);
+  return GSR_OK;
+}
+
+int gsr_densify_select(void* stream, int64_t P, const float* accum, const float* denom, const uint8_t* mask,
+                       const float* scaling, double max_grad, double max_densify_percent, double percent_dense, double extent,
+                       void* workspace, uint8_t* clone_sel, uint8_t* split_sel, gsr_densify_result* result_host) {
+  if (!result_host) return GSR_ERR_BAD_ARGUMENT;
+  memset(result_host, 0, sizeof(*result_host));
+  // max_grad <= 0 would select unmasked rows (g = 0 >= 0), which the reference asserts against (:756-758); NaN likewise refused
+  if (P < 0 || P > (1ll << 24) || !(max_grad > 0.0) || !(max_densify_percent >= 0.0)) return GSR_ERR_BAD_ARGUMENT;
+  if (P == 0) return GSR_OK;
+  if (!accum || !denom || !mask || !scaling || !workspace || !clone_sel || !split_sel || ((uintptr_t)workspace & 7u) != 0)
+    return GSR_ERR_BAD_ARGUMENT;
+  hipStream_t s = (hipStream_t)stream;
+  // a float32 tensor compared with a Python number: the number is rounded to binary32 first
+  GSR_HIP(launch_densify_select(s, P, accum, denom, mask, scaling, (float)max_grad, max_densify_percent,
+                                (float)(percent_dense * extent), workspace, clone_sel, split_sel));
+  GSR_HIP(hipMemcpyAsync(result_host, densify_result_ptr(workspace, P), sizeof(*result_host), hipMemcpyDeviceToHost, s));
+  GSR_HIP(hipStreamSynchronize(s));
+  return GSR_OK;
+}
+
+int gsr_densify_split_xyz(void* stream, int64_t P, const float* xyz, const float* scaling, const float* rotation,
+                          const uint8_t* split_sel, const void* split_plan, int64_t n_split, int N, const float* noise,
+                          float* new_xyz) {
+  if (P < 0 || P >= (1ll << 32) - 1024 || n_split < 0 || n_split > P || N < 1 || N > 8) return GSR_ERR_BAD_ARGUMENT;
+  if (P == 0 || n_split == 0) return GSR_OK;
+  if (!xyz || !scaling || !rotation || !split_sel || !split_plan || !noise || !new_xyz) return GSR_ERR_BAD_ARGUMENT;
+  GSR_HIP(launch_densify_split_xyz((hipStream_t)stream, P, xyz, scaling, rotation, split_sel, const_cast<void*>(split_plan),
+                                   n_split, N, noise, new_xyz));
+  return GSR_OK;
+}
+
+int gsr_densify_keep(void* stream, int64_t P, const float* opacity, const float* scaling, const float* max_radii2D,
+                     const uint8_t* mask, const uint8_t* drop, double min_opacity, double max_screen_size, double extent,
+                     uint8_t* keep) {
+  if (P < 0 || P > 0x7fffffffll) return GSR_ERR_BAD_ARGUMENT;
+  if (P == 0) return GSR_OK;
+  if (!opacity || !scaling || !mask || !keep) return GSR_ERR_BAD_ARGUMENT;
+  GSR_HIP(launch_densify_keep((hipStream_t)stream, P, opacity, scaling, max_radii2D, mask, drop, (float)min_opacity,
+                              (float)max_screen_size, (float)(0.1 * extent), keep));
+  return GSR_OK;
+}
+
 int gsr_debug_cov3d(void* stream, int P, const float* scales, float scale_modifier, const float* rotations, float* cov3D) {
   if (P <= 0) return GSR_OK;
   if (!scales || !rotations || !cov3D) return GSR_ERR_BAD_ARGUMENT;

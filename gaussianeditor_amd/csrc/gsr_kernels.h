@@ -171,6 +171,21 @@ const uint64_t* compact_total_ptr(void* workspace, int64_t P);
 hipError_t launch_compact_apply(hipStream_t s, int64_t P, const uint8_t* keep, void* workspace, int nt,
                                 const gsr_compact_tensor* tensors, int64_t limit = -1);
 hipError_t launch_append_rows(hipStream_t s, int64_t P, int64_t n, int nt, const gsr_append_tensor* tensors);
+// the densification policy (gsr_densify.hip)
+hipError_t launch_densify_stats(hipStream_t s, int64_t P, int V, const float* const* grads, const int32_t* const* radii,
+                                float* accum, float* denom, float* max_radii);
+size_t densify_workspace_bytes(int64_t P);
+void densify_plans(void* workspace, int64_t P, void** clone_plan, void** split_plan);
+hipError_t launch_densify_select(hipStream_t s, int64_t P, const float* accum, const float* denom, const uint8_t* mask,
+                                 const float* scaling, float max_grad, double max_densify_percent, float t_dense,
+                                 void* workspace, uint8_t* clone_sel, uint8_t* split_sel);
+const gsr_densify_result* densify_result_ptr(void* workspace, int64_t P);
+hipError_t launch_densify_split_xyz(hipStream_t s, int64_t P, const float* xyz, const float* scaling, const float* rotation,
+                                    const uint8_t* split_sel, void* split_plan, int64_t n_split, int N, const float* noise,
+                                    float* new_xyz);
+hipError_t launch_densify_keep(hipStream_t s, int64_t P, const float* opacity, const float* scaling, const float* max_radii,
+                               const uint8_t* mask, const uint8_t* drop, float min_opacity, float max_screen, float big_ws,
+                               uint8_t* keep);
 hipError_t launch_adam_step(hipStream_t s, int nt, const gsr_adam_tensor* tensors, long long step, double beta1,
                             double beta2, double eps, const uint8_t* row_mask, const float* row_weight,
                             const uint8_t* grad_valid = nullptr);

@@ -66,7 +66,9 @@ extern "C" {
  * gsr_preprocess_backward_rows_flags.  Then, likewise additive: GSR_FLAG_ABS_GRAD, the GSR_ACC_ABS2D columns and
  * gsr_abs_grad_take.  Then, likewise additive: gsr_alpha_image and gsr_blend_backward_alpha (no new flag bit).  Then,
  * likewise additive: gsr_loss_workspace_size, gsr_photometric_loss_forward and gsr_photometric_loss_backward (the fused
- * L1 + SSIM loss; nothing of the rasterizer changed). */
+ * L1 + SSIM loss; nothing of the rasterizer changed).  Then, likewise additive: gsr_densify_stats,
+ * gsr_densify_workspace_size, gsr_densify_select, gsr_densify_plans, gsr_densify_split_xyz and gsr_densify_keep (the
+ * densification policy; nothing existing changed). */
 #define GSR_ABI_VERSION 6
 /* The blend backward's accumulator table: GSR_ACC_ROW floats (one 64-byte line) per Gaussian, 64-byte aligned.  Columns:
  *   [GSR_ACC_MEAN2D] .x [+1] .y of dL_dmean2D      (backward.cu:545-546)
@@ -589,6 +591,74 @@ typedef struct gsr_append_tensor {
   int64_t row_bytes;
 } gsr_append_tensor;
 int gsr_append_rows(void* stream, int64_t P, int64_t n, int num_tensors, const gsr_append_tensor* tensors);
+
+/* ---- the densification POLICY: statistics, selection, split positions, prune mask ----
+ * The tensor surgery above moves rows; these entry points decide WHICH rows, as the reference's torch lines do, bit for bit
+ * where stated: all float arithmetic is single binary32 operations in the order written here, no float atomics (the same
+ * bits on every run), no device allocation, P == 0 is an empty call, arguments are checked before the device is touched.
+ *
+ * gsr_densify_stats: the per-step statistics of on_before_optimizer_step (threestudio/systems/GassuianEditor.py:251-281)
+ * with add_densification_stats (gaussiansplatting/scene/gaussian_model.py:811-815) in ONE launch, no readback, never
+ * blocking.  grads / radii: HOST arrays of num_views (1..8) device pointers, the views' screen-space gradients (P,3) f32
+ * (viewspace_points.grad or .absgrad) and radii (P) i32.  Per row: r = max over the views of radii; r <= 0: the row is not
+ * in update_filter, nothing of it is read or written (a NaN in its gradient never enters); otherwise
+ * gx = ((0 + g[0].x) + g[1].x) + ..., gy likewise (:254-261), xyz_gradient_accum += sqrtf(gx*gx + gy*gy), denom += 1,
+ * max_radii2D = fmaxf(max_radii2D, (float)r) (:271-273).  All three (P) f32, updated in place.  P <= 2^31 - 1. */
+int gsr_densify_stats(void* stream, int64_t P, int num_views, const float* const* grads, const int32_t* const* radii,
+                      float* xyz_gradient_accum, float* denom, float* max_radii2D);
+
+/* gsr_densify_select: the decision of densify_and_prune (:771-777), densify_and_clone (:732-739) and densify_and_split
+ * (:676-683) on the P original rows; P <= 2^24 (torch.quantile's own limit; the rank is computed in binary32).
+ *   g = accum / denom, NaN -> 0, mask == 0 -> 0                                                     (:771-773)
+ *   max_densify_percent < 1: nnz = #{g != 0}; q = 1 - (double)nnz * max_densify_percent / (double)P, rounded to binary32;
+ *     rank = q * (float)(P-1), lo = floor(rank), w = rank - lo; a, b = the lo-th and min(lo+1, P-1)-th smallest g;
+ *     threshold = fmaf(w, b - a, a) for w < 0.5, else fmaf(w - 1, b - a, b) (torch.quantile, 'linear'); g < threshold -> 0
+ *     (:774-777).  a and b come from a radix select over the order-preserving integer image of g: four histogram passes,
+ *     state on the device, no sort.  Otherwise no threshold is applied and 0 is reported.
+ *   t_dense = (float)(percent_dense * extent);  hot = g >= (float)max_grad   (a float32 tensor against a Python number)
+ *   clone_sel = hot && max(scaling) <= t_dense;  split_sel = hot && max(scaling) > t_dense       (P) u8 each, 0 / 1
+ * The rows the clone step appends carry a padded gradient of 0 (:676-677) and are never split, so both masks are decided
+ * here.  scaling (P,3) f32 is the ACTIVATED scaling (get_scaling); mask (P) u8.  max_grad <= 0 is refused (it would select
+ * unmasked rows, which the reference asserts against, :756-758), as is max_densify_percent < 0.
+ * workspace: gsr_densify_workspace_size(P) bytes of device scratch, 8-byte aligned.  *result_host is read back once, the
+ * only host synchronisation of the call (as gsr_compact_plan's count).  Afterwards the workspace holds a gsr_compact_plan
+ * of clone_sel and one of split_sel: gsr_densify_plans (host only, no device access) returns their addresses, usable as
+ * gsr_compact_apply's `workspace` with the respective mask and as gsr_densify_split_xyz's `split_plan`. */
+typedef struct gsr_densify_result {
+  int64_t nonzero;   /* #{g != 0} before the threshold */
+  int64_t n_clone;
+  int64_t n_split;
+  float threshold;   /* 0 when max_densify_percent >= 1 */
+} gsr_densify_result;
+int gsr_densify_workspace_size(int64_t P, size_t* bytes);
+int gsr_densify_select(void* stream, int64_t P, const float* accum, const float* denom, const uint8_t* mask,
+                       const float* scaling, double max_grad, double max_densify_percent, double percent_dense, double extent,
+                       void* workspace, uint8_t* clone_sel, uint8_t* split_sel, gsr_densify_result* result_host);
+int gsr_densify_plans(void* workspace, int64_t P, void** clone_plan, void** split_plan);
+
+/* gsr_densify_split_xyz: the positions of densify_and_split's children (:685-691).  xyz (P,3), activated scaling (P,3),
+ * raw rotation (P,4) (_rotation, not normalised), split_sel (P) u8 with its plan (gsr_densify_plans, or a gsr_compact_plan
+ * of split_sel), n_split = its number of set rows, N copies (1..8; the reference: 2), noise (N*n_split,3) f32 standard
+ * normal numbers drawn by the caller.  The child of the r-th selected parent (ascending row), copy c, is row c*n_split + r
+ * of new_xyz (N*n_split,3) -- .repeat(N,1) order:
+ *   sample = noise * scaling;  n = sqrtf(((r0*r0 + r1*r1) + r2*r2) + r3*r3), q = rot / n;  R = build_rotation(q) exactly as
+ *   gaussiansplatting/utils/general_utils.py:78-99 writes its nine entries;
+ *   new_xyz_i = ((R_i0*sample_0 + R_i1*sample_1) + R_i2*sample_2) + xyz_i.
+ * The children's scaling stays with the caller (a division by a Python scalar and a log that must be torch's own).
+ * P < 2^32 - 1024 (gsr_compact_plan's limit) and 0 <= n_split <= P; n_split == 0 is an empty call. */
+int gsr_densify_split_xyz(void* stream, int64_t P, const float* xyz, const float* scaling, const float* rotation,
+                          const uint8_t* split_sel, const void* split_plan, int64_t n_split, int N, const float* noise,
+                          float* new_xyz);
+
+/* gsr_densify_keep: the prune mask of densify_and_prune (:787-794) joined with the removal of the split parents
+ * (:720-727), as a KEEP mask over the P rows after the append:
+ *   keep = !(drop && drop[i]) && !((opacity < (float)min_opacity || (max_radii2D && max_radii2D[i] > (float)max_screen_size)
+ *                                   || max(scaling) > (float)(0.1 * extent)) && mask)
+ * opacity (P) and scaling (P,3) f32 ACTIVATED, mask (P) u8, drop (P) u8 or NULL, max_radii2D (P) f32 or NULL, keep (P) u8.
+ * P <= 2^31 - 1. */
+int gsr_densify_keep(void* stream, int64_t P, const float* opacity, const float* scaling, const float* max_radii2D,
+                     const uint8_t* mask, const uint8_t* drop, double min_opacity, double max_screen_size, double extent,
+                     uint8_t* keep);
 
 /* ---- the training loss: fused L1 + SSIM of two images, and its gradient ----
  * Replaces l1_loss / ssim of gaussiansplatting/utils/loss_utils.py:17-63 and the loss line of the reference's trainers,
