@@ -132,6 +132,10 @@ SIGNATURES = {
     "gsr_debug_blend_forward_profile": (c_int, [_P, c_int, c_int64, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_int64,
                                                 POINTER(c_int64)]),
     "gsr_debug_export_image": (c_int, [_P, c_int, c_int, _P, _P, _P, _P]),
+    # which K7 ran, on what work (host-side bookkeeping): (counts[32]), index FAST | SEG << 1 | DEPTH << 2 | ABS << 3 |
+    # ALPHA << 4; (stream, W, H, image, counts[2] = {items, list-segment items} of the latest backward's work list)
+    "gsr_debug_blend_backward_launches": (c_int, [POINTER(ctypes.c_uint64)]),
+    "gsr_debug_blend_backward_items": (c_int, [_P, c_int, c_int, _P, POINTER(c_int64)]),
     # the fused L1 + SSIM loss (gaussianeditor_amd/losses.py): (planes, H, W, bytes);
     # (stream, planes, H, W, img, gt, w_l1, w_ssim, c, maps | NULL, workspace, out3);
     # (stream, planes, H, W, img, gt, maps, w_l1, w_ssim, dL_dloss, dL_dimg)

@@ -25,6 +25,7 @@
 //     and ONE global atomic per (tile, instance, term) leaves the CU -- the reference issues one per pixel.
 #include <limits.h>
 
+#include <atomic>
 #include <type_traits>
 
 #include "gsr_kernels.h"
@@ -732,6 +733,7 @@ constexpr uint32_t BWD_ITEM_PART = 0x40000000u;   // ... quadrants {2,3} instead
 // their final state (backward_tile).  The work list makes one item per stride (lo == hi): runs of several strides, merged
 // to about equal measured work, were measured in round 6 and bought nothing (profiles/r06_m_fine_checkpoints.md).
 constexpr uint32_t BWD_ITEM_SEG = 0x10000000u;
+static_assert(BWD_ITEM_SEG == BWD_ITEM_SEG_BIT, "gsr_kernels.h states the bit gsr_debug_blend_backward_items counts");
 constexpr int BWD_SEG_SHIFT = 20, BWD_NSEG_SHIFT = 24;  // 4 bits each: first stride of the run, last stride of the run
 static_assert(CK_MAX <= 16, "a stride index must fit the item code's 4 bits");
 constexpr uint32_t BWD_ITEM_TILE = 0x000fffffu;   // (images of up to 2^20 tiles: GSR_MAX_TILES, checked by gsr_blend_backward)
@@ -1608,13 +1610,19 @@ hipError_t launch_blend_forward(hipStream_t s, BlendArgs a) {
 #undef GSR_FWD_LAUNCH
   return hipGetLastError();
 }
+// Host-side launch counts of K7 per instantiation (gsr_debug_blend_backward_launches), index FAST | SEG << 1 | DEPTH << 2 |
+// ABS << 3 | ALPHA << 4; relaxed: renders run from several host threads and nothing is ordered by the counts.
+static std::atomic<uint64_t> g_bwd_launches[32];
+void blend_backward_launch_counts(uint64_t counts[32]) {
+  for (int i = 0; i < 32; ++i) counts[i] = g_bwd_launches[i].load(std::memory_order_relaxed);
+}
 hipError_t launch_blend_backward(hipStream_t s, BlendArgs a) {
   // #CUs x 4 workgroups of 4 waves: the same 4 waves per SIMD as the forward
   const unsigned grid = blend_grid_size(s, a.shared_simds != 0) / BWD_WAVES;
   hipError_t e = prepare_queue(s, a, grid);
   if (e != hipSuccess) return e;
   a.units = (int)blend_units(BWD_WAVES, grid, s);
-  bool seg_items = false;  // the work list holds list-segment items (views whose forward left checkpoints)
+  bool seg_items = false;  // the work list may hold list-segment items (views whose forward left checkpoints; set below)
   ClearArgs clear = {{nullptr, nullptr, nullptr, nullptr}, {0, 0, 0, 0}};
   if (a.clear_grads) {
     const long long P = a.P;
@@ -1646,6 +1654,10 @@ hipError_t launch_blend_backward(hipStream_t s, BlendArgs a) {
                          (const uint32_t*)nullptr, (const uint32_t*)nullptr, CkTable{}, 0u, 0);
   }
   const dim3 g(grid), b(WAVE * BWD_WAVES);
+  // (the same conditions as the dispatch below, in its order: DEPTH excludes SEG)
+  const bool depth = a.dL_ddepth != nullptr;
+  g_bwd_launches[(a.fast_exp ? 1 : 0) | (!depth && seg_items ? 2 : 0) | (depth ? 4 : 0) | (a.abs_grad ? 8 : 0) |
+                 (a.dL_dalpha != nullptr ? 16 : 0)].fetch_add(1, std::memory_order_relaxed);
 #define GSR_BWD_LAUNCH2(SEGV, DEPTHV, ABSV, ALPHAV)                                                                   \
   do {                                                                                                                \
     if (a.fast_exp) hipLaunchKernelGGL((blend_backward_kernel<true, SEGV, DEPTHV, ABSV, ALPHAV>), g, b, 0, s, a);      \

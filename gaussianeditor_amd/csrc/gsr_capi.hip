@@ -7,6 +7,7 @@
 
 #include <chrono>
 #include <mutex>
+#include <vector>
 
 
 #include "gsr_kernels.h"
@@ -1210,6 +1211,34 @@ int gsr_debug_export_image(void* stream, int W, int H, const void* image, uint32
   if (ranges) GSR_HIP(hipMemcpyAsync(ranges, im.ranges, sizeof(uint2) * T, hipMemcpyDeviceToDevice, s));
   if (final_T) GSR_HIP(hipMemcpyAsync(final_T, im.final_T, sizeof(float) * N, hipMemcpyDeviceToDevice, s));
   if (n_contrib) GSR_HIP(hipMemcpyAsync(n_contrib, im.n_contrib, sizeof(uint32_t) * N, hipMemcpyDeviceToDevice, s));
+  return GSR_OK;
+}
+
+int gsr_debug_blend_backward_launches(uint64_t* counts) {
+  if (!counts) return GSR_ERR_BAD_ARGUMENT;
+  blend_backward_launch_counts(counts);
+  return GSR_OK;
+}
+
+int gsr_debug_blend_backward_items(void* stream, int W, int H, const void* image, int64_t* counts) {
+  if (!image || !counts || W <= 0 || H <= 0) return GSR_ERR_BAD_ARGUMENT;
+  const size_t T = (size_t)((W + TILE - 1) / TILE) * ((H + TILE - 1) / TILE);
+  if (T > (size_t)GSR_MAX_TILES) return GSR_ERR_BAD_ARGUMENT;
+  const Image im = carve_image(const_cast<void*>(image), W, H);
+  hipStream_t s = (hipStream_t)stream;
+  uint32_t n = 0;
+  GSR_HIP(hipMemcpyAsync(&n, im.bwd_meta, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  GSR_HIP(hipStreamSynchronize(s));
+  if ((size_t)n > 2 * T + CK_MAX * ck_tiles(T)) return GSR_ERR_BAD_ARGUMENT;  // (not the state of a blend backward)
+  std::vector<uint32_t> items(n);
+  if (n != 0) {
+    GSR_HIP(hipMemcpyAsync(items.data(), im.bwd_order, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
+    GSR_HIP(hipStreamSynchronize(s));
+  }
+  int64_t seg = 0;
+  for (uint32_t code : items) seg += (code & BWD_ITEM_SEG_BIT) != 0u;
+  counts[0] = (int64_t)n;
+  counts[1] = seg;
   return GSR_OK;
 }
 

@@ -192,6 +192,9 @@ hipError_t launch_adam_step(hipStream_t s, int nt, const gsr_adam_tensor* tensor
 hipError_t launch_blend_forward(hipStream_t s, BlendArgs a);
 unsigned blend_grid_size(hipStream_t s, bool shared_simds = false);  // persistent waves of a blend launch on the device of stream s
 hipError_t launch_blend_backward(hipStream_t s, BlendArgs a);
+// debug (host only): launches of K7 per instantiation in this process, index FAST | SEG << 1 | DEPTH << 2 | ABS << 3 | ALPHA << 4
+void blend_backward_launch_counts(uint64_t counts[32]);
+constexpr uint32_t BWD_ITEM_SEG_BIT = 0x10000000u;  // item code of Image::bwd_order: a list segment (gsr_blend.hip: BWD_ITEM_SEG)
 // GSR_FLAG_ABS_GRAD: columns ACC_ABS2D, + 1 of the accumulator rows -> absgrad (P,3), and back to zero (gsr_blend.hip)
 hipError_t launch_abs_grad_take(hipStream_t s, int P, float* acc, const uint8_t* touched, float* absgrad);
 // the alpha image (accumulated opacity) 1 - final_T of the image state a forward left (gsr_blend.hip)

@@ -718,6 +718,20 @@ int gsr_debug_blend_forward_profile(void* stream, int P, int64_t R, int W, int H
                                     const void* binning, void* image, float* out_color, float* out_depth,
                                     uint64_t* records, int64_t max_records, int64_t* n_records_host);
 
+/* Which kernel did a backward run, and on what work?  Host-side bookkeeping for the tests: nothing is launched.
+ * gsr_debug_blend_backward_launches: counts[32] (HOST) receives how often this process has launched K7 so far, per
+ * instantiation, at index FAST | SEG << 1 | DEPTH << 2 | ABS << 3 | ALPHA << 4 -- FAST: GSR_FLAG_FAST_EXP; SEG: the work
+ * list MAY hold list-segment items (the view's forward left checkpoints, GSR_BWD_SEG > 0 and there is no depth gradient;
+ * whether a tile is then cut depends on its work: gsr_debug_blend_backward_items says); DEPTH: gsr_blend_backward_depth / _alpha with
+ * dL_ddepth (excludes SEG: those eight indices stay 0); ABS: GSR_FLAG_ABS_GRAD; ALPHA: gsr_blend_backward_alpha.  Counted
+ * where the instantiation is chosen, with relaxed atomics (renders may run from several host threads).
+ * gsr_debug_blend_backward_items: counts[2] (HOST) receives {items, list-segment items among them} of the work list the
+ * LATEST blend backward of the view with image state `image` (W x H) built.  Copies the list to the host and waits for
+ * `stream`; GSR_ERR_BAD_ARGUMENT for NULL / non-positive arguments or a state whose item count exceeds the list's room
+ * (no blend backward has run on it). */
+int gsr_debug_blend_backward_launches(uint64_t* counts);
+int gsr_debug_blend_backward_items(void* stream, int W, int H, const void* image, int64_t* counts);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

@@ -101,6 +101,8 @@ def test_argument_validation_needs_no_gpu():
     assert L.gsr_bin(None, 10, 100, 5, 64, 64, None, None, ctypes.c_void_p(16)) == -1  # scratch must be 256-byte aligned
     assert L.gsr_bin(None, 10, 100, 101, 64, 64, ctypes.c_void_p(256), ctypes.c_void_p(256), ctypes.c_void_p(256)) == -1  # G <= R
     assert L.gsr_debug_cov3d(None, 10, None, 1.0, None, None) == -1
+    assert L.gsr_debug_blend_backward_launches(None) == -1  # (no array for the 32 counts)
+    assert L.gsr_debug_blend_backward_items(None, 64, 64, None, r) == -1 and L.gsr_debug_blend_backward_items(None, 0, 64, ctypes.c_void_p(256), r) == -1
     assert L.gsr_sh_grad_compose(None, 10, 4, 16, 1, None, None, None, None) == -1  # degree > 3
     assert L.gsr_view_message_plan(None, 10, None, None, None, None, None) == -1
     assert L.gsr_view_messages_accumulate(None, 10, 3, 16, 0, None, 0, 0, None, None) == -1  # no views
