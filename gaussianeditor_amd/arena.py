@@ -25,6 +25,11 @@ the peak at that moment is (2 + 2 x growth) x capacity rows.  That is the moment
 failure there is reported as such (RuntimeError naming the sizes) instead of surfacing as a bare HIP out-of-memory error;
 `OptimizerArena(..., headroom=, growth=)` / `RowArena(..., headroom=, growth=)` choose the trade.
 
+Every view shares the buffer's version counter, and so does a Parameter wrapped around one.  The kernels write through raw
+pointers, so `compact`, `append` and `_reserve` move that counter themselves ("Native writers and the version
+counter"): after a prune or an append nothing that was read from ANY view of the arena before counts as unchanged -- an
+append-and-prune round trip brings a tensor back to the same address, shape and strides with other rows inside.
+
 Results are bit-identical to `tensor[mask]` / `torch.cat` (the same kernels as densify.compact_rows / append_rows; tests).
 No CPU fallback.
 """
@@ -34,6 +39,7 @@ import ctypes
 from typing import Dict, List, Optional
 
 import torch
+from torch.autograd.graph import increment_version
 
 from . import _native
 
@@ -99,6 +105,7 @@ class RowArena:
         self.capacity, self._offsets, self._half_bytes, self._buf = capacity, offsets, off, buf
         self.allocations += 1
         self._live = 0
+        increment_version(buf)  # (the rule of compact / append, kept here too: whoever refills the buffer moves its counter)
         if old is not None:
             for k, t in old.items():
                 self[k].copy_(t)
@@ -134,6 +141,7 @@ class RowArena:
             n = int(kept.value)
             other = self._live ^ 1
             if n > 0:
+                increment_version(self._buf)  # the kernel writes the other half through raw pointers: every view is "written"
                 for lo in range(0, len(self.names), 32):
                     chunk = self.names[lo:lo + 32]
                     arr = (_native.CompactTensor * len(chunk))()
@@ -162,6 +170,7 @@ class RowArena:
             self._reserve(max(int(self.growth * self.capacity), self.P + n + 1024))  # (rare: one copy of everything)
         L = _native.lib()
         keep_alive = []
+        increment_version(self._buf)  # the kernel writes behind the live rows through raw pointers: every view is "written"
         with torch.cuda.device(self.device):
             s = torch.cuda.current_stream(self.device).cuda_stream
             for lo in range(0, len(self.names), 32):

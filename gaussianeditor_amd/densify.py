@@ -32,6 +32,7 @@ import ctypes
 from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import torch
+from torch.autograd.graph import increment_version
 
 from . import _native
 
@@ -262,6 +263,7 @@ def add_densification_stats(xyz_gradient_accum: torch.Tensor, denom: torch.Tenso
     gp = (ctypes.c_void_p * V)(*[g.data_ptr() for g in gs])
     rp = (ctypes.c_void_p * V)(*[r.data_ptr() for r in rs])
     L = _native.lib()
+    increment_version((xyz_gradient_accum, denom, max_radii2D))  # updated through raw pointers: what `+=` does by itself
     with torch.cuda.device(dev):
         s = torch.cuda.current_stream(dev).cuda_stream
         _native.check("gsr_densify_stats", L.gsr_densify_stats(s, P, V, gp, rp, xyz_gradient_accum.data_ptr(), denom.data_ptr(),
@@ -364,6 +366,7 @@ def split_positions(xyz: torch.Tensor, scaling: torch.Tensor, rotation: torch.Te
         raise RuntimeError("split_positions: out must be a contiguous (N * n_split, 3) float32 tensor")
     if n_split == 0:
         return out
+    increment_version(out)  # (a caller's `out=` is written through its raw pointer)
     x, sc, rot, nz = xyz.detach().contiguous(), scaling.detach().contiguous(), rotation.detach().contiguous(), noise.contiguous()
     L = _native.lib()
     with torch.cuda.device(dev):

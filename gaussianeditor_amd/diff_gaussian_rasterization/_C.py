@@ -676,6 +676,7 @@ def apply_weights(background, means3D, weights, opacity, scales, rotations, scal
     w_work = weights if weights.is_contiguous() else weights.contiguous()
     c_work = cnt if cnt.is_contiguous() else cnt.contiguous()
     radii = torch.empty((P,), dtype=torch.int32, device=dev)
+    torch.autograd.graph.increment_version((w_work, c_work))  # updated through raw pointers: what an in-place op does by itself
     with torch.cuda.device(dev):
         # the reference passes `weights` in the colour slot only to skip the SH evaluation
         # (rasterizer_impl.cu:384, apply_weights.cu:219): no colour is needed at all here.

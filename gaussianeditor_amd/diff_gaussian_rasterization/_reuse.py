@@ -13,10 +13,18 @@ on the remembered geometry / lists (K6 alone), the first render's radii and dept
   * scalars (image size, fov tangents, scale modifier, flags, P, device, stream) by value;
   * every tensor that shaped the remembered state (means3D, scales, rotations, opacities, cov3D_precomp, the two matrices)
     either IS the tensor of the first render (same object, or the same storage at the same offset) with an unchanged
-    version counter -- an optimizer step, a densification or any other in-place write bumps it --, or is compared with it
-    bit for bit on the device (`gsr_arrays_equal`): the reference's `pc.get_opacity` / `get_scaling` / `get_rotation` are
-    fresh activation tensors on every call, equal in content and nothing else;
+    version counter, or is compared with it bit for bit on the device (`gsr_arrays_equal`): the reference's
+    `pc.get_opacity` / `get_scaling` / `get_rotation` are fresh activation tensors on every call, equal in content and
+    nothing else;
   * a remembered tensor whose version moved since the render cannot vouch for anything: miss.
+For the first kind the version counter is the whole proof, so it rests on a contract: WHOEVER WRITES INTO A TENSOR IN PLACE
+MOVES ITS COUNTER.  torch's own in-place ops do (`torch.optim.Adam.step`, `add_`, `copy_`, indexed assignment).  A kernel
+that writes through `data_ptr()` does not by itself: this package's writers -- `FusedMaskedAdam.step`, `RowArena.compact` /
+`append` (one counter for every view of the arena) and the others DESIGN.md lists under "Native writers and the version
+counter" -- call `torch.autograd.graph.increment_version` for what they write, and a caller's own native code has to do the
+same (or call `forget()`, from the rendering thread).  A write that moves no counter is served a stale image.
+The first render's radii and depth are the caller's tensors too: they are remembered as detached aliases (no autograd graph
+is kept alive) with their versions, and a caller who has edited one in place gets a miss, not the edit served back.
 A miss costs a few attribute reads; a hit one compare launch (0.1 ms per 500 MB) plus K6.
 
 The served image is connected to autograd like any render: if somebody differentiates through it -- GaussianEditor never
@@ -83,7 +91,7 @@ class _Tracked:
 
 
 class _Entry:
-    __slots__ = ("key", "tensors", "R", "geom", "binning", "img", "radii", "depth")
+    __slots__ = ("key", "tensors", "R", "geom", "binning", "img", "radii", "depth", "out_versions")
 
 
 _ROLES = ("means3D", "scales", "rotations", "opacities", "cov3D_precomp", "viewmatrix", "projmatrix")
@@ -108,7 +116,10 @@ def remember(rs, flags, means3D, scales, rotations, opacities, cov3D_precomp, nu
     e.key = _key(rs, flags, means3D)
     e.tensors = {r: _Tracked(t) for r, t in zip(_ROLES, (means3D, scales, rotations, opacities, cov3D_precomp,
                                                            rs.viewmatrix, rs.projmatrix))}
-    e.R, e.geom, e.binning, e.img, e.radii, e.depth = num_rendered, geom, binning, img, radii, depth
+    e.R, e.geom, e.binning, e.img = num_rendered, geom, binning, img
+    # radii and depth are handed to the caller: aliases without the render's graph, good for as long as nobody wrote to them
+    e.radii, e.depth = radii.detach(), depth.detach()
+    e.out_versions = (radii._version, depth._version)
     if not hasattr(_local, "entries"):
         _local.entries = {}
     _local.entries[means3D.device] = e
@@ -122,7 +133,7 @@ def lookup(rs, flags, means3D, scales, rotations, opacities, cov3D_precomp):
     e = getattr(_local, "entries", {}).get(means3D.device)
     if e is None:
         return None
-    if e.key != _key(rs, flags, means3D):
+    if e.key != _key(rs, flags, means3D) or (e.radii._version, e.depth._version) != e.out_versions:
         stats["misses"] += 1
         return None
     pending = []

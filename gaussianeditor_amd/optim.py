@@ -6,12 +6,18 @@
 launch of the HIP kernel behind `gsr_adam_step` (include/gsr.h): every scalar is read and written once, the row mask
 of `GaussianModel.apply_grad_mask` (:841-856) is applied inside, and optionally the gradient of the anchor loss
 (:152-184) is added on the fly.  The arithmetic is torch's single-tensor Adam in float32; there is no CPU fallback.
+
+The kernel writes through raw pointers, so `step()` moves the version counter of every parameter and moment it hands over
+("Native writers and the version counter"): a backward through tensors saved before the step raises as it does
+after `torch.optim.Adam.step()`, and a render remembered for view reuse stops vouching for them.
 """
 from __future__ import annotations
 
 from typing import Dict, Optional
 
 import torch
+
+from torch.autograd.graph import increment_version
 
 from . import _native
 
@@ -129,6 +135,9 @@ class FusedMaskedAdam(torch.optim.Optimizer):
                 mask_ptr = self._row_mask.data_ptr() if self._row_mask is not None else None
                 w_ptr = self._row_weight.data_ptr() if self._row_weight is not None else None
                 valid_ptr = self._grad_valid.data_ptr() if self._grad_valid is not None else None
+                # what an in-place torch op does by itself (host only; ahead of the launch, like torch: a counter that
+                # moved without a write costs a view-reuse miss, a write without it a stale image)
+                increment_version([t for p, _, st in chunk for t in (p, st["exp_avg"], st["exp_avg_sq"])])
                 with torch.cuda.device(dev):
                     _native.check("gsr_adam_step_rows", L.gsr_adam_step_rows(
                         torch.cuda.current_stream(dev).cuda_stream, len(chunk), arr, step, float(betas[0]), float(betas[1]),

@@ -45,3 +45,33 @@ def test_switch_and_thread_local_state():
         assert _reuse._local.entries == {}
     finally:
         gaussianeditor_amd.set_view_reuse(was)
+
+
+def test_a_bumped_arena_buffer_invalidates_every_view_of_it():
+    """The arena's tensors (gaussianeditor_amd/arena.py) are views of ONE byte buffer and share its version counter, and so
+    does a Parameter wrapped around one.  Its kernels write through raw pointers and bump the buffer
+    (torch.autograd.graph.increment_version): from then on no remembered view vouches for anything -- not even for a new
+    view of the same bytes with the same shape and strides, which is all an append-and-prune round trip leaves to tell by."""
+    from torch.autograd.graph import increment_version
+
+    buf = torch.zeros(2 * 4096, dtype=torch.uint8)
+
+    def region(start, rows):  # RowArena._region: a byte slice seen as the dtype, then as rows
+        return buf[start:start + rows * 12].view(torch.float32).view((rows, 3))
+
+    view = region(256, 10)
+    param = torch.nn.Parameter(region(256, 10).requires_grad_(True))
+    other = _reuse._Tracked(region(512, 10))
+    tv, tp = _reuse._Tracked(view), _reuse._Tracked(param)
+    assert tv.match(view) is True and tv.match(region(256, 10)) is True
+    assert tp.match(param) is True and tp.match(torch.nn.Parameter(region(256, 10).requires_grad_(True))) is True
+    assert tv.match(region(512, 10)) is None           # other rows of the buffer: other memory
+    increment_version(buf)                             # what RowArena.compact / append do next to their launches
+    assert view._version == param._version == buf._version == tv.version + 1
+    assert tv.match(view) is False and tv.match(region(256, 10)) is False
+    assert tp.match(param) is False and tp.match(torch.nn.Parameter(region(256, 10).requires_grad_(True))) is False
+    assert other.match(other.t) is False               # one counter for the whole buffer: every region is "written"
+    # a bump of a Parameter (FusedMaskedAdam.step) reaches the views it wraps, and the other way round
+    tv2 = _reuse._Tracked(view)
+    increment_version(param)
+    assert tv2.match(view) is False
