@@ -723,14 +723,16 @@ int gsr_alpha_image(void* stream, int W, int H, const void* image, float* out_al
   return GSR_OK;
 }
 
+// the flags K8+K9 reads (the persistent-rows form takes GSR_FLAG_ANTIALIAS alone)
+static const unsigned PRE_BWD_FLAGS = GSR_FLAG_ACC_SELF_CLEAN | GSR_FLAG_DEPTH_GRAD | GSR_FLAG_ANTIALIAS;
+
 static int preprocess_backward_impl(void* stream, int P, int D, int M, int W, int H, const float* means3D, const float* shs,
                                     const float* scales, float scale_modifier, const float* rotations,
                                     const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
                                     const float* campos, float tan_fovx, float tan_fovy, const int32_t* radii,
                                     const void* geom, const float* acc, float* dL_dmeans2D, float* dL_dopacity,
                                     float* dL_dcolors, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
-                                    float* dL_drgb, float* dL_dscales, float* dL_drots, uint8_t* row_state = nullptr,
-                                    bool self_clean = false, bool depth = false, bool antialias = false) {
+                                    float* dL_drgb, float* dL_dscales, float* dL_drots, uint8_t* row_state, unsigned flags) {
   if (P == 0) return GSR_OK;
   if (P < 0 || W <= 0 || H <= 0 || D < 0 || D > 3) return GSR_ERR_BAD_ARGUMENT;
   if (!means3D || !viewmatrix || !projmatrix || !radii || !geom) return GSR_ERR_BAD_ARGUMENT;
@@ -760,10 +762,10 @@ static int preprocess_backward_impl(void* stream, int P, int D, int M, int W, in
   pa.dL_dscale = scales ? dL_dscales : nullptr;
   pa.dL_drot = scales ? dL_drots : nullptr;
   pa.row_state = row_state;
-  pa.acc_clean = self_clean ? const_cast<float*>(acc) : nullptr;  // (GSR_FLAG_ACC_SELF_CLEAN: the caller's table, writable by contract)
-  pa.depth = depth ? 1 : 0;  // (GSR_FLAG_DEPTH_GRAD: column ACC_DEPTH enters dL_dmeans3D)
+  pa.acc_clean = (flags & GSR_FLAG_ACC_SELF_CLEAN) ? const_cast<float*>(acc) : nullptr;  // (GSR_FLAG_ACC_SELF_CLEAN: the caller's table, writable by contract)
+  pa.depth = (flags & GSR_FLAG_DEPTH_GRAD) ? 1 : 0;  // (GSR_FLAG_DEPTH_GRAD: column ACC_DEPTH enters dL_dmeans3D)
   // (GSR_FLAG_ANTIALIAS: where K8+K9 finds rec0 -- carve_geom puts it in front of `clamped`, both sections 256-byte aligned)
-  pa.rec0_lines = antialias ? (uint32_t)(((const char*)g.clamped - (const char*)g.rec0) / 256) : 0u;
+  pa.rec0_lines = (flags & GSR_FLAG_ANTIALIAS) ? (uint32_t)(((const char*)g.clamped - (const char*)g.rec0) / 256) : 0u;
   GSR_HIP(launch_preprocess_backward((hipStream_t)stream, pa));
   return GSR_OK;
 }
@@ -802,13 +804,10 @@ int gsr_preprocess_backward(void* stream, int P, int D, int M, int W, int H, con
                             float* dL_dcolors, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
                             float* dL_dscales, float* dL_drots, unsigned flags) {
   if (shs && !dL_dsh) return GSR_ERR_BAD_ARGUMENT;
-  // (the three flags this half reads)
-  if (flags & ~(GSR_FLAG_ACC_SELF_CLEAN | GSR_FLAG_DEPTH_GRAD | GSR_FLAG_ANTIALIAS)) return GSR_ERR_BAD_ARGUMENT;
+  if (flags & ~PRE_BWD_FLAGS) return GSR_ERR_BAD_ARGUMENT;
   return preprocess_backward_impl(stream, P, D, M, W, H, means3D, shs, scales, scale_modifier, rotations, cov3D_precomp,
                                   viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom, acc, dL_dmeans2D, dL_dopacity,
-                                  dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, nullptr, dL_dscales, dL_drots, nullptr,
-                                  (flags & GSR_FLAG_ACC_SELF_CLEAN) != 0, (flags & GSR_FLAG_DEPTH_GRAD) != 0,
-                                  (flags & GSR_FLAG_ANTIALIAS) != 0);
+                                  dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, nullptr, dL_dscales, dL_drots, nullptr, flags);
 }
 
 int gsr_preprocess_backward_rgb(void* stream, int P, int D, int M, int W, int H, const float* means3D, const float* shs,
@@ -819,12 +818,10 @@ int gsr_preprocess_backward_rgb(void* stream, int P, int D, int M, int W, int H,
                                 float* dL_dmeans3D, float* dL_dcov3D, float* dL_drgb,
                                 float* dL_dscales, float* dL_drots, unsigned flags) {
   if (!shs || !dL_drgb) return GSR_ERR_BAD_ARGUMENT;
-  if (flags & ~(GSR_FLAG_ACC_SELF_CLEAN | GSR_FLAG_DEPTH_GRAD | GSR_FLAG_ANTIALIAS)) return GSR_ERR_BAD_ARGUMENT;
+  if (flags & ~PRE_BWD_FLAGS) return GSR_ERR_BAD_ARGUMENT;
   return preprocess_backward_impl(stream, P, D, M, W, H, means3D, shs, scales, scale_modifier, rotations, cov3D_precomp,
                                   viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom, acc, dL_dmeans2D, dL_dopacity,
-                                  nullptr, dL_dmeans3D, dL_dcov3D, nullptr, dL_drgb, dL_dscales, dL_drots, nullptr,
-                                  (flags & GSR_FLAG_ACC_SELF_CLEAN) != 0, (flags & GSR_FLAG_DEPTH_GRAD) != 0,
-                                  (flags & GSR_FLAG_ANTIALIAS) != 0);
+                                  nullptr, dL_dmeans3D, dL_dcov3D, nullptr, dL_drgb, dL_dscales, dL_drots, nullptr, flags);
 }
 
 int gsr_preprocess_backward_rows(void* stream, int P, int D, int M, int W, int H, const float* means3D, const float* shs,
@@ -852,8 +849,7 @@ int gsr_preprocess_backward_rows_flags(void* stream, int P, int D, int M, int W,
   if (shs && !dL_dsh && !dL_drgb) return GSR_ERR_BAD_ARGUMENT;
   return preprocess_backward_impl(stream, P, D, M, W, H, means3D, shs, scales, scale_modifier, rotations, cov3D_precomp,
                                   viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom, acc, dL_dmeans2D, dL_dopacity,
-                                  dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_drgb, dL_dscales, dL_drots, row_state, false,
-                                  false, (flags & GSR_FLAG_ANTIALIAS) != 0);
+                                  dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_drgb, dL_dscales, dL_drots, row_state, flags);
 }
 
 int gsr_sh_grad_compose(void* stream, int P, int D, int M, int num_views, const float* means3D, const float* campos,
@@ -943,6 +939,29 @@ int gsr_view_messages_accumulate_rows(void* stream, int64_t P, int D, int M, int
   return GSR_OK;
 }
 
+// gsr_backward and gsr_backward_depth (`depth`: the blend half is gsr_blend_backward_depth and K8+K9 reads GSR_FLAG_DEPTH_GRAD)
+static int backward_fused(bool depth, void* stream, int P, int D, int M, int64_t R, int W, int H, const float* bg,
+                          const float* means3D, const float* shs, const float* scales, float scale_modifier,
+                          const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                          const float* campos, float tan_fovx, float tan_fovy, const int32_t* radii, const void* geom,
+                          const void* binning, const void* image, const float* dL_dpix, const float* dL_ddepth, float* acc,
+                          float* dL_dmeans2D, float* dL_dopacity, float* dL_dcolors, float* dL_dmeans3D, float* dL_dcov3D,
+                          float* dL_dsh, float* dL_dscales, float* dL_drots, unsigned flags) {
+  if (P == 0) return GSR_OK;
+  if (flags & GSR_FLAG_ABS_GRAD) return GSR_ERR_BAD_ARGUMENT;  // (no output for it here: the halves, with gsr_abs_grad_take between them)
+  if (R > 0 && !binning) return GSR_ERR_BAD_ARGUMENT;
+  if ((flags & GSR_FLAG_ACC_SELF_CLEAN) && (flags & GSR_FLAG_CLEAR_GRADS)) return GSR_ERR_BAD_ARGUMENT;
+  const unsigned blend_flags = flags & ~GSR_FLAG_ACC_SELF_CLEAN;
+  const int st = depth ? gsr_blend_backward_depth(stream, P, R, W, H, bg, geom, binning, image, dL_dpix, dL_ddepth, acc, nullptr,
+                                                  blend_flags)
+                       : gsr_blend_backward(stream, P, R, W, H, bg, geom, binning, image, dL_dpix, acc, nullptr, blend_flags);
+  if (st != GSR_OK) return st;
+  return gsr_preprocess_backward(stream, P, D, M, W, H, means3D, shs, scales, scale_modifier, rotations, cov3D_precomp,
+                                 viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom, acc, dL_dmeans2D, dL_dopacity,
+                                 dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drots,
+                                 (flags & (GSR_FLAG_ACC_SELF_CLEAN | GSR_FLAG_ANTIALIAS)) | (depth ? GSR_FLAG_DEPTH_GRAD : 0u));
+}
+
 int gsr_backward(void* stream, int P, int D, int M, int64_t R, int W, int H, const float* bg, const float* means3D,
                  const float* shs, const float* colors_precomp, const float* scales, float scale_modifier,
                  const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
@@ -951,17 +970,9 @@ int gsr_backward(void* stream, int P, int D, int M, int64_t R, int W, int H, con
                  float* dL_dopacity, float* dL_dcolors, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
                  float* dL_dscales, float* dL_drots, unsigned flags) {
   (void)colors_precomp;  // the blend kernels read the colour copy held in the geometry records
-  if (P == 0) return GSR_OK;
-  if (flags & GSR_FLAG_ABS_GRAD) return GSR_ERR_BAD_ARGUMENT;  // (no output for it here: the halves, with gsr_abs_grad_take between them)
-  if (R > 0 && !binning) return GSR_ERR_BAD_ARGUMENT;
-  const bool self_clean = (flags & GSR_FLAG_ACC_SELF_CLEAN) != 0;
-  if (self_clean && (flags & GSR_FLAG_CLEAR_GRADS)) return GSR_ERR_BAD_ARGUMENT;
-  int st = gsr_blend_backward(stream, P, R, W, H, bg, geom, binning, image, dL_dpix, acc, nullptr, flags & ~GSR_FLAG_ACC_SELF_CLEAN);
-  if (st != GSR_OK) return st;
-  return gsr_preprocess_backward(stream, P, D, M, W, H, means3D, shs, scales, scale_modifier, rotations, cov3D_precomp,
-                                 viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom, acc, dL_dmeans2D, dL_dopacity,
-                                 dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drots,
-                                 (self_clean ? GSR_FLAG_ACC_SELF_CLEAN : 0u) | (flags & GSR_FLAG_ANTIALIAS));
+  return backward_fused(false, stream, P, D, M, R, W, H, bg, means3D, shs, scales, scale_modifier, rotations, cov3D_precomp,
+                        viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom, binning, image, dL_dpix, nullptr, acc,
+                        dL_dmeans2D, dL_dopacity, dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drots, flags);
 }
 
 int gsr_backward_depth(void* stream, int P, int D, int M, int64_t R, int W, int H, const float* bg, const float* means3D,
@@ -973,18 +984,9 @@ int gsr_backward_depth(void* stream, int P, int D, int M, int64_t R, int W, int 
                        float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drots,
                        unsigned flags) {
   (void)colors_precomp;
-  if (P == 0) return GSR_OK;
-  if (flags & GSR_FLAG_ABS_GRAD) return GSR_ERR_BAD_ARGUMENT;  // (no output for it here: the halves, with gsr_abs_grad_take between them)
-  if (R > 0 && !binning) return GSR_ERR_BAD_ARGUMENT;
-  const bool self_clean = (flags & GSR_FLAG_ACC_SELF_CLEAN) != 0;
-  if (self_clean && (flags & GSR_FLAG_CLEAR_GRADS)) return GSR_ERR_BAD_ARGUMENT;
-  int st = gsr_blend_backward_depth(stream, P, R, W, H, bg, geom, binning, image, dL_dpix, dL_ddepth, acc, nullptr,
-                                    flags & ~GSR_FLAG_ACC_SELF_CLEAN);
-  if (st != GSR_OK) return st;
-  return gsr_preprocess_backward(stream, P, D, M, W, H, means3D, shs, scales, scale_modifier, rotations, cov3D_precomp,
-                                 viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom, acc, dL_dmeans2D, dL_dopacity,
-                                 dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drots,
-                                 (self_clean ? GSR_FLAG_ACC_SELF_CLEAN : 0u) | GSR_FLAG_DEPTH_GRAD | (flags & GSR_FLAG_ANTIALIAS));
+  return backward_fused(true, stream, P, D, M, R, W, H, bg, means3D, shs, scales, scale_modifier, rotations, cov3D_precomp,
+                        viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom, binning, image, dL_dpix, dL_ddepth, acc,
+                        dL_dmeans2D, dL_dopacity, dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drots, flags);
 }
 
 int gsr_mark_visible(void* stream, int P, const float* means3D, const float* viewmatrix, const float* projmatrix,

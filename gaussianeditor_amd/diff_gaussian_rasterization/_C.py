@@ -50,6 +50,13 @@ def _require_cuda(t: torch.Tensor, name: str) -> None:
             "(device 'cuda') through the HIP extension -- there is no CPU fallback.")
 
 
+def _same_device(t: torch.Tensor, name: str, dev: torch.device) -> None:
+    if t.device != dev:
+        raise RuntimeError(
+            f"diff_gaussian_rasterization: `{name}` is on {t.device} but `means3D` is on {dev}; every tensor of a call "
+            "must live on the device of `means3D` (the native library receives raw device pointers)")
+
+
 def _f32(t: torch.Tensor, name: str, dev: Optional[torch.device] = None) -> torch.Tensor:
     """contiguous float32, 16-byte aligned (the kernels use dwordx4 loads on (P,4)/(P,16,3) rows), and -- with `dev`, the
     device of `means3D` -- on that device: the native call takes raw pointers, so a tensor on the host or on another GPU
@@ -59,24 +66,25 @@ def _f32(t: torch.Tensor, name: str, dev: Optional[torch.device] = None) -> torc
         raise RuntimeError(f"diff_gaussian_rasterization: `{name}` must be a tensor, got {type(t).__name__}")
     if t.dtype != torch.float32:
         raise RuntimeError(f"expected float32 for `{name}`, got {t.dtype}")
-    if dev is not None and t.numel() != 0 and t.device != dev:
-        raise RuntimeError(
-            f"diff_gaussian_rasterization: `{name}` is on {t.device} but `means3D` is on {dev}; every tensor of a call "
-            "must live on the device of `means3D` (the native library receives raw device pointers)")
+    if dev is not None and t.numel() != 0:
+        _same_device(t, name, dev)
     t = t.contiguous()
     if t.data_ptr() % 16 != 0:
         t = t.clone(memory_format=torch.contiguous_format)
     return t
 
 
+def _f32_all(dev: torch.device, **named) -> list:
+    """`_f32` of a call's float tensors, each under the name its messages use, in the order given."""
+    return [_f32(t, name, dev) for name, t in named.items()]
+
+
 def _on_device(t: torch.Tensor, name: str, dev: torch.device, dtype: torch.dtype) -> None:
     """device + dtype check for the non-float arguments (radii, the three saved state buffers, cnt)."""
     if not isinstance(t, torch.Tensor) or t.dtype != dtype:
         raise RuntimeError(f"diff_gaussian_rasterization: `{name}` must be a {dtype} tensor")
-    if t.numel() != 0 and t.device != dev:
-        raise RuntimeError(
-            f"diff_gaussian_rasterization: `{name}` is on {t.device} but `means3D` is on {dev}; every tensor of a call "
-            "must live on the device of `means3D` (the native library receives raw device pointers)")
+    if t.numel() != 0:
+        _same_device(t, name, dev)
 
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
@@ -102,6 +110,16 @@ def _check_means(means3D: torch.Tensor) -> None:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")  # rasterize_points.cu:46-48
 
 
+def _bin(s: int, dev, P, R, G, W, H, geom):
+    """The binning and image scratch of a view whose counts (R, and G tile-group instances) are known, and gsr_bin."""
+    # (the image scratch is sized once R is known: its checkpoint pool, 128 MB at 1080p, exists only for views with long lists)
+    _, bbytes, ibytes = _native.scratch_sizes(P, R, W, H, G)
+    binning = torch.empty(bbytes, dtype=torch.uint8, device=dev)
+    img = torch.empty(ibytes, dtype=torch.uint8, device=dev)
+    _native.check("gsr_bin", _native.lib().gsr_bin(s, P, R, G, W, H, geom.data_ptr(), _ptr(binning), img.data_ptr()))
+    return binning, img
+
+
 def _preprocess_and_bin(dev, P, D, M, means3D, scales, scale_modifier, rotations, opacity, sh, cov3D_precomp, colors,
                         viewmatrix, projmatrix, campos, W, H, tan_fovx, tan_fovy, prefiltered, skip_color, radii, flags):
     L = _native.lib()
@@ -113,12 +131,8 @@ def _preprocess_and_bin(dev, P, D, M, means3D, scales, scale_modifier, rotations
         s, P, D, M, _ptr(means3D), _ptr(scales), scale_modifier, _ptr(rotations), _ptr(opacity), _ptr(sh),
         _ptr(cov3D_precomp), _ptr(colors), _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos), W, H, tan_fovx, tan_fovy,
         int(bool(prefiltered)), int(skip_color), flags, radii.data_ptr(), geom.data_ptr(), counts))
-    R, G = int(counts[0]), int(counts[1])
-    # (the image scratch is sized once R is known: its checkpoint pool, 128 MB at 1080p, exists only for views with long lists)
-    _, bbytes, ibytes = _native.scratch_sizes(P, R, W, H, G)
-    binning = torch.empty(bbytes, dtype=torch.uint8, device=dev)
-    img = torch.empty(ibytes, dtype=torch.uint8, device=dev)
-    _native.check("gsr_bin", L.gsr_bin(s, P, R, G, W, H, geom.data_ptr(), _ptr(binning), img.data_ptr()))
+    R = int(counts[0])
+    binning, img = _bin(s, dev, P, R, int(counts[1]), W, H, geom)
     return R, geom, binning, img
 
 
@@ -139,12 +153,9 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
                 torch.zeros((1, H, W), dtype=torch.float32, device=dev), torch.zeros((0,), dtype=torch.int32, device=dev),
                 torch.empty(0, **u8), torch.empty(0, **u8), torch.empty(0, **u8))
     M = int(sh.size(1)) if sh.size(0) != 0 else 0
-    means3D, opacity = _f32(means3D, "means3D"), _f32(opacity, "opacity", dev)
-    background, viewmatrix, projmatrix, campos = (_f32(background, "bg", dev), _f32(viewmatrix, "viewmatrix", dev),
-                                                  _f32(projmatrix, "projmatrix", dev), _f32(campos, "campos", dev))
-    colors, scales, rotations, cov3D_precomp, sh = (_f32(colors, "colors_precomp", dev), _f32(scales, "scales", dev),
-                                                    _f32(rotations, "rotations", dev),
-                                                    _f32(cov3D_precomp, "cov3D_precomp", dev), _f32(sh, "sh", dev))
+    means3D, opacity, background, viewmatrix, projmatrix, campos, colors, scales, rotations, cov3D_precomp, sh = _f32_all(
+        dev, means3D=means3D, opacity=opacity, bg=background, viewmatrix=viewmatrix, projmatrix=projmatrix, campos=campos,
+        colors_precomp=colors, scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp, sh=sh)
     out_color = torch.empty((NUM_CHANNELS, H, W), dtype=torch.float32, device=dev)
     out_depth = torch.empty((1, H, W), dtype=torch.float32, device=dev)
     radii = torch.empty((P,), dtype=torch.int32, device=dev)
@@ -184,12 +195,9 @@ def rasterize_gaussians_begin(background, means3D, colors, opacity, scales, rota
     if P == 0:
         raise RuntimeError("rasterize_gaussians_begin: an empty scene has nothing to wait for; call rasterize_gaussians()")
     M = int(sh.size(1)) if sh.size(0) != 0 else 0
-    means3D, opacity = _f32(means3D, "means3D"), _f32(opacity, "opacity", dev)
-    background, viewmatrix, projmatrix, campos = (_f32(background, "bg", dev), _f32(viewmatrix, "viewmatrix", dev),
-                                                  _f32(projmatrix, "projmatrix", dev), _f32(campos, "campos", dev))
-    colors, scales, rotations, cov3D_precomp, sh = (_f32(colors, "colors_precomp", dev), _f32(scales, "scales", dev),
-                                                    _f32(rotations, "rotations", dev),
-                                                    _f32(cov3D_precomp, "cov3D_precomp", dev), _f32(sh, "sh", dev))
+    means3D, opacity, background, viewmatrix, projmatrix, campos, colors, scales, rotations, cov3D_precomp, sh = _f32_all(
+        dev, means3D=means3D, opacity=opacity, bg=background, viewmatrix=viewmatrix, projmatrix=projmatrix, campos=campos,
+        colors_precomp=colors, scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp, sh=sh)
     pf = PendingForward()
     pf.dev, pf.P, pf.H, pf.W, pf.flags, pf.debug, pf.background = dev, P, H, W, flags, bool(debug), background
     pf.keep = (means3D, opacity, viewmatrix, projmatrix, campos, colors, scales, rotations, cov3D_precomp, sh)
@@ -221,13 +229,10 @@ def rasterize_gaussians_finish(pf: "PendingForward"):
         ticket, pf.ticket = pf.ticket, None  # (spent by the native call whatever it returns)
         counts = (ctypes.c_int64 * 2)()
         _native.check("gsr_preprocess_end", L.gsr_preprocess_end(s, P, W, H, pf.geom.data_ptr(), ticket, counts))
-        R, G = int(counts[0]), int(counts[1])
-        _, bbytes, ibytes = _native.scratch_sizes(P, R, W, H, G)
-        binning = torch.empty(bbytes, dtype=torch.uint8, device=dev)
-        img = torch.empty(ibytes, dtype=torch.uint8, device=dev)
+        R = int(counts[0])
         out_color = torch.empty((NUM_CHANNELS, H, W), dtype=torch.float32, device=dev)
         out_depth = torch.empty((1, H, W), dtype=torch.float32, device=dev)
-        _native.check("gsr_bin", L.gsr_bin(s, P, R, G, W, H, pf.geom.data_ptr(), _ptr(binning), img.data_ptr()))
+        binning, img = _bin(s, dev, P, R, int(counts[1]), W, H, pf.geom)
         _native.check("gsr_blend_forward", L.gsr_blend_forward(
             s, P, R, W, H, pf.background.data_ptr(), pf.geom.data_ptr(), _ptr(binning), img.data_ptr(),
             out_color.data_ptr(), out_depth.data_ptr(), flags))
@@ -330,13 +335,14 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                            hold the zeros of an earlier call are not rewritten.
     `dL_dout_depth` (extension, keyword): (1,H,W) gradient of the depth output, or None (the reference: the depth image
     carries no gradient).  Given, the backward also differentiates the depth image (include/gsr.h: GSR_FLAG_DEPTH_GRAD,
-    gsr_backward_depth); not with the "row_state" mode (gsr_preprocess_backward_rows takes no depth gradient).
+    gsr_blend_backward_depth); not with the "row_state" mode (gsr_preprocess_backward_rows takes no depth gradient).
     `abs_grad_out` (extension, keyword): a contiguous (P,3) float32 tensor on the device of `means3D`, or None.  Given, it is
-    fully written with the absolute screen-space gradient (include/gsr.h: GSR_FLAG_ABS_GRAD) -- the backward then always runs
-    as its two halves with gsr_abs_grad_take between them; the eight returned gradients are what they are without it.
+    fully written with the absolute screen-space gradient (include/gsr.h: GSR_FLAG_ABS_GRAD), by gsr_abs_grad_take between
+    the backward's two halves; the eight returned gradients are what they are without it.
     `dL_dout_alpha` (extension, keyword): (1,H,W) float32 gradient of the alpha image (alpha_image()), or None.  Given, the
-    blend half is gsr_blend_backward_alpha (with `dL_dout_depth` too, if that is given) and the backward runs as its two
-    halves; the K8+K9 half is the one the route uses without it."""
+    blend half is gsr_blend_backward_alpha (with `dL_dout_depth` too, if that is given); the K8+K9 half is the one the
+    route uses without it.
+    Every backward is issued as its two halves (a blend half, then a K8+K9 half), never through the fused gsr_backward."""
     flags = _flags(flags)
     dev = means3D.device
     P = int(means3D.size(0))
@@ -348,33 +354,24 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
         if hw is None or tuple(dL_dout_alpha.shape) != (1,) + hw:
             raise RuntimeError(f"diff_gaussian_rasterization: `dL_dout_alpha` must be a {(1,) + (hw or ('H', 'W'))} tensor, "
                                f"got {tuple(dL_dout_alpha.shape)}")
-        if dL_dout_alpha.device != dev:
-            raise RuntimeError(
-                f"diff_gaussian_rasterization: `dL_dout_alpha` is on {dL_dout_alpha.device} but `means3D` is on {dev}; every "
-                "tensor of a call must live on the device of `means3D` (the native library receives raw device pointers)")
+        _same_device(dL_dout_alpha, "dL_dout_alpha", dev)
     if abs_grad_out is not None:
         if not isinstance(abs_grad_out, torch.Tensor) or abs_grad_out.dtype != torch.float32:
             raise RuntimeError("diff_gaussian_rasterization: `abs_grad_out` must be a float32 tensor")
         if tuple(abs_grad_out.shape) != (P, 3) or not abs_grad_out.is_contiguous():
             raise RuntimeError(f"diff_gaussian_rasterization: `abs_grad_out` must be a contiguous ({P}, 3) tensor, got "
                                f"{tuple(abs_grad_out.shape)}")
-        if abs_grad_out.device != dev:
-            raise RuntimeError(
-                f"diff_gaussian_rasterization: `abs_grad_out` is on {abs_grad_out.device} but `means3D` is on {dev}; every "
-                "tensor of a call must live on the device of `means3D` (the native library receives raw device pointers)")
+        _same_device(abs_grad_out, "abs_grad_out", dev)
     H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
     M = int(sh.size(1)) if sh.size(0) != 0 else 0
     if P == 0:
         z = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)  # noqa: E731
         return z(0, 3), z(0, NUM_CHANNELS), z(0, 1), z(0, 3), z(0, 6), z(0, M, 3), z(0, 3), z(0, 4)
     _require_cuda(means3D, "means3D")
-    means3D = _f32(means3D, "means3D")
-    background, viewmatrix, projmatrix, campos = (_f32(background, "bg", dev), _f32(viewmatrix, "viewmatrix", dev),
-                                                  _f32(projmatrix, "projmatrix", dev), _f32(campos, "campos", dev))
-    colors, scales, rotations, cov3D_precomp, sh = (_f32(colors, "colors_precomp", dev), _f32(scales, "scales", dev),
-                                                    _f32(rotations, "rotations", dev),
-                                                    _f32(cov3D_precomp, "cov3D_precomp", dev), _f32(sh, "sh", dev))
-    dL_dpix = _f32(dL_dout_color, "dL_dout_color", dev)
+    means3D, background, viewmatrix, projmatrix, campos, colors, scales, rotations, cov3D_precomp, sh, dL_dpix = _f32_all(
+        dev, means3D=means3D, bg=background, viewmatrix=viewmatrix, projmatrix=projmatrix, campos=campos,
+        colors_precomp=colors, scales=scales, rotations=rotations, cov3D_precomp=cov3D_precomp, sh=sh,
+        dL_dout_color=dL_dout_color)
     dL_ddepth = None
     if dL_dout_depth is not None:
         dL_ddepth = _f32(dL_dout_depth, "dL_dout_depth", dev)
@@ -427,105 +424,64 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     persist = _ACC_PERSIST and acc is None and row_state is None
     if persist:
         acc = _checkout_acc(dev, stream, P)
-        bwd_flags = flags | options.FLAG_ACC_SELF_CLEAN
-    else:
-        if acc is None:
-            acc = torch.empty((_native.ACC_ROW * P,), dtype=torch.float32, device=dev)
-        bwd_flags = flags | options.FLAG_CLEAR_GRADS  # (the table is not zero: the blend backward clears it)
+    elif acc is None:
+        acc = torch.empty((_native.ACC_ROW * P,), dtype=torch.float32, device=dev)
     acc = acc.view(P, _native.ACC_ROW)
     if not has_colors:
         dL_dcolors = acc[:, _native.ACC_COLOR:_native.ACC_COLOR + NUM_CHANNELS] if not persist else \
             torch.zeros((0, NUM_CHANNELS), dtype=torch.float32, device=dev)
     L = _native.lib()
-    # absolute screen-space gradients: the blend half takes the bit and a row mask, and gsr_abs_grad_take moves the two
-    # columns out of the table (and zeroes them) in front of K8+K9, whichever entry point that is
-    abs_bit = options.FLAG_ABS_GRAD if abs_grad_out is not None else 0
-
-    def new_touched():  # K7 clears it and marks the rows it adds to
-        return torch.empty(((P + 15) // 16) * 16, dtype=torch.uint8, device=dev)
-
-    def take_abs_grad(touched):
-        if abs_grad_out is not None:
-            _native.check("gsr_abs_grad_take", L.gsr_abs_grad_take(_stream(dev), P, acc.data_ptr(), touched.data_ptr(),
-                                                                   abs_grad_out.data_ptr()))
-
-    def blend_half(touched, blend_flags):  # K7 through the entry point that takes the pixel gradients this backward was given
-        head = (_stream(dev), P, int(R), W, H, background.data_ptr(), geomBuffer.data_ptr(), _ptr(binningBuffer),
-                imageBuffer.data_ptr(), dL_dpix.data_ptr())
-        tail = (acc.data_ptr(), _ptr(touched), blend_flags)
+    # One route, whatever was asked: K7 through the entry point that takes the pixel gradients this backward was given, the
+    # absolute sums out of the table where asked for, the "sh_rgb" notification, then K8+K9 in the form that has the outputs.
+    # (The library's fused gsr_backward / gsr_backward_depth are these two calls behind one; the binding does not use them:
+    # profiles/backward_routes_ab.md.)
+    # The blend half clears a table that is not the persistent one (CLEAR_GRADS) and takes ABS_GRAD; K8+K9 zeroes the
+    # persistent one again (ACC_SELF_CLEAN) and takes DEPTH_GRAD; ANTIALIAS, a flag of the view, goes to both.
+    blend_flags = (flags | (0 if persist else options.FLAG_CLEAR_GRADS)
+                   | (options.FLAG_ABS_GRAD if abs_grad_out is not None else 0))
+    pre_flags = ((options.FLAG_ACC_SELF_CLEAN if persist else 0) | (options.FLAG_DEPTH_GRAD if dL_ddepth is not None else 0)
+                 | (flags & options.FLAG_ANTIALIAS))
+    # K7's row mask (it clears it and marks the rows it adds to): only where somebody reads it -- with a mask the work-list
+    # launch carries extra fill blocks
+    touched = torch.empty(((P + 15) // 16) * 16, dtype=torch.uint8, device=dev) \
+        if (dL_drgb is not None or abs_grad_out is not None) else None
+    with torch.cuda.device(dev):
+        # (every call also when nothing was rendered: the blend half then only clears the accumulator table)
+        blend = (_stream(dev), P, int(R), W, H, background.data_ptr(), geomBuffer.data_ptr(), _ptr(binningBuffer),
+                 imageBuffer.data_ptr(), dL_dpix.data_ptr())
+        blend_out = (acc.data_ptr(), _ptr(touched), blend_flags)
         if dL_dalpha is not None:
             _native.check("gsr_blend_backward_alpha", L.gsr_blend_backward_alpha(
-                *head, None if dL_ddepth is None else dL_ddepth.data_ptr(), dL_dalpha.data_ptr(), *tail))
+                *blend, None if dL_ddepth is None else dL_ddepth.data_ptr(), dL_dalpha.data_ptr(), *blend_out))
         elif dL_ddepth is not None:
-            _native.check("gsr_blend_backward_depth", L.gsr_blend_backward_depth(*head, dL_ddepth.data_ptr(), *tail))
+            _native.check("gsr_blend_backward_depth", L.gsr_blend_backward_depth(*blend, dL_ddepth.data_ptr(), *blend_out))
         else:
-            _native.check("gsr_blend_backward", L.gsr_blend_backward(*head, *tail))
-    with torch.cuda.device(dev):
-        col_out = dL_dcolors.data_ptr() if has_colors else None
-        if row_state is not None:  # gradient arrays kept across calls: only the rows that change are written
-            # (also when nothing was rendered: the call then only clears the accumulator table)
-            touched = new_touched() if (dL_drgb is not None or abs_grad_out is not None) else None
-            blend_half(touched, bwd_flags | abs_bit)
-            take_abs_grad(touched)
-            if dL_drgb is not None:
-                grad_alloc("after_blend_backward", touched[:P], False)
-            _native.check("gsr_preprocess_backward_rows_flags", L.gsr_preprocess_backward_rows_flags(
-                _stream(dev), P, int(degree), M, W, H, means3D.data_ptr(), _ptr(sh), _ptr(scales), float(scale_modifier),
-                _ptr(rotations), _ptr(cov3D_precomp), viewmatrix.data_ptr(), projmatrix.data_ptr(), _ptr(campos),
-                float(tan_fovx), float(tan_fovy), radii.data_ptr(), geomBuffer.data_ptr(), acc.data_ptr(),
-                dL_dmeans2D.data_ptr(), dL_dopacity.data_ptr(), col_out, dL_dmeans3D.data_ptr(), _ptr(dL_dcov3D),
-                _ptr(dL_dsh) if dL_drgb is None else None, None if dL_drgb is None else dL_drgb.data_ptr(),
-                dL_dscales.data_ptr() if has_scales else None, dL_drotations.data_ptr() if has_scales else None,
-                row_state.data_ptr(), flags & options.FLAG_ANTIALIAS))
-        elif dL_drgb is None and (abs_grad_out is not None or dL_dalpha is not None):
-            # gsr_backward / gsr_backward_depth as their halves (the fused calls have no output for the absolute sums and no
-            # input for the alpha image's gradient); the row mask only where gsr_abs_grad_take reads it
-            touched = new_touched() if abs_grad_out is not None else None
-            blend_half(touched, (bwd_flags & ~options.FLAG_ACC_SELF_CLEAN) | abs_bit)
-            take_abs_grad(touched)
-            _native.check("gsr_preprocess_backward", L.gsr_preprocess_backward(
-                _stream(dev), P, int(degree), M, W, H, means3D.data_ptr(), _ptr(sh), _ptr(scales), float(scale_modifier),
-                _ptr(rotations), _ptr(cov3D_precomp), viewmatrix.data_ptr(), projmatrix.data_ptr(), _ptr(campos),
-                float(tan_fovx), float(tan_fovy), radii.data_ptr(), geomBuffer.data_ptr(), acc.data_ptr(),
-                dL_dmeans2D.data_ptr(), dL_dopacity.data_ptr(), col_out, dL_dmeans3D.data_ptr(), _ptr(dL_dcov3D),
-                _ptr(dL_dsh), dL_dscales.data_ptr() if has_scales else None,
-                dL_drotations.data_ptr() if has_scales else None,
-                (options.FLAG_ACC_SELF_CLEAN if persist else 0) | (options.FLAG_DEPTH_GRAD if dL_ddepth is not None else 0)
-                | (flags & options.FLAG_ANTIALIAS)))
-        elif dL_drgb is None and dL_ddepth is not None:
-            _native.check("gsr_backward_depth", L.gsr_backward_depth(
-                _stream(dev), P, int(degree), M, int(R), W, H, background.data_ptr(), means3D.data_ptr(), _ptr(sh),
-                _ptr(colors), _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp),
-                viewmatrix.data_ptr(), projmatrix.data_ptr(), _ptr(campos), float(tan_fovx), float(tan_fovy),
-                radii.data_ptr(), geomBuffer.data_ptr(), _ptr(binningBuffer), imageBuffer.data_ptr(), dL_dpix.data_ptr(),
-                dL_ddepth.data_ptr(), acc.data_ptr(), dL_dmeans2D.data_ptr(), dL_dopacity.data_ptr(), col_out,
-                dL_dmeans3D.data_ptr(), _ptr(dL_dcov3D), _ptr(dL_dsh), dL_dscales.data_ptr() if has_scales else None,
-                dL_drotations.data_ptr() if has_scales else None, bwd_flags))
-        elif dL_drgb is None:
-            _native.check("gsr_backward", L.gsr_backward(
-                _stream(dev), P, int(degree), M, int(R), W, H, background.data_ptr(), means3D.data_ptr(), _ptr(sh),
-                _ptr(colors), _ptr(scales), float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp),
-                viewmatrix.data_ptr(), projmatrix.data_ptr(), _ptr(campos), float(tan_fovx), float(tan_fovy),
-                radii.data_ptr(), geomBuffer.data_ptr(), _ptr(binningBuffer), imageBuffer.data_ptr(), dL_dpix.data_ptr(),
-                acc.data_ptr(), dL_dmeans2D.data_ptr(), dL_dopacity.data_ptr(), col_out,
-                dL_dmeans3D.data_ptr(), _ptr(dL_dcov3D), _ptr(dL_dsh), dL_dscales.data_ptr() if has_scales else None,
-                dL_drotations.data_ptr() if has_scales else None, bwd_flags))
-        else:
-            # (also when nothing was rendered: the call then only clears the accumulator table)
-            touched = new_touched()
-            blend_half(touched, (bwd_flags & ~options.FLAG_ACC_SELF_CLEAN) | abs_bit)
-            take_abs_grad(touched)
+            _native.check("gsr_blend_backward", L.gsr_blend_backward(*blend, *blend_out))
+        if abs_grad_out is not None:  # moves the two columns out of the table (and zeroes them) in front of K8+K9
+            _native.check("gsr_abs_grad_take", L.gsr_abs_grad_take(_stream(dev), P, acc.data_ptr(), touched.data_ptr(),
+                                                                   abs_grad_out.data_ptr()))
+        if dL_drgb is not None:
             # notification (no allocation): K7 is enqueued, K8+K9 not yet -- multiview.py starts the exchange of the
             # touched-row counts here (from K7's row mask), so that it and the host's wait for it run underneath K8+K9
             grad_alloc("after_blend_backward", touched[:P], False)
+        # the argument head the three K8+K9 entry points share, then what each signature differs in
+        pre = (_stream(dev), P, int(degree), M, W, H, means3D.data_ptr(), _ptr(sh), _ptr(scales), float(scale_modifier),
+               _ptr(rotations), _ptr(cov3D_precomp), viewmatrix.data_ptr(), projmatrix.data_ptr(), _ptr(campos),
+               float(tan_fovx), float(tan_fovy), radii.data_ptr(), geomBuffer.data_ptr(), acc.data_ptr(),
+               dL_dmeans2D.data_ptr(), dL_dopacity.data_ptr())
+        col_out = dL_dcolors.data_ptr() if has_colors else None
+        geo_out = (dL_dmeans3D.data_ptr(), _ptr(dL_dcov3D))
+        sr_out = (dL_dscales.data_ptr(), dL_drotations.data_ptr()) if has_scales else (None, None)
+        if row_state is not None:  # gradient arrays kept across calls: only the rows that change are written
+            _native.check("gsr_preprocess_backward_rows_flags", L.gsr_preprocess_backward_rows_flags(
+                *pre, col_out, *geo_out, _ptr(dL_dsh), _ptr(dL_drgb), *sr_out, row_state.data_ptr(),
+                flags & options.FLAG_ANTIALIAS))
+        elif dL_drgb is not None:
             _native.check("gsr_preprocess_backward_rgb", L.gsr_preprocess_backward_rgb(
-                _stream(dev), P, int(degree), M, W, H, means3D.data_ptr(), _ptr(sh), _ptr(scales), float(scale_modifier),
-                _ptr(rotations), _ptr(cov3D_precomp), viewmatrix.data_ptr(), projmatrix.data_ptr(), _ptr(campos),
-                float(tan_fovx), float(tan_fovy), radii.data_ptr(), geomBuffer.data_ptr(), acc.data_ptr(),
-                dL_dmeans2D.data_ptr(), dL_dopacity.data_ptr(), dL_dmeans3D.data_ptr(), _ptr(dL_dcov3D), dL_drgb.data_ptr(),
-                dL_dscales.data_ptr() if has_scales else None, dL_drotations.data_ptr() if has_scales else None,
-                (options.FLAG_ACC_SELF_CLEAN if persist else 0) | (options.FLAG_DEPTH_GRAD if dL_ddepth is not None else 0)
-                | (flags & options.FLAG_ANTIALIAS)))
+                *pre, *geo_out, dL_drgb.data_ptr(), *sr_out, pre_flags))
+        else:
+            _native.check("gsr_preprocess_backward", L.gsr_preprocess_backward(
+                *pre, col_out, *geo_out, _ptr(dL_dsh), *sr_out, pre_flags))
         if debug:
             torch.cuda.synchronize(dev)
     if persist:  # both halves are enqueued: in stream order the table is all zero again
@@ -668,11 +624,9 @@ def apply_weights(background, means3D, weights, opacity, scales, rotations, scal
         raise RuntimeError("apply_weights: weights must hold P*C and cnt P elements")
     _on_device(weights, "weights", dev, torch.float32)
     _on_device(cnt, "cnt", dev, torch.int32)
-    means3D, opacity = _f32(means3D, "means3D"), _f32(opacity, "opacity", dev)
-    viewmatrix, projmatrix = _f32(viewmatrix, "viewmatrix", dev), _f32(projmatrix, "projmatrix", dev)
-    scales, rotations, cov3D_precomp = (_f32(scales, "scales", dev), _f32(rotations, "rotations", dev),
-                                        _f32(cov3D_precomp, "cov3D_precomp", dev))
-    image_weights = _f32(image_weights, "image_weights", dev)
+    means3D, opacity, viewmatrix, projmatrix, scales, rotations, cov3D_precomp, image_weights = _f32_all(
+        dev, means3D=means3D, opacity=opacity, viewmatrix=viewmatrix, projmatrix=projmatrix, scales=scales,
+        rotations=rotations, cov3D_precomp=cov3D_precomp, image_weights=image_weights)
     w_work = weights if weights.is_contiguous() else weights.contiguous()
     c_work = cnt if cnt.is_contiguous() else cnt.contiguous()
     radii = torch.empty((P,), dtype=torch.int32, device=dev)

@@ -107,59 +107,48 @@ class _RasterizeGaussians(torch.autograd.Function):
     def backward(ctx, grad_out_color, grad_radii, grad_depth, *grad_rest):  # (grad_rest: of aux and / or alpha, in that order)
         # grad_radii is ignored exactly as in the reference (:137, :155-177); so is grad_depth -- depth is a forward-only
         # output -- unless this render ran with FLAG_DEPTH_GRAD (gaussianeditor_amd.set_depth_grad)
-        rs = ctx.raster_settings
         (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
          imgBuffer) = ctx.saved_tensors
-        depth_grad = _depth_grad(ctx.gsr_flags, grad_depth)
-        alpha_grad = grad_rest[-1] if ctx.gsr_alpha else None
-        abs_grad = _abs_grad_out(ctx.gsr_flags, means3D)
-        if grad_out_color is None:  # only the depth and / or alpha output was used downstream
-            grad_out_color = torch.zeros((3, rs.image_height, rs.image_width), dtype=torch.float32, device=means3D.device)
-        # argument order of _C.rasterize_gaussians_backward (rasterize_points.h:38-60)
-        args = (rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
-                rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, sh, rs.sh_degree, rs.campos,
-                geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer, rs.debug)
-        (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
-         grad_rotations) = _call_native(
-             lambda *a: _C.rasterize_gaussians_backward(*a, flags=ctx.gsr_flags,
-                                                        grad_allocator=getattr(ctx, "gsr_grad_allocator", None),
-                                                        **_depth_kw(depth_grad), **_abs_kw(abs_grad),
-                                                        **_alpha_kw(alpha_grad)),
-             args, rs.debug, "snapshot_bw.dump",
-             "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
-        if abs_grad is not None:
-            ctx.gsr_means2D.absgrad = abs_grad
-        # one slot per forward() input (:213-225)
-        return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
-                grad_cov3Ds_precomp, None, None, None)
+        return _backward(ctx, (means3D, sh, colors_precomp, scales, rotations, cov3Ds_precomp),
+                         (ctx.num_rendered, radii, geomBuffer, binningBuffer, imgBuffer),
+                         (grad_out_color, grad_depth, grad_rest[-1] if ctx.gsr_alpha else None), dump=True,
+                         grad_allocator=getattr(ctx, "gsr_grad_allocator", None))
 
 
-def _depth_grad(flags, grad_depth):
-    """The depth image's gradient a backward passes on: only for a render that ran with FLAG_DEPTH_GRAD."""
-    return grad_depth if (flags & _options.FLAG_DEPTH_GRAD) and grad_depth is not None else None
-
-
-def _depth_kw(depth_grad):
-    # (the keyword only where there is a depth gradient: without one the call is today's, to any `_C` backend)
-    return {} if depth_grad is None else {"dL_dout_depth": depth_grad}
-
-
-def _abs_grad_out(flags, means3D):
-    """The tensor a backward fills with the absolute screen-space gradient (and then assigns to `means2D.absgrad`): a new
-    (P,3) one per backward of a render that ran with FLAG_ABS_GRAD (gaussianeditor_amd.set_abs_grad), None otherwise."""
-    if not flags & _options.FLAG_ABS_GRAD:
-        return None
-    return torch.empty((means3D.shape[0], 3), dtype=torch.float32, device=means3D.device)
-
-
-def _abs_kw(abs_grad):
-    # (the keyword only under the flag, as _depth_kw: any `_C` backend without it keeps working with the flag off)
-    return {} if abs_grad is None else {"abs_grad_out": abs_grad}
-
-
-def _alpha_kw(alpha_grad):
-    # (the keyword only where the alpha image was returned AND used: every other backward is today's call, to any `_C` backend)
-    return {} if alpha_grad is None else {"dL_dout_alpha": alpha_grad}
+def _backward(ctx, inputs, state, grads, dump=False, **route_kw):
+    """The backward of both autograd functions: _C.rasterize_gaussians_backward on `inputs` (means3D, sh, colors_precomp, scales,
+    rotations, cov3Ds_precomp) and the `state` their forward left (num_rendered, radii, geomBuffer, binningBuffer, imgBuffer),
+    with `grads`, the gradients of the colour, depth and alpha outputs -> one gradient slot per forward() input (:213-225).
+    The extension keywords are passed only where there is something to pass -- a depth gradient of a render that ran with
+    FLAG_DEPTH_GRAD (depth is a forward-only output otherwise), the tensor for the absolute screen-space gradient under
+    FLAG_ABS_GRAD (a new (P,3) one per backward, assigned to `means2D.absgrad`), a gradient of an alpha image that was
+    returned AND used; `route_kw` likewise -- so that every other backward is the reference's call, to any `_C` backend."""
+    rs, flags = ctx.raster_settings, ctx.gsr_flags
+    means3D, sh, colors_precomp, scales, rotations, cov3Ds_precomp = inputs
+    num_rendered, radii, geomBuffer, binningBuffer, imgBuffer = state
+    grad_out_color, grad_depth, grad_alpha = grads
+    kw = dict(route_kw, flags=flags)
+    if (flags & _options.FLAG_DEPTH_GRAD) and grad_depth is not None:
+        kw["dL_dout_depth"] = grad_depth
+    abs_grad = None
+    if flags & _options.FLAG_ABS_GRAD:
+        abs_grad = kw["abs_grad_out"] = torch.empty((means3D.shape[0], 3), dtype=torch.float32, device=means3D.device)
+    if grad_alpha is not None:
+        kw["dL_dout_alpha"] = grad_alpha
+    if grad_out_color is None:  # only the depth and / or alpha output was used downstream
+        grad_out_color = torch.zeros((3, rs.image_height, rs.image_width), dtype=torch.float32, device=means3D.device)
+    # argument order of _C.rasterize_gaussians_backward (rasterize_points.h:38-60)
+    args = (rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
+            rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, sh, rs.sh_degree, rs.campos,
+            geomBuffer, num_rendered, binningBuffer, imgBuffer, rs.debug)
+    (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
+     grad_rotations) = _call_native(
+         lambda *a: _C.rasterize_gaussians_backward(*a, **kw), args, rs.debug and dump, "snapshot_bw.dump",
+         "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
+    if abs_grad is not None:
+        ctx.gsr_means2D.absgrad = abs_grad
+    return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
+            grad_cov3Ds_precomp, None, None, None)
 
 
 class _ReusedRender(torch.autograd.Function):
@@ -193,25 +182,11 @@ class _ReusedRender(torch.autograd.Function):
     def backward(ctx, grad_out_color, grad_radii, grad_depth, grad_alpha=None):
         rs, flags = ctx.raster_settings, ctx.gsr_flags
         means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp = ctx.saved_tensors
-        depth_grad = _depth_grad(flags, grad_depth)
-        alpha_grad = grad_alpha if ctx.gsr_alpha else None
-        abs_grad = _abs_grad_out(flags, means3D)
-        if grad_out_color is None:
-            grad_out_color = torch.zeros((3, rs.image_height, rs.image_width), dtype=torch.float32, device=means3D.device)
         fwd = _C.rasterize_gaussians(rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier,
                                      cov3Ds_precomp, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height,
                                      rs.image_width, sh, rs.sh_degree, rs.campos, rs.prefiltered, rs.debug, flags=flags)
-        num_rendered, _, _, radii, geomBuffer, binningBuffer, imgBuffer = fwd
-        (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
-         grad_rotations) = _C.rasterize_gaussians_backward(
-             rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix,
-             rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, sh, rs.sh_degree, rs.campos, geomBuffer, num_rendered,
-             binningBuffer, imgBuffer, rs.debug, flags=flags, **_depth_kw(depth_grad), **_abs_kw(abs_grad),
-             **_alpha_kw(alpha_grad))
-        if abs_grad is not None:
-            ctx.gsr_means2D.absgrad = abs_grad
-        return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
-                grad_cov3Ds_precomp, None, None, None)
+        return _backward(ctx, (means3D, sh, colors_precomp, scales, rotations, cov3Ds_precomp), (fwd[0], *fwd[3:]),
+                         (grad_out_color, grad_depth, grad_alpha if ctx.gsr_alpha else None))
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
