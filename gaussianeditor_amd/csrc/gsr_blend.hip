@@ -20,8 +20,9 @@
 //     the four quadrants of a tile are consecutive items of ONE queue, so they gather the same
 //     Gaussians through the same 4 MiB L2.  Which wave runs an item never affects results;
 //   * the backward runs one 4-wave workgroup per tile: the quadrant waves reduce the 9 per-Gaussian gradient terms of
-//     four entries at a time across their 64 lanes (two v_permlane32_swap, one v_permlane16_swap, four row_shr DPP adds),
-//     add their totals into a per-chunk LDS accumulator (double-buffered by chunk parity: one workgroup barrier per chunk),
+//     four entries at a time across their 64 lanes (wave_sum4_pack: the 36 values are packed pairwise, by selects and DPP
+//     adds inside the rows and three lane swaps across them, until every lane holds one total), add their totals with one
+//     ds_add_f32 into a per-chunk LDS accumulator (double-buffered by chunk parity: one workgroup barrier per chunk),
 //     and ONE global atomic per (tile, instance, term) leaves the CU -- the reference issues one per pixel.
 #include <limits.h>
 
@@ -199,8 +200,8 @@ constexpr int GROUP = 4;  // survivors processed per inner-loop iteration
 // Sums each of four per-lane values over the 64 lanes of the wave, 10 instructions for all four
 // instead of 4 x 6: two v_permlane32_swap + adds fold the half-waves (a,c | b,d), one
 // v_permlane16_swap + add folds row pairs so that row r of the wave holds 16 partial sums of
-// value r, then 4 row_shr DPP adds finish each row.  The total of value r ends up in lane 16 r + 15.
-__device__ __forceinline__ float wave_sum4_to_rows(float a, float b, float c, float d) {
+// value r (wave_fold4_to_rows), then 4 row_shr DPP adds finish each row.  The total of value r ends up in lane 16 r + 15.
+__device__ __forceinline__ float wave_fold4_to_rows(float a, float b, float c, float d) {
   unsigned ua = __builtin_bit_cast(unsigned, a), ub = __builtin_bit_cast(unsigned, b);
   unsigned uc = __builtin_bit_cast(unsigned, c), ud = __builtin_bit_cast(unsigned, d);
   {
@@ -221,13 +222,147 @@ __device__ __forceinline__ float wave_sum4_to_rows(float a, float b, float c, fl
     ux = r[0];
     uy = r[1];
   }
-  float z = __builtin_bit_cast(float, ux) + __builtin_bit_cast(float, uy);  // rows: a, b, c, d
+  return __builtin_bit_cast(float, ux) + __builtin_bit_cast(float, uy);  // rows: a, b, c, d
+}
+__device__ __forceinline__ float wave_sum4_to_rows(float a, float b, float c, float d) {
+  float z = wave_fold4_to_rows(a, b, c, d);
   z = dpp_add<0x111>(z);
   z = dpp_add<0x112>(z);
   z = dpp_add<0x114>(z);
   z = dpp_add<0x118>(z);
   return z;
 }
+
+// The same for NM values per entry at once (K7: the raw moments), PACKED: a reduction that finishes one total per register
+// leaves 63 of its 64 lanes unused, and the v_permlane*_swap that the transposed form spends on every value are the
+// expensive instructions of K7's group body (about 10 cycles of a SIMD each against 2 for a DPP add or a select,
+// profiles/r07_a_packed_reduction.md).  Here the 4 NM registers are PAIRED at every distance: a lane keeps the first
+// register of a pair if its bit of that distance is clear and the second if it is set, and one add takes the same register
+// from the lane that differs in that bit (which kept the other one); a register without a partner adds its own other half.
+// Six stages halve 4 NM registers to one:
+//   inside a row, distances 8, 4, 2, 1: two selects and one DPP add per pair -- row_ror:8 (lane ^ 8), row_half_mirror
+//   (7 - lane inside the 8-lane half: flips bit 2 and stays inside the half, which row_ror:4 does not), quad_perm [2,3,0,1]
+//   (lane ^ 2), quad_perm [1,0,3,2] (lane ^ 1);
+//   across the rows, 32 and 16: one v_permlane32_swap / v_permlane16_swap and one add per pair, no select (the swap itself
+//   leaves the first register's two halves in the lower lanes and the second's in the upper ones).
+// For NM = 9: 36 -> 18 -> 9 -> 5 -> 3 -> 2 -> 1 registers, 35 DPP adds, 66 selects and 3 swaps where one chain per value
+// took 36 DPP adds and 27 swaps.  Afterwards lane i holds the complete wave total of ONE value, pack_lanes<NM>() says which.
+template <int S> struct PackStage {
+  static_assert(S == 8 || S == 4 || S == 2 || S == 1 || S == 32 || S == 16, "distances inside a wave");
+  static constexpr int ctrl = S == 8 ? 0x128 : S == 4 ? 0x141 : S == 2 ? 0x4E : 0xB1;
+  static constexpr int partner(int lane) { return S == 4 ? lane ^ 7 : lane ^ S; }
+  static constexpr bool second(int lane) { return (lane & S) != 0; }
+};
+template <int S, int N>
+__device__ __forceinline__ void pack_stage(float* z, int lane) {
+  if constexpr (S >= 16) {
+    auto fold = [](float a, float b) __attribute__((always_inline)) {
+      const unsigned ua = __builtin_bit_cast(unsigned, a), ub = __builtin_bit_cast(unsigned, b);
+      // (the two results go through scalars: __builtin_bit_cast applied to r[1] itself reads r[0] with this compiler)
+      if constexpr (S == 32) {
+        auto r = __builtin_amdgcn_permlane32_swap(ua, ub, false, false);  // [a_lo | b_lo], [a_hi | b_hi]
+        const unsigned r0 = r[0], r1 = r[1];
+        return __builtin_bit_cast(float, r0) + __builtin_bit_cast(float, r1);
+      } else {
+        auto r = __builtin_amdgcn_permlane16_swap(ua, ub, false, false);  // rows [a0, b0, a2, b2], [a1, b1, a3, b3]
+        const unsigned r0 = r[0], r1 = r[1];
+        return __builtin_bit_cast(float, r0) + __builtin_bit_cast(float, r1);
+      }
+    };
+#pragma unroll
+    for (int p = 0; p < N / 2; ++p) z[p] = fold(z[2 * p], z[2 * p + 1]);
+    if (N & 1) z[N / 2] = fold(z[N - 1], z[N - 1]);
+  } else {
+    auto other = [](float x) __attribute__((always_inline)) {  // folds into the add: v_add_f32_dpp
+      return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), PackStage<S>::ctrl, 0xf, 0xf, true));
+    };
+    const bool second = (lane & S) != 0;
+#pragma unroll
+    for (int p = 0; p < N / 2; ++p) {
+      const float a = z[2 * p], b = z[2 * p + 1];
+      const float keep = second ? b : a, give = second ? a : b;
+      z[p] = keep + other(give);
+    }
+    if (N & 1) z[N / 2] = z[N - 1] + other(z[N - 1]);
+  }
+}
+template <int NM>
+__device__ __forceinline__ float wave_sum4_pack(const float (&v)[NM][GROUP]) {
+  static_assert(GROUP == 4 && NM >= 1 && NM <= 16, "4 NM values, at most one per lane");
+  const int lane = lane_id();
+  constexpr int N0 = NM * GROUP, N1 = (N0 + 1) / 2, N2 = (N1 + 1) / 2, N3 = (N2 + 1) / 2, N4 = (N3 + 1) / 2, N5 = (N4 + 1) / 2;
+  static_assert((N5 + 1) / 2 == 1, "six halvings leave one register");
+  float z[N0];  // value k of entry u: register GROUP k + u -- the first two stages fold the four entries of a value
+#pragma unroll
+  for (int k = 0; k < NM; ++k)
+#pragma unroll
+    for (int u = 0; u < GROUP; ++u) z[GROUP * k + u] = v[k][u];
+  pack_stage<8, N0>(z, lane);
+  pack_stage<4, N1>(z, lane);
+  pack_stage<2, N2>(z, lane);
+  pack_stage<1, N3>(z, lane);
+  pack_stage<32, N4>(z, lane);
+  pack_stage<16, N5>(z, lane);
+  return z[0];
+}
+// Which value a lane ends up with: the same pairing, run on indices.  ok = false if a stage would add two different values
+// (the lane an add reads from must have kept the same register) -- the static_asserts below rule that out.
+//   adds: the lanes that add their total to the accumulators -- of the lanes that hold the same value, the lowest;
+//   term_bit / entry_bit: bit planes over the lanes of the value's index k and of its entry u.
+struct PackLanes {
+  uint64_t adds, term_bit[4], entry_bit[2];
+  int value[WAVE];
+  bool ok;
+};
+template <int NM>
+constexpr PackLanes pack_lanes() {
+  constexpr int N0 = NM * GROUP;
+  PackLanes m = {};
+  int t[N0][WAVE] = {};
+  for (int k = 0; k < N0; ++k)
+    for (int i = 0; i < WAVE; ++i) t[k][i] = k;
+  int n = N0;
+  auto stage = [&](auto part, auto second) {
+    for (int p = 0; p < n / 2; ++p) {
+      int out[WAVE] = {};
+      for (int i = 0; i < WAVE; ++i) {
+        out[i] = second(i) ? t[2 * p + 1][i] : t[2 * p][i];
+        if ((second(i) ? t[2 * p + 1][part(i)] : t[2 * p][part(i)]) != out[i]) return false;
+      }
+      for (int i = 0; i < WAVE; ++i) t[p][i] = out[i];
+    }
+    if (n & 1)
+      for (int i = 0; i < WAVE; ++i) {
+        if (t[n - 1][part(i)] != t[n - 1][i]) return false;
+        t[n / 2][i] = t[n - 1][i];
+      }
+    n = (n + 1) / 2;
+    return true;
+  };
+  m.ok = stage(PackStage<8>::partner, PackStage<8>::second) && stage(PackStage<4>::partner, PackStage<4>::second) &&
+         stage(PackStage<2>::partner, PackStage<2>::second) && stage(PackStage<1>::partner, PackStage<1>::second) &&
+         stage(PackStage<32>::partner, PackStage<32>::second) && stage(PackStage<16>::partner, PackStage<16>::second) && n == 1;
+  uint64_t seen = 0;  // (4 NM <= 64 values)
+  for (int i = 0; i < WAVE; ++i) {
+    const int val = t[0][i];
+    m.value[i] = val;
+    if (val < 0 || val >= N0) {
+      m.ok = false;
+      continue;
+    }
+    if (!((seen >> val) & 1ull)) m.adds |= 1ull << i;
+    seen |= 1ull << val;
+    for (int b = 0; b < 4; ++b) m.term_bit[b] |= (uint64_t)(((val / GROUP) >> b) & 1) << i;
+    for (int b = 0; b < 2; ++b) m.entry_bit[b] |= (uint64_t)(((val % GROUP) >> b) & 1) << i;
+  }
+  m.ok = m.ok && seen == (N0 == 64 ? ~0ull : (1ull << N0) - 1ull) && __builtin_popcountll(m.adds) == N0;
+  return m;
+}
+static_assert(pack_lanes<9>().ok && pack_lanes<10>().ok && pack_lanes<11>().ok && pack_lanes<12>().ok && pack_lanes<13>().ok,
+              "every moment of every entry, for every K7 row width, reaches a lane");
+static_assert(pack_lanes<9>().value[0] == 0 && pack_lanes<9>().value[8] == 1 && pack_lanes<9>().value[4] == 2 &&
+                  pack_lanes<9>().value[2] == GROUP && pack_lanes<9>().value[16] == 8 * GROUP,
+              "nine moments: lane bits 3, 2 pick the entry, bits 1, 0, 5 the moment 0 .. 7, bit 4 the ninth");
 
 struct Entry {
   uint32_t id;
@@ -719,7 +854,8 @@ __device__ __forceinline__ void wave_lds_sync() {
 constexpr int BWD_WAVES = 4;  // one workgroup = the four quadrants of one tile (or two quadrants of a heavy one)
 constexpr int ACC_LDS_ROW = 9;  // floats per chunk slot of the backward's LDS accumulators: the nine raw moments
 // ... of a DEPTH backward (gsr_blend_backward_depth): ten raw moments (the tenth: alpha T dL_ddepth) in rows of 11 floats
-// (odd, as 9: the slots of the tail's four ds_add lanes and the four rows of a flush instruction spread over the banks)
+// (odd, as 9: the rows of the tail's ds_add -- up to four slots, two per 32-lane half -- and the four rows of a flush
+// instruction spread over the banks)
 // ... of an ABS backward (GSR_FLAG_ABS_GRAD): two more raw moments behind those, |A qx + B qy| and |B qx + C qy|, in rows of
 // 11 floats, with DEPTH 13 (odd again)
 template <bool DEPTH, bool ABS = false> constexpr int bwd_moments() { return (DEPTH ? 10 : 9) + (ABS ? 2 : 0); }
@@ -775,6 +911,14 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
   constexpr int NM = bwd_moments<DEPTH, ABS>();  // raw moments per entry
   constexpr int IABS = bwd_moments<DEPTH>();     // (ABS) index of the first of the two absolute moments
   const int w = (int)(threadIdx.x >> 6), lane = lane_id();
+  // the group loop's tail (wave_sum4_pack): the moment, and the entry of the group, whose total this lane ends up with, and
+  // whether it is the lane that adds it
+  constexpr PackLanes tail = pack_lanes<NM>();
+  auto tail_bit = [lane](uint64_t plane) __attribute__((always_inline)) { return (uint32_t)(plane >> (uint32_t)lane) & 1u; };
+  const uint32_t tail_term = tail_bit(tail.term_bit[0]) | tail_bit(tail.term_bit[1]) << 1 | tail_bit(tail.term_bit[2]) << 2 |
+                             tail_bit(tail.term_bit[3]) << 3;
+  const uint32_t tail_entry = tail_bit(tail.entry_bit[0]) | tail_bit(tail.entry_bit[1]) << 1;
+  const bool tail_adds = tail_bit(tail.adds) != 0u;
   // The item's descriptor (assembled by the caller from three scalar loads): x = code -- a whole tile, wave w = quadrant w; or
   // half a tile, waves (0,1) and (2,3) = the upper / lower 8x4 pixels of its two quadrants; or one list segment --, y = first
   // position of the tile's list, z = how deep the item's pixels reach into it (the forward's work_maxc).  Until round 4 an
@@ -1042,21 +1186,16 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
           }
         }
       }
-      // 4-entry transposed wave reduction: afterwards lane 15 of row r holds the wave totals of entry j + r and adds the
-      // nine RAW moments to the tile-level accumulator of the entry's chunk slot (they are relative to the entry's own
-      // mean, so the quadrants' sums simply add; the flush turns them into the reference's terms).
-      float tot[NM];
-#pragma unroll
-      for (int k = 0; k < NM; ++k)
-        tot[k] = wave_sum4_to_rows(v[k][0], v[k][1], v[k][2], v[k][3]);
-      // keep the reductions whole in front of the 4-lane tail: otherwise the last row_shr step is sunk into the masked
-      // region as v_mov 0 + v_mov_dpp + v_add (3 instructions per term instead of one v_add_f32_dpp)
-#pragma unroll
-      for (int k = 0; k < NM; ++k) asm volatile("" : "+v"(tot[k]));
-      if ((lane & 15) == 15) {
-        const uint32_t my_slot = __float_as_uint(s2[w][j + (uint32_t)(lane >> 4)].w);
-#pragma unroll
-        for (int k = 0; k < NM; ++k) atomicAdd(&sacc[cb][my_slot][k], tot[k]);
+      // 4-entry packed wave reduction: afterwards a lane holds the wave total of moment tail_term of entry j + tail_entry,
+      // and ONE ds_add_f32 (the lowest lane of every total, 4 NM lanes) adds the RAW moments to the tile-level
+      // accumulator of the entry's chunk slot (they are relative to the entry's own mean, so the quadrants' sums simply
+      // add; the flush turns them into the reference's terms).  A null entry adds zeros to slot 0.
+      float tot = wave_sum4_pack<NM>(v);
+      // (keeps the reduction whole in front of the masked tail)
+      asm volatile("" : "+v"(tot));
+      if (tail_adds) {
+        const uint32_t my_slot = __float_as_uint(s2[w][j + tail_entry].w);
+        atomicAdd(&sacc[cb][my_slot][tail_term], tot);
       }
     }
     __syncthreads();  // (B) every quadrant's contribution to this chunk is in sacc[cb]

@@ -20,7 +20,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 OUT = os.path.join(ROOT, "build_variants")
-KERNEL = "_ZN3gsr21blend_backward_kernelILb0ELb0ELb0EEEvNS_9BlendArgsE"
+KERNEL = "_ZN3gsr21blend_backward_kernelILb0ELb0ELb0ELb0ELb0EEEvNS_9BlendArgsE"
 FLAGS = ("--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -munsafe-fp-atomics -fno-gpu-rdc -fno-slp-vectorize "
          "-fvisibility=hidden -mllvm -amdgpu-sched-strategy=max-ilp -mllvm -amdgpu-atomic-optimizer-strategy=None").split()
 
@@ -70,8 +70,9 @@ def clean(lines, variant):
         op = t.split()[0]
         if op in ("s_cbranch_vccz", "s_cbranch_vccnz", "s_cbranch_execz", "s_cbranch_execnz", "s_cbranch_scc1", "s_cbranch_scc0", "s_branch"):
             continue  # straight line: every group is evaluated in full, the masked tail included
-        if op == "v_add_u32_e32" and t.replace(" ", "").startswith("v_add_u32_e32v2,64,v2"):
-            t = "v_add_u32_e32 v2, 0, v2"  # (the LDS cursor of the loop: stays on the first group's records)
+        m = re.match(r"v_add_u32_e32 (v\d+), 64, \1$", t)
+        if m:
+            t = f"v_add_u32_e32 {m.group(1)}, 0, {m.group(1)}"  # (the LDS cursor of the loop: stays on the first group's records)
         if variant in ("nolds", "noxlane"):
             if op.startswith("ds_"):
                 continue
@@ -83,6 +84,22 @@ def clean(lines, variant):
             continue  # (no vector memory in the replay)
         out.append(t)
     return out
+
+
+def packed_lanes(nm=9, group=4):
+    """wave_sum4_pack's lane map (pack_lanes<NM>, gsr_blend.hip), emulated: -> (mask of the lanes that add, [moment of lane])."""
+    t = [[k] * 64 for k in range(nm * group)]
+    for s in (8, 4, 2, 1, 32, 16):
+        out = [[(b if i & s else a)[i] for i in range(64)] for a, b in zip(t[0::2], t[1::2])]
+        t = out + ([t[-1]] if len(t) & 1 else [])
+    assert len(t) == 1
+    seen, mask = set(), 0
+    for i, val in enumerate(t[0]):
+        if val not in seen:
+            mask |= 1 << i
+        seen.add(val)
+    assert len(seen) == nm * group
+    return mask, [val // group for val in t[0]]
 
 
 def registers(body):
@@ -113,9 +130,21 @@ def emit(isa: str) -> str:
         n_valu = sum(1 for t in body if t.startswith("v_"))
         n_salu = sum(1 for t in body if t.startswith("s_") and not t.startswith("s_waitcnt"))
         n_lds = sum(1 for t in body if t.startswith("ds_"))
-        init = [f"v_mov_b32 v{r}, 0" for r in v] + [f"s_mov_b32 s{r}, 0" for r in s if r not in (8, 9)]
-        # s[8:9]: the lanes that own a row total (lane & 15 == 15), what the masked tail runs under
-        init += ["s_mov_b32 s8, 0x80008000", "s_mov_b32 s9, 0x80008000", f"s_mov_b32 s{cnt}, %0"]
+        init = [f"v_mov_b32 v{r}, 0" for r in v] + [f"s_mov_b32 s{r}, 0" for r in s]
+        # what the masked tail runs under (the operand of its s_and_saveexec_b64): the lanes that add a total -- lane 15 of every
+        # row with one row_shr chain per moment, the lowest lane of every total with the packed reduction (told by its
+        # row_ror:8)
+        tail = next(re.match(r"s_and_saveexec_b64 s\[\d+:\d+\], s\[(\d+):(\d+)\]", t) for t in body if t.startswith("s_and_saveexec_b64"))
+        packed = any("row_ror:8" in t for t in variants["full"])
+        mask, term = packed_lanes() if packed else (0x8000800080008000, None)
+        init += [f"s_mov_b32 s{tail.group(1)}, {mask & 0xffffffff:#x}", f"s_mov_b32 s{tail.group(2)}, {mask >> 32:#x}", f"s_mov_b32 s{cnt}, %0"]
+        if packed:
+            # the lane's own share of the add's address, 4 x its moment: the addend of the v_mad_u64_u32 in front of the single
+            # ds_add_f32.  (All four entries of the replayed group are null records, slot 0: the four lanes of a moment add to
+            # one address, as the four row ends of the unpacked form do.)
+            mad = next(re.match(r"v_mad_u64_u32 v\[\d+:\d+\], s\[\d+:\d+\], v\d+, \d+, v\[(\d+):\d+\]", t) for t in variants["full"]
+                       if t.startswith("v_mad_u64_u32"))
+            init += [f"v_writelane_b32 v{mad.group(1)}, {4 * k}, {i}" for i, k in enumerate(term)]
         text = init + [f"K7R_{name}_%=:"] + body + [f"s_sub_u32 s{cnt}, s{cnt}, 1", f"s_cmp_lg_u32 s{cnt}, 0", f"s_cbranch_scc1 K7R_{name}_%="]
         asm = "\n".join(f'      "{t}\\n"' for t in text)
         clob = ", ".join([f'"v{r}"' for r in v] + [f'"s{r}"' for r in s] + [f'"s{cnt}"', '"vcc"', '"scc"', '"memory"'])
