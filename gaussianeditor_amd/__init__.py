@@ -123,6 +123,26 @@ def get_alpha_output() -> bool:
     return bool(options.default_flags() & options.FLAG_ALPHA_OUT)
 
 
+def set_pose_grad(on: bool) -> None:
+    """Opt-in: the default of FLAG_POSE_GRAD (options.py; a bit of the binding, the library has none) -- the camera becomes
+    a differentiable input.  A render whose `viewmatrix`, `projmatrix` or `campos` (`world_view_transform`,
+    `full_proj_transform`, `camera_center` of the camera `render()` is given) requires a gradient returns, from its
+    backward, the raw partial derivative with respect to each of the three, and autograd carries them on through whatever
+    torch code built the tensors from a pose (`gaussianeditor_amd.pose.camera_tensors`).  Gaussians may be frozen: a
+    pose-only optimisation works.  Off (default), or with a camera that requires no gradient: every render is the call it
+    always was, and a camera that does require one silently gets none, as in the reference."""
+    from . import options
+
+    f = options.default_flags() & ~options.FLAG_POSE_GRAD
+    options.set_default_flags(f | (options.FLAG_POSE_GRAD if on else 0))
+
+
+def get_pose_grad() -> bool:
+    from . import options
+
+    return bool(options.default_flags() & options.FLAG_POSE_GRAD)
+
+
 def set_antialiasing(on: bool) -> None:
     """Opt-in: the default of GSR_FLAG_ANTIALIAS (include/gsr.h) -- the opacity-compensated 2D filter of antialiased
     3DGS rasterizers.  Every Gaussian is blended with opacity * h, h = sqrt(max(2.5e-5, det(S) / det(S + 0.3 I))) of its

@@ -74,6 +74,11 @@ SIGNATURES = {
                                    c_uint]),
     # absolute screen-space gradients (GSR_FLAG_ABS_GRAD), between the two halves: (stream, P, acc, touched, absgrad (P,3))
     "gsr_abs_grad_take": (c_int, [_P, c_int, _P, _P, _P]),
+    # the camera gradient, between the two halves: (P, bytes); (stream, P, D, M, W, H, means3D, scales, scale_modifier,
+    # rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom, acc, workspace, pose_grad[35], flags)
+    "gsr_pose_workspace_size": (c_int, [c_int, POINTER(c_size_t)]),
+    "gsr_pose_backward": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_float, _P, _P, _P, _P, _P, c_float, c_float,
+                                  _P, _P, _P, _P, _P, c_uint]),
     # alpha image: (stream, W, H, image, out_alpha (1,H,W)); its backward: gsr_blend_backward with dL_ddepth | NULL and
     # dL_dalpha (1,H,W) behind dL_dpix
     "gsr_alpha_image": (c_int, [_P, c_int, c_int, _P, _P]),

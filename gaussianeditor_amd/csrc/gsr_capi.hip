@@ -689,6 +689,50 @@ int gsr_abs_grad_take(void* stream, int P, float* acc, const uint8_t* touched, f
   return GSR_OK;
 }
 
+int gsr_pose_workspace_size(int P, size_t* bytes) {
+  if (P < 0 || !bytes) return GSR_ERR_BAD_ARGUMENT;
+  *bytes = sizeof(float) * POSE_SUMS_PAD * (size_t)pose_blocks(P);
+  return GSR_OK;
+}
+
+int gsr_pose_backward(void* stream, int P, int D, int M, int W, int H, const float* means3D, const float* scales,
+                      float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                      const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy, const int32_t* radii,
+                      const void* geom, const float* acc, void* workspace, float* pose_grad, unsigned flags) {
+  if (flags & ~(GSR_FLAG_DEPTH_GRAD | GSR_FLAG_ANTIALIAS)) return GSR_ERR_BAD_ARGUMENT;
+  if (P < 0 || !pose_grad || ((uintptr_t)pose_grad & 3u)) return GSR_ERR_BAD_ARGUMENT;
+  if (P == 0) {  // no Gaussian, no term
+    GSR_HIP(hipMemsetAsync(pose_grad, 0, sizeof(float) * POSE_OUT, (hipStream_t)stream));
+    return GSR_OK;
+  }
+  if (W <= 0 || H <= 0 || D < 0 || D > 3 || M < 0 || (M > 0 && M < (D + 1) * (D + 1))) return GSR_ERR_BAD_ARGUMENT;
+  if (!means3D || !viewmatrix || !projmatrix || !radii || !geom || misaligned(geom)) return GSR_ERR_BAD_ARGUMENT;
+  if (M > 0 && !campos) return GSR_ERR_BAD_ARGUMENT;
+  // this geometry state was left by gsr_preprocess(GSR_FLAG_FORWARD_ONLY): Geom::dcol was never written (as K8+K9 refuses it)
+  if (M > 0 && geom_is_forward_only(geom)) return GSR_ERR_BAD_ARGUMENT;
+  if (!acc || ((uintptr_t)acc & 63u) || !workspace || ((uintptr_t)workspace & 15u)) return GSR_ERR_BAD_ARGUMENT;
+  if (!cov3D_precomp && (!scales || !rotations)) return GSR_ERR_BAD_ARGUMENT;
+  const Geom g = carve_geom(const_cast<void*>(geom), P);
+  PoseArgs pa;
+  pa.P = P; pa.D = D; pa.sh = M > 0 ? 1 : 0;
+  pa.scale_modifier = scale_modifier;
+  pa.means3D = means3D; pa.radii = radii;
+  pa.scales = cov3D_precomp ? nullptr : scales; pa.rotations = cov3D_precomp ? nullptr : rotations;
+  pa.cov3D_precomp = cov3D_precomp;
+  pa.viewmatrix = viewmatrix; pa.projmatrix = projmatrix; pa.campos = campos;
+  pa.h_y = H / (2.0f * tan_fovy);  // (as preprocess_backward_impl)
+  pa.h_x = W / (2.0f * tan_fovx);
+  pa.tan_fovx = tan_fovx; pa.tan_fovy = tan_fovy;
+  pa.acc = acc;
+  pa.clamped = g.clamped;
+  for (int i = 0; i < 3; ++i) pa.dcol[i] = g.dcol[i];
+  pa.rec0 = (flags & GSR_FLAG_ANTIALIAS) ? g.rec0 : nullptr;
+  pa.partials = static_cast<float*>(workspace);
+  GSR_HIP(launch_pose_backward((hipStream_t)stream, pa, (flags & GSR_FLAG_DEPTH_GRAD) != 0, (flags & GSR_FLAG_ANTIALIAS) != 0,
+                               pose_grad));
+  return GSR_OK;
+}
+
 int gsr_blend_backward(void* stream, int P, int64_t R, int W, int H, const float* bg, const void* geom,
                        const void* binning, const void* image, const float* dL_dpix, float* acc, uint8_t* touched,
                        unsigned flags) {

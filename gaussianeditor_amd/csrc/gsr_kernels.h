@@ -201,4 +201,115 @@ hipError_t launch_abs_grad_take(hipStream_t s, int P, float* acc, const uint8_t*
 hipError_t launch_alpha_image(hipStream_t s, int W, int H, const float* final_T, float* out_alpha);
 hipError_t launch_trace_weights(hipStream_t s, BlendArgs a);
 
+// The camera gradient (pose_backward_kernel, gsr_pose.hip): between K7 and K8+K9, from the accumulator rows K7 left
+struct PoseArgs {
+  int P, D;
+  int sh;                      // the view's colours came from SHs (campos is read, dL/dcampos can be non-zero); 0: colors_precomp
+  float scale_modifier;
+  const float* means3D;
+  const int32_t* radii;
+  const float* scales;         // with rotations, or null: then cov3D_precomp
+  const float* rotations;
+  const float* cov3D_precomp;
+  const float* viewmatrix;
+  const float* projmatrix;
+  const float* campos;
+  float h_x, h_y, tan_fovx, tan_fovy;
+  const float* acc;            // (P, ACC_ROW), read only
+  const uint8_t* clamped;      // Geom::clamped
+  const float* dcol[3];        // Geom::dcol
+  const float4* rec0;          // Geom::rec0 (AA: opacity * h in .w) | null
+  float* partials;             // (blocks, POSE_SUMS_PAD): one row of partial sums per block, fully written
+};
+constexpr int POSE_SUMS = 27;       // 12 dL/dviewmatrix[:, :3] + 12 dL/dprojmatrix[:, (0, 1, 3)] + 3 dL/dcampos
+constexpr int POSE_SUMS_PAD = 32;
+constexpr int POSE_MAX_BLOCKS = 1024;
+constexpr int POSE_OUT = 35;        // viewmatrix 16, projmatrix 16, campos 3
+inline int pose_blocks(int P) {
+  const int nb = (P + GAUSS_BLOCK - 1) / GAUSS_BLOCK;
+  return nb < 1 ? 1 : (nb > POSE_MAX_BLOCKS ? POSE_MAX_BLOCKS : nb);
+}
+hipError_t launch_pose_backward(hipStream_t s, const PoseArgs& a, bool depth, bool antialias, float* pose_grad);
+
+#if defined(__HIPCC__)
+// ----------------------------------------------------------------------------------
+// Device helpers of the per-Gaussian kernels (gsr_preprocess.hip: K1, K8+K9; gsr_pose.hip: the camera gradient), here so
+// that both translation units evaluate the covariance chain with the same operations.
+// ----------------------------------------------------------------------------------
+// glm::mat3 semantics (column-major m[col][row]; product evaluated left to right),
+// DGR/third_party/glm/glm/detail/type_mat3x3.inl:486-519.
+struct M3 {
+  float m[3][3];
+};
+__device__ __forceinline__ M3 mk(float a, float b, float c, float d, float e, float f, float g, float h, float i) {
+  M3 r;
+  r.m[0][0] = a; r.m[0][1] = b; r.m[0][2] = c;
+  r.m[1][0] = d; r.m[1][1] = e; r.m[1][2] = f;
+  r.m[2][0] = g; r.m[2][1] = h; r.m[2][2] = i;
+  return r;
+}
+__device__ __forceinline__ M3 mul(const M3& A, const M3& B) {
+  M3 R;
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int r = 0; r < 3; ++r) R.m[c][r] = A.m[0][r] * B.m[c][0] + A.m[1][r] * B.m[c][1] + A.m[2][r] * B.m[c][2];
+  return R;
+}
+__device__ __forceinline__ M3 tr(const M3& A) {
+  M3 R;
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int r = 0; r < 3; ++r) R.m[c][r] = A.m[r][c];
+  return R;
+}
+
+struct Cam {
+  float view[16];
+  float proj[16];
+  float campos[3];
+};
+
+__device__ __forceinline__ void load_cam(Cam& c, const float* view, const float* proj, const float* campos) {
+  // 35 uniform floats: the compiler turns these into scalar (s_load) loads.
+#pragma unroll
+  for (int i = 0; i < 16; ++i) c.view[i] = view[i];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) c.proj[i] = proj[i];
+  if (campos) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) c.campos[i] = campos[i];
+  }
+}
+
+struct V3 {
+  float x, y, z;
+};
+__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
+__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ V3 operator*(float s, V3 a) { return {s * a.x, s * a.y, s * a.z}; }
+__device__ __forceinline__ V3 operator*(V3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
+__device__ __forceinline__ float dot3(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+
+// computeCov3D, forward.cu:118-152: Sigma = (S R)^T (S R), upper triangle.  Used by K1 and again by K8+K9 -- the reference
+// keeps the six floats in its geometry buffer between the passes (rasterizer_impl.cu:225, 388); recomputing them from
+// the 28 bytes of scale and rotation the backward reads anyway saves a 24-byte store and a 24-byte load per Gaussian.
+__device__ __forceinline__ void cov3d_from_values(float s0, float s1, float s2, float scale_modifier, const float4& q,
+                                                  float (&c3)[6]) {
+  M3 S = mk(1, 0, 0, 0, 1, 0, 0, 0, 1);
+  S.m[0][0] = scale_modifier * s0;
+  S.m[1][1] = scale_modifier * s1;
+  S.m[2][2] = scale_modifier * s2;
+  const float r = q.x, x = q.y, y = q.z, z = q.w;
+  const M3 R = mk(1.f - 2.f * (y * y + z * z), 2.f * (x * y - r * z), 2.f * (x * z + r * y),
+                  2.f * (x * y + r * z), 1.f - 2.f * (x * x + z * z), 2.f * (y * z - r * x),
+                  2.f * (x * z - r * y), 2.f * (y * z + r * x), 1.f - 2.f * (x * x + y * y));
+  const M3 Mm = mul(S, R);
+  const M3 Sigma = mul(tr(Mm), Mm);
+  c3[0] = Sigma.m[0][0]; c3[1] = Sigma.m[0][1]; c3[2] = Sigma.m[0][2];
+  c3[3] = Sigma.m[1][1]; c3[4] = Sigma.m[1][2]; c3[5] = Sigma.m[2][2];
+}
+#endif  // __HIPCC__
+
 }  // namespace gsr

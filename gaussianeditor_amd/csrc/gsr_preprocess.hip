@@ -10,58 +10,11 @@
 
 namespace gsr {
 
-// glm::mat3 semantics (column-major m[col][row]; product evaluated left to right),
-// DGR/third_party/glm/glm/detail/type_mat3x3.inl:486-519.
-struct M3 {
-  float m[3][3];
-};
-__device__ __forceinline__ M3 mk(float a, float b, float c, float d, float e, float f, float g, float h, float i) {
-  M3 r;
-  r.m[0][0] = a; r.m[0][1] = b; r.m[0][2] = c;
-  r.m[1][0] = d; r.m[1][1] = e; r.m[1][2] = f;
-  r.m[2][0] = g; r.m[2][1] = h; r.m[2][2] = i;
-  return r;
-}
-__device__ __forceinline__ M3 mul(const M3& A, const M3& B) {
-  M3 R;
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-#pragma unroll
-    for (int r = 0; r < 3; ++r) R.m[c][r] = A.m[0][r] * B.m[c][0] + A.m[1][r] * B.m[c][1] + A.m[2][r] * B.m[c][2];
-  return R;
-}
-__device__ __forceinline__ M3 tr(const M3& A) {
-  M3 R;
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-#pragma unroll
-    for (int r = 0; r < 3; ++r) R.m[c][r] = A.m[r][c];
-  return R;
-}
-
 __device__ __forceinline__ int f2i_sat(float v) {
   if (!(v == v)) return 0;
   if (v >= 2147483648.0f) return 2147483647;
   if (v <= -2147483648.0f) return (-2147483647 - 1);
   return (int)v;
-}
-
-struct Cam {
-  float view[16];
-  float proj[16];
-  float campos[3];
-};
-
-__device__ __forceinline__ void load_cam(Cam& c, const float* view, const float* proj, const float* campos) {
-  // 35 uniform floats: the compiler turns these into scalar (s_load) loads.
-#pragma unroll
-  for (int i = 0; i < 16; ++i) c.view[i] = view[i];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) c.proj[i] = proj[i];
-  if (campos) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) c.campos[i] = campos[i];
-  }
 }
 
 __device__ __forceinline__ void get_rect(float px, float py, int max_radius, int gx, int gy, uint32_t& minx,
@@ -81,15 +34,6 @@ __device__ constexpr float SH_C2[5] = {1.0925484305920792f, -1.0925484305920792f
 __device__ constexpr float SH_C3[7] = {-0.5900435899266435f, 2.890611442640554f,  -0.4570457994644658f,
                                        0.3731763325901154f,  -0.4570457994644658f, 1.445305721320277f,
                                        -0.5900435899266435f};
-
-struct V3 {
-  float x, y, z;
-};
-__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 operator*(float s, V3 a) { return {s * a.x, s * a.y, s * a.z}; }
-__device__ __forceinline__ V3 operator*(V3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
-__device__ __forceinline__ float dot3(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 
 // Loads the SH coefficients of one Gaussian into registers.  M == 16 (the standard 3DGS ply) is a
 // 192-byte, 16-byte-aligned record read with dwordx4 loads.  All loads of a degree are issued
@@ -133,24 +77,6 @@ __device__ __forceinline__ void load_sh(const float* __restrict__ shs, size_t id
   }
 }
 
-// computeCov3D, forward.cu:118-152: Sigma = (S R)^T (S R), upper triangle.  Used by K1 and again by K8+K9 -- the reference
-// keeps the six floats in its geometry buffer between the passes (rasterizer_impl.cu:225, 388); recomputing them from
-// the 28 bytes of scale and rotation the backward reads anyway saves a 24-byte store and a 24-byte load per Gaussian.
-__device__ __forceinline__ void cov3d_from_values(float s0, float s1, float s2, float scale_modifier, const float4& q,
-                                                  float (&c3)[6]) {
-  M3 S = mk(1, 0, 0, 0, 1, 0, 0, 0, 1);
-  S.m[0][0] = scale_modifier * s0;
-  S.m[1][1] = scale_modifier * s1;
-  S.m[2][2] = scale_modifier * s2;
-  const float r = q.x, x = q.y, y = q.z, z = q.w;
-  const M3 R = mk(1.f - 2.f * (y * y + z * z), 2.f * (x * y - r * z), 2.f * (x * z + r * y),
-                  2.f * (x * y + r * z), 1.f - 2.f * (x * x + z * z), 2.f * (y * z - r * x),
-                  2.f * (x * z - r * y), 2.f * (y * z + r * x), 1.f - 2.f * (x * x + y * y));
-  const M3 Mm = mul(S, R);
-  const M3 Sigma = mul(tr(Mm), Mm);
-  c3[0] = Sigma.m[0][0]; c3[1] = Sigma.m[0][1]; c3[2] = Sigma.m[0][2];
-  c3[3] = Sigma.m[1][1]; c3[4] = Sigma.m[1][2]; c3[5] = Sigma.m[2][2];
-}
 __device__ __forceinline__ void cov3d_from_scale_rot(const float* __restrict__ scales, float scale_modifier,
                                                      const float* __restrict__ rotations, int idx, float (&c3)[6]) {
   cov3d_from_values(scales[3 * idx + 0], scales[3 * idx + 1], scales[3 * idx + 2], scale_modifier,

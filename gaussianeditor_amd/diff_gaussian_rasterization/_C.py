@@ -38,9 +38,10 @@ def attach_grad_allocator(output: torch.Tensor, fn) -> None:
 def _flags(flags) -> int:
     # (FLAG_DEPTH_GRAD never reaches the library as a bit: a backward with a depth gradient calls the _depth entry points;
     #  FLAG_ABS_GRAD only from a backward that was given `abs_grad_out`, and then only to its blend half; FLAG_ALPHA_OUT
-    #  never: the library has no such bit, alpha_image / `dL_dout_alpha` say what is asked)
+    #  never: the library has no such bit, alpha_image / `dL_dout_alpha` say what is asked; FLAG_POSE_GRAD likewise:
+    #  `pose_grad_out` says it)
     return (options.current_flags() if flags is None else int(flags)) & ~(options.FLAG_DEPTH_GRAD | options.FLAG_ABS_GRAD
-                                                                          | options.FLAG_ALPHA_OUT)
+                                                                          | options.FLAG_ALPHA_OUT | options.FLAG_POSE_GRAD)
 
 
 def _require_cuda(t: torch.Tensor, name: str) -> None:
@@ -313,7 +314,7 @@ def _alloc(fn, name: str, shape, zero: bool, dev) -> torch.Tensor:
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
                                  viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
                                  geomBuffer, R, binningBuffer, imageBuffer, debug, flags=None, grad_allocator=None,
-                                 dL_dout_depth=None, abs_grad_out=None, dL_dout_alpha=None):
+                                 dL_dout_depth=None, abs_grad_out=None, dL_dout_alpha=None, pose_grad_out=None):
     """RasterizeGaussiansBackwardCUDA, rasterize_points.cu:97-157 ->
     (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D | None, dL_dsh, dL_dscales, dL_drotations).
     `flags` (extension, keyword): the flags the forward of this view ran with; None = options.current_flags().
@@ -342,6 +343,11 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     `dL_dout_alpha` (extension, keyword): (1,H,W) float32 gradient of the alpha image (alpha_image()), or None.  Given, the
     blend half is gsr_blend_backward_alpha (with `dL_dout_depth` too, if that is given); the K8+K9 half is the one the
     route uses without it.
+    `pose_grad_out` (extension, keyword): a contiguous (35,) float32 tensor on the device of `means3D`, or None.  Given, it is
+    fully written with the camera gradient -- dL/dviewmatrix (16), dL/dprojmatrix (16), dL/dcampos (3), include/gsr.h:
+    gsr_pose_backward -- between the backward's two halves, after gsr_abs_grad_take; the eight returned gradients are what
+    they are without it, and a backward without it makes exactly the calls it made before the keyword existed.  Not with the
+    "row_state" mode.
     Every backward is issued as its two halves (a blend half, then a K8+K9 half), never through the fused gsr_backward."""
     flags = _flags(flags)
     dev = means3D.device
@@ -362,9 +368,18 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
             raise RuntimeError(f"diff_gaussian_rasterization: `abs_grad_out` must be a contiguous ({P}, 3) tensor, got "
                                f"{tuple(abs_grad_out.shape)}")
         _same_device(abs_grad_out, "abs_grad_out", dev)
+    if pose_grad_out is not None:
+        if not isinstance(pose_grad_out, torch.Tensor) or pose_grad_out.dtype != torch.float32:
+            raise RuntimeError("diff_gaussian_rasterization: `pose_grad_out` must be a float32 tensor")
+        if tuple(pose_grad_out.shape) != (35,) or not pose_grad_out.is_contiguous():
+            raise RuntimeError("diff_gaussian_rasterization: `pose_grad_out` must be a contiguous (35,) tensor, got "
+                               f"{tuple(pose_grad_out.shape)}")
+        _same_device(pose_grad_out, "pose_grad_out", dev)
     H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
     M = int(sh.size(1)) if sh.size(0) != 0 else 0
     if P == 0:
+        if pose_grad_out is not None:
+            pose_grad_out.zero_()
         z = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)  # noqa: E731
         return z(0, 3), z(0, NUM_CHANNELS), z(0, 1), z(0, 3), z(0, 6), z(0, M, 3), z(0, 3), z(0, 4)
     _require_cuda(means3D, "means3D")
@@ -417,6 +432,9 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     if row_state is not None and dL_ddepth is not None:
         raise RuntimeError("diff_gaussian_rasterization: depth gradients are not supported with persistent gradient rows "
                            "(the grad_allocator's \"row_state\" mode)")
+    if row_state is not None and pose_grad_out is not None:
+        raise RuntimeError("diff_gaussian_rasterization: camera gradients are not supported with persistent gradient rows "
+                           "(the grad_allocator's \"row_state\" mode)")
     # Which table?  The one kept across backwards on this stream: zero on entry, zeroed again by K8+K9 -- no clear (nobody reads
     # the table between K7 and K8+K9: the exchange routes plan their messages from K7's `touched` mask, handed to
     # after_blend_backward).  With an allocator's own table or persistent rows: a table cleared by K7's own launch.
@@ -460,6 +478,16 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
         if abs_grad_out is not None:  # moves the two columns out of the table (and zeroes them) in front of K8+K9
             _native.check("gsr_abs_grad_take", L.gsr_abs_grad_take(_stream(dev), P, acc.data_ptr(), touched.data_ptr(),
                                                                    abs_grad_out.data_ptr()))
+        if pose_grad_out is not None:  # reads the rows K7 left, in front of K8+K9 (which may clean them); changes nothing
+            nbytes = ctypes.c_size_t(0)
+            _native.check("gsr_pose_workspace_size", L.gsr_pose_workspace_size(P, ctypes.byref(nbytes)))
+            pose_ws = torch.empty((int(nbytes.value),), dtype=torch.uint8, device=dev)
+            _native.check("gsr_pose_backward", L.gsr_pose_backward(
+                _stream(dev), P, int(degree), M, W, H, means3D.data_ptr(), _ptr(scales), float(scale_modifier), _ptr(rotations),
+                _ptr(cov3D_precomp), viewmatrix.data_ptr(), projmatrix.data_ptr(), _ptr(campos) if M != 0 else None,
+                float(tan_fovx), float(tan_fovy), radii.data_ptr(), geomBuffer.data_ptr(), acc.data_ptr(), pose_ws.data_ptr(),
+                pose_grad_out.data_ptr(),
+                (options.FLAG_DEPTH_GRAD if dL_ddepth is not None else 0) | (flags & options.FLAG_ANTIALIAS)))
         if dL_drgb is not None:
             # notification (no allocation): K7 is enqueued, K8+K9 not yet -- multiview.py starts the exchange of the
             # touched-row counts here (from K7's row mask), so that it and the host's wait for it run underneath K8+K9

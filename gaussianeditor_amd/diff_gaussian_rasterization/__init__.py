@@ -62,7 +62,9 @@ def _call_native(fn, args, debug: bool, dump_path: str, message: str):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, aux_colors=None, return_alpha=False):
+                raster_settings, aux_colors=None, return_alpha=False, viewmatrix=None, projmatrix=None, campos=None):
+        # (viewmatrix, projmatrix, campos: rs.viewmatrix / rs.projmatrix / rs.campos once more, as inputs autograd can see --
+        #  passed under FLAG_POSE_GRAD only, and only when one of them requires a gradient: _pose_inputs)
         rs = raster_settings
         # behaviour flags (include/gsr.h: GSR_FLAG_*) are fixed per render: read once here, reused by the backward
         flags = _options.current_flags()
@@ -79,6 +81,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             "\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
         ctx.raster_settings = rs
         ctx.gsr_flags = flags
+        ctx.gsr_pose = viewmatrix is not None
         ctx.num_rendered = num_rendered
         if flags & _options.FLAG_ABS_GRAD:
             ctx.gsr_means2D = means2D  # the caller's screen-space tensor: the backward assigns its `.absgrad`
@@ -128,6 +131,9 @@ def _backward(ctx, inputs, state, grads, dump=False, **route_kw):
     num_rendered, radii, geomBuffer, binningBuffer, imgBuffer = state
     grad_out_color, grad_depth, grad_alpha = grads
     kw = dict(route_kw, flags=flags)
+    pose = None
+    if getattr(ctx, "gsr_pose", False):  # the camera tensors were inputs of this render (FLAG_POSE_GRAD)
+        pose = kw["pose_grad_out"] = torch.empty((35,), dtype=torch.float32, device=means3D.device)
     if (flags & _options.FLAG_DEPTH_GRAD) and grad_depth is not None:
         kw["dL_dout_depth"] = grad_depth
     abs_grad = None
@@ -147,8 +153,14 @@ def _backward(ctx, inputs, state, grads, dump=False, **route_kw):
          "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
     if abs_grad is not None:
         ctx.gsr_means2D.absgrad = abs_grad
-    return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
-            grad_cov3Ds_precomp, None, None, None)
+    out = (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
+           grad_cov3Ds_precomp, None, None, None)
+    if pose is None:
+        return out
+    # three more slots, in the layout of the tensors themselves; None for one that does not require a gradient
+    need = ctx.needs_input_grad[11:14]
+    parts = ((pose[:16], rs.viewmatrix), (pose[16:32], rs.projmatrix), (pose[32:], rs.campos))
+    return out + tuple(g.reshape(t.shape) if n else None for (g, t), n in zip(parts, need))
 
 
 class _ReusedRender(torch.autograd.Function):
@@ -189,11 +201,28 @@ class _ReusedRender(torch.autograd.Function):
                          (grad_out_color, grad_depth, grad_alpha if ctx.gsr_alpha else None))
 
 
+def _pose_inputs(rs):
+    """The camera tensors as trailing inputs of `_RasterizeGaussians.apply` -- under FLAG_POSE_GRAD
+    (gaussianeditor_amd.set_pose_grad) and only when one of them requires a gradient; () otherwise, so that every other
+    render is the call it always was.  (Inside a NamedTuple autograd does not see them: a camera built from a learnable
+    pose renders correctly and gets no gradient.)"""
+    if not (_options.current_flags() & _options.FLAG_POSE_GRAD):
+        return ()
+    cams = (rs.viewmatrix, rs.projmatrix, rs.campos)
+    if not any(isinstance(t, torch.Tensor) and t.requires_grad for t in cams):
+        return ()
+    return cams
+
+
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings, return_alpha=False):
     # (return_alpha: the alpha image as an additional last value; the extra arguments only then, so that a call without it
     #  is the call it always was)
     with_alpha = (True,) if return_alpha else ()
+    pose = _pose_inputs(raster_settings)
+    if pose:  # (a render whose camera takes a gradient is never served from a remembered state: it runs in full)
+        return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                         cov3Ds_precomp, raster_settings, None, bool(return_alpha), *pose)
     if colors_precomp.numel() != 0 and sh.numel() == 0 and means3D.is_cuda:
         # a colour-override render: is it the view the rasterizer rendered last (the reference's second render() of every
         # training view / GUI frame)?  Then the blend kernel alone, on that render's state (_reuse.py)
@@ -209,6 +238,10 @@ def rasterize_gaussians_with_aux(means3D, means2D, sh, colors_precomp, opacities
                                  raster_settings, aux_colors, return_alpha=False):
     """rasterize_gaussians plus a second image blended with `aux_colors` (P,3): (color, radii, depth, aux_color), with
     `return_alpha` (color, radii, depth, aux_color, alpha)."""
+    pose = _pose_inputs(raster_settings)
+    if pose:
+        return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                         cov3Ds_precomp, raster_settings, aux_colors, bool(return_alpha), *pose)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                                      cov3Ds_precomp, raster_settings, aux_colors, *((True,) if return_alpha else ()))
 

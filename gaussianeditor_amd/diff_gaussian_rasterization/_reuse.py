@@ -99,7 +99,8 @@ _ROLES = ("means3D", "scales", "rotations", "opacities", "cov3D_precomp", "viewm
 #: the opacities the geometry state holds, so a render under it and one without it never serve each other)
 _IGNORED_FLAGS = (_options.FLAG_FORWARD_ONLY | _options.FLAG_CLEAR_GRADS | _options.FLAG_SHARED_SIMDS
                   | _options.FLAG_DEPTH_GRAD | _options.FLAG_ABS_GRAD  # (read by the backward alone)
-                  | _options.FLAG_ALPHA_OUT)  # (read by render() alone: the alpha image comes out of the state as it is)
+                  | _options.FLAG_ALPHA_OUT  # (read by render() alone: the alpha image comes out of the state as it is)
+                  | _options.FLAG_POSE_GRAD)  # (read by the Python layer alone; a render whose camera takes a gradient never looks up)
 
 
 def _key(rs, flags, means3D):

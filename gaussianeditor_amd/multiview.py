@@ -305,7 +305,9 @@ def render_view_grads(settings: GaussianRasterizationSettings, means3D, opacitie
     pixel gradient.  Returns (color, radii, depth, grads) where grads has the six
     rasterizer-input gradients (views of `bucket` when one is given).  `after_forward(radii)` is called between the
     forward and the backward (multiview_step starts the radii's MAX all-reduce there, so that it overlaps the backward).
-    The depth image takes no gradient on this route, whatever gaussianeditor_amd.set_depth_grad says."""
+    The depth image takes no gradient on this route, whatever gaussianeditor_amd.set_depth_grad says; nor does the camera,
+    whatever gaussianeditor_amd.set_pose_grad says: the routes of this module return the six gradients of the Gaussians and
+    exchange nothing else."""
     state = _view_forward(settings, means3D, opacities, shs, scales, rotations)
     color, radii, depth, _ = state
     if after_forward is not None:

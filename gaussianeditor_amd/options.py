@@ -17,8 +17,13 @@ FLAG_DEPTH_GRAD = 64     # the backward also differentiates the depth image (rea
 FLAG_ANTIALIAS = 1024    # opacity-compensated 2D filter: opacity * sqrt(det(Sigma) / det(Sigma + 0.3 I)) (include/gsr.h)
 FLAG_ABS_GRAD = 4096     # the backward also leaves the absolute screen-space gradient, means2D.absgrad (read by the backward only)
 FLAG_ALPHA_OUT = 16384   # render() also returns the alpha image, out["alpha"] (read by render() alone: the library never sees it)
+# the backward also returns the gradient of rs.viewmatrix / rs.projmatrix / rs.campos where they require one (read by the
+# rasterizer's Python layer alone: the library never sees it).  The next free bit: 32768 stays refused, as the alpha
+# output's checks pin it.
+FLAG_POSE_GRAD = 65536
 # the behaviour switches a caller may set
-FLAG_ALL = FLAG_TILE_BOUNDS_ALPHA | FLAG_FAST_EXP | FLAG_DEPTH_GRAD | FLAG_ANTIALIAS | FLAG_ABS_GRAD | FLAG_ALPHA_OUT
+FLAG_ALL = (FLAG_TILE_BOUNDS_ALPHA | FLAG_FAST_EXP | FLAG_DEPTH_GRAD | FLAG_ANTIALIAS | FLAG_ABS_GRAD | FLAG_ALPHA_OUT
+            | FLAG_POSE_GRAD)
 FLAG_CLEAR_GRADS = 4     # (internal to the binding: the backward clears its accumulators itself; include/gsr.h)
 FLAG_FORWARD_ONLY = 8    # (internal to the binding: a render none of whose inputs requires a gradient)
 FLAG_SHARED_SIMDS = 16   # (set by multiview_batch_step for a rank's pipelined views: 2 persistent blend waves per SIMD)

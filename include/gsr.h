@@ -68,7 +68,8 @@ extern "C" {
  * likewise additive: gsr_loss_workspace_size, gsr_photometric_loss_forward and gsr_photometric_loss_backward (the fused
  * L1 + SSIM loss; nothing of the rasterizer changed).  Then, likewise additive: gsr_densify_stats,
  * gsr_densify_workspace_size, gsr_densify_select, gsr_densify_plans, gsr_densify_split_xyz and gsr_densify_keep (the
- * densification policy; nothing existing changed). */
+ * densification policy; nothing existing changed).  Then, likewise additive: gsr_pose_workspace_size and gsr_pose_backward
+ * (the camera gradient; no new flag bit, nothing existing changed). */
 #define GSR_ABI_VERSION 6
 /* The blend backward's accumulator table: GSR_ACC_ROW floats (one 64-byte line) per Gaussian, 64-byte aligned.  Columns:
  *   [GSR_ACC_MEAN2D] .x [+1] .y of dL_dmean2D      (backward.cu:545-546)
@@ -356,6 +357,37 @@ int gsr_backward_depth(void* stream, int P, int D, int M, int64_t R, int W, int 
  * backward without the flag leaves, so K8+K9 -- whichever entry point, GSR_FLAG_ACC_SELF_CLEAN included -- runs unchanged.
  * acc: 64-byte aligned, as for gsr_blend_backward.  P == 0 is an empty call. */
 int gsr_abs_grad_take(void* stream, int P, float* acc, const uint8_t* touched, float* absgrad);
+
+/* Camera gradient (opt-in; no flag bit: the call says what is asked): the raw partial derivatives of the loss with respect
+ * to the view's three camera tensors, each in the tensor's own layout.  Called after the blend backward of the view (and
+ * after gsr_abs_grad_take, if that is called) and BEFORE its K8+K9 entry point, on the same stream: it reads the
+ * accumulator rows, which K8+K9 may clean, and changes nothing in them -- the K8+K9 call that follows runs unchanged.
+ *   pose_grad[0..15]   dL/dviewmatrix (4,4): the view matrix enters through the view-space mean (which feeds the Jacobian
+ *                      J), through its rotation block in T = W J and, under GSR_FLAG_DEPTH_GRAD, through the depth; only
+ *                      [:, :3] can be non-zero, column 3 is written as exact zeros
+ *   pose_grad[16..31]  dL/dprojmatrix (4,4): enters through p_hom = (mean, 1) projmatrix and ndc = p_hom.xy / (p_hom.w +
+ *                      1e-7); columns 0, 1 and 3 can be non-zero, column 2 is written as exact zeros
+ *   pose_grad[32..34]  dL/dcampos (3): enters through the view direction of the SH colour only -- minus the sum over the
+ *                      Gaussians of the dnormvdv term K8+K9 adds to dL_dmeans3D; exact zeros with M == 0
+ * Conventions: those of K8+K9 (the reference's analytic backward) -- off-cone tx / ty are constants, the alpha clamp is
+ * straight-through, under GSR_FLAG_ANTIALIAS the opacity factor is differentiated through the covariance.  A caller composes
+ * the three with whatever built the tensors (full_proj = view @ projection, campos = inverse(view)[3, :3]).
+ * Only Gaussians with radii > 0 and a row that is not zero contribute.  No float atomics: per-block partial sums in
+ * `workspace`, added in a fixed order in double -- the same accumulator table gives the same 35 floats, bit for bit.
+ *   M          SH coefficients per Gaussian the view's forward was given, 0 = it was given colors_precomp (campos may
+ *              then be NULL and is not read)
+ *   geom       the geometry state of the view's gsr_preprocess; with M > 0 one left by GSR_FLAG_FORWARD_ONLY is refused
+ *              (GSR_ERR_BAD_ARGUMENT), as K8+K9 refuses it
+ *   acc        the table the blend backward of the view added into, 64-byte aligned; read only
+ *   workspace  gsr_pose_workspace_size(P) bytes, 16-byte aligned, the caller's; contents on entry are irrelevant
+ *   flags      0 | GSR_FLAG_DEPTH_GRAD (the blend backward was given dL_ddepth: column GSR_ACC_DEPTH is read)
+ *              | GSR_FLAG_ANTIALIAS (the view's flag); any other bit is GSR_ERR_BAD_ARGUMENT
+ * All 35 floats are written whatever is visible; P == 0 writes 35 zeros.  Arguments are checked before any device work. */
+int gsr_pose_workspace_size(int P, size_t* bytes);
+int gsr_pose_backward(void* stream, int P, int D, int M, int W, int H, const float* means3D, const float* scales,
+                      float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                      const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy, const int32_t* radii,
+                      const void* geom, const float* acc, void* workspace, float* pose_grad, unsigned flags);
 
 /* Alpha image (accumulated opacity, opt-in; no flag bit: the pointers say what is asked).
  * gsr_alpha_image: out_alpha (1,H,W) = 1 - final_T of the image state a gsr_blend_forward left (every forward that is not
