@@ -1722,31 +1722,51 @@ static int forward_split(unsigned grid, unsigned quads, bool for_backward) {
   if (for_backward) return quads > grid ? 1 : (4u * quads > grid ? 2 : 4);
   return quads >= 2u * grid ? 1 : (quads >= grid ? 2 : 4);
 }
+// What the three persistent launches share: the grid in workgroups of `waves_per_wg` waves (handed back), the queue's
+// cursors and the placement units.
+static inline __attribute__((always_inline)) hipError_t persistent_launch(hipStream_t s, BlendArgs& a, unsigned waves_per_wg, unsigned* grid) {
+  *grid = blend_grid_size(s, a.shared_simds != 0) / waves_per_wg;
+  a.units = (int)blend_units(waves_per_wg, *grid, s);
+  return prepare_queue(s, a, *grid);
+}
+// Run-time choices as the compile-time arguments of a generic lambda: with_constants(f, fast, OneOf<1, 2, 4>{split}) calls
+// f(std::bool_constant<fast>{}, std::integral_constant<int, split>{}); an int that is none of the listed values: no call.
+template <int... Vs> struct OneOf { int v; };
+template <class F> static void with_constants(F f) { f(); }
+template <class F, class... Rest> static void with_constants(F f, bool v, Rest... rest);
+template <class F, int V, int... Vs, class... Rest> static void with_constants(F f, OneOf<V, Vs...> o, Rest... rest) {
+  if (o.v == V) with_constants([&](auto... c) { f(std::integral_constant<int, V>{}, c...); }, rest...);
+  else if constexpr (sizeof...(Vs) != 0) with_constants(f, OneOf<Vs...>{o.v}, rest...);
+}
+template <class F, class... Rest> static void with_constants(F f, bool v, Rest... rest) {
+  if (v) with_constants([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+  else with_constants([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+// Which instantiations of the kernel families are built: the launchers below pick a kernel under these and nowhere else, and
+// a call whose choices name none gets hipErrorInvalidValue.  K12 is built for every C, cut and exp mode its launcher lists.
+// K6: the profiled kernel in one form; an auxiliary render leaves no checkpoints.
+constexpr bool forward_exists(bool PROFILE, bool AUX, int SPLIT, bool FAST, bool CKPT) {
+  return PROFILE ? !AUX && SPLIT == 1 && !FAST && !CKPT : !(AUX && CKPT);
+}
+// K7: a depth backward walks no list segments (the checkpoints hold no depth behind a segment, backward_tile).
+constexpr bool backward_exists(bool FAST, bool SEG, bool DEPTH, bool ABS, bool ALPHA) { return !(SEG && DEPTH); }
+
 hipError_t launch_blend_forward(hipStream_t s, BlendArgs a) {
-  const unsigned grid = blend_grid_size(s, a.shared_simds != 0);
-  hipError_t e = prepare_queue(s, a, grid);
+  unsigned grid;
+  hipError_t e = persistent_launch(s, a, 1, &grid);
   if (e != hipSuccess) return e;
-  a.units = (int)blend_units(1, grid, s);
   const int split = forward_split(grid, 4u * (unsigned)(a.gx * a.gy), a.for_backward != 0);
   const dim3 g(grid), b(WAVE);
-#define GSR_FWD_LAUNCH(AUXV, FASTV, CKV)                                                                        \
-  do {                                                                                                          \
-    if (split == 1) hipLaunchKernelGGL((blend_forward_kernel<false, AUXV, 1, FASTV, CKV>), g, b, 0, s, a);       \
-    else if (split == 2) hipLaunchKernelGGL((blend_forward_kernel<false, AUXV, 2, FASTV, CKV>), g, b, 0, s, a);  \
-    else hipLaunchKernelGGL((blend_forward_kernel<false, AUXV, 4, FASTV, CKV>), g, b, 0, s, a);                  \
-  } while (0)
   // checkpoints for the backward's list segments: where the caller handed the tables over (gsr_capi.hip: checkpoint_chunks)
   const bool ck = a.ck_table != nullptr && a.ck_chunks > 0 && a.colors3 == nullptr && !a.profile;
-  if (a.profile)
-    hipLaunchKernelGGL((blend_forward_kernel<true, false, 1, false, false>), g, b, 0, s, a);
-  else if (a.colors3 != nullptr) {
-    if (a.fast_exp) GSR_FWD_LAUNCH(true, true, false); else GSR_FWD_LAUNCH(true, false, false);
-  } else if (ck) {
-    if (a.fast_exp) GSR_FWD_LAUNCH(false, true, true); else GSR_FWD_LAUNCH(false, false, true);
-  } else {
-    if (a.fast_exp) GSR_FWD_LAUNCH(false, true, false); else GSR_FWD_LAUNCH(false, false, false);
-  }
-#undef GSR_FWD_LAUNCH
+  // (a profiled render: the plain kernel, uncut, whatever else the arguments say)
+  const bool plain = a.profile == nullptr;
+  void (*kernel)(BlendArgs) = nullptr;
+  with_constants([&](auto PROFILE, auto AUX, auto SPLIT, auto FAST, auto CKPT) {
+    if constexpr (forward_exists(PROFILE, AUX, SPLIT, FAST, CKPT)) kernel = blend_forward_kernel<PROFILE, AUX, SPLIT, FAST, CKPT>;
+  }, !plain, plain && a.colors3 != nullptr, OneOf<1, 2, 4>{plain ? split : 1}, plain && a.fast_exp, ck);
+  if (kernel == nullptr) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kernel, g, b, 0, s, a);
   return hipGetLastError();
 }
 // Host-side launch counts of K7 per instantiation (gsr_debug_blend_backward_launches), index FAST | SEG << 1 | DEPTH << 2 |
@@ -1757,10 +1777,9 @@ void blend_backward_launch_counts(uint64_t counts[32]) {
 }
 hipError_t launch_blend_backward(hipStream_t s, BlendArgs a) {
   // #CUs x 4 workgroups of 4 waves: the same 4 waves per SIMD as the forward
-  const unsigned grid = blend_grid_size(s, a.shared_simds != 0) / BWD_WAVES;
-  hipError_t e = prepare_queue(s, a, grid);
+  unsigned grid;
+  hipError_t e = persistent_launch(s, a, BWD_WAVES, &grid);
   if (e != hipSuccess) return e;
-  a.units = (int)blend_units(BWD_WAVES, grid, s);
   bool seg_items = false;  // the work list may hold list-segment items (views whose forward left checkpoints; set below)
   ClearArgs clear = {{nullptr, nullptr, nullptr, nullptr}, {0, 0, 0, 0}};
   if (a.clear_grads) {
@@ -1793,31 +1812,20 @@ hipError_t launch_blend_backward(hipStream_t s, BlendArgs a) {
                          (const uint32_t*)nullptr, (const uint32_t*)nullptr, CkTable{}, 0u, 0);
   }
   const dim3 g(grid), b(WAVE * BWD_WAVES);
-  // (the same conditions as the dispatch below, in its order: DEPTH excludes SEG)
-  const bool depth = a.dL_ddepth != nullptr;
-  g_bwd_launches[(a.fast_exp ? 1 : 0) | (!depth && seg_items ? 2 : 0) | (depth ? 4 : 0) | (a.abs_grad ? 8 : 0) |
-                 (a.dL_dalpha != nullptr ? 16 : 0)].fetch_add(1, std::memory_order_relaxed);
-#define GSR_BWD_LAUNCH2(SEGV, DEPTHV, ABSV, ALPHAV)                                                                   \
-  do {                                                                                                                \
-    if (a.fast_exp) hipLaunchKernelGGL((blend_backward_kernel<true, SEGV, DEPTHV, ABSV, ALPHAV>), g, b, 0, s, a);      \
-    else hipLaunchKernelGGL((blend_backward_kernel<false, SEGV, DEPTHV, ABSV, ALPHAV>), g, b, 0, s, a);                \
-  } while (0)
   // (dL_dalpha: gsr_blend_backward_alpha -- the ALPHA twin of whatever the call would launch without it)
-#define GSR_BWD_LAUNCH(SEGV, DEPTHV, ABSV)                                                                    \
-  do {                                                                                                        \
-    if (a.dL_dalpha != nullptr) GSR_BWD_LAUNCH2(SEGV, DEPTHV, ABSV, true);                                    \
-    else GSR_BWD_LAUNCH2(SEGV, DEPTHV, ABSV, false);                                                          \
-  } while (0)
   // (abs_grad: GSR_FLAG_ABS_GRAD -- the ABS twins of the three routes, nothing else is instantiated)
-  if (a.dL_ddepth != nullptr) {
-    if (a.abs_grad) GSR_BWD_LAUNCH(false, true, true); else GSR_BWD_LAUNCH(false, true, false);
-  } else if (seg_items) {
-    if (a.abs_grad) GSR_BWD_LAUNCH(true, false, true); else GSR_BWD_LAUNCH(true, false, false);
-  } else {
-    if (a.abs_grad) GSR_BWD_LAUNCH(false, false, true); else GSR_BWD_LAUNCH(false, false, false);
-  }
-#undef GSR_BWD_LAUNCH
-#undef GSR_BWD_LAUNCH2
+  void (*kernel)(BlendArgs) = nullptr;
+  int index = 0;
+  with_constants([&](auto FAST, auto SEG, auto DEPTH, auto ABS, auto ALPHA) {
+    if constexpr (backward_exists(FAST, SEG, DEPTH, ABS, ALPHA)) {
+      kernel = blend_backward_kernel<FAST, SEG, DEPTH, ABS, ALPHA>;
+      constexpr int of_kernel = FAST | SEG << 1 | DEPTH << 2 | ABS << 3 | ALPHA << 4;
+      index = of_kernel;
+    }
+  }, a.fast_exp != 0, seg_items, a.dL_ddepth != nullptr, a.abs_grad != 0, a.dL_dalpha != nullptr);
+  if (kernel == nullptr) return hipErrorInvalidValue;
+  g_bwd_launches[index].fetch_add(1, std::memory_order_relaxed);
+  hipLaunchKernelGGL(kernel, g, b, 0, s, a);
   return hipGetLastError();
 }
 // GSR_FLAG_ABS_GRAD: the way of K7's absolute sums out of the accumulator table (gsr_abs_grad_take), between K7 and K8+K9.
@@ -1866,30 +1874,16 @@ hipError_t launch_alpha_image(hipStream_t s, int W, int H, const float* final_T,
   return hipGetLastError();
 }
 hipError_t launch_trace_weights(hipStream_t s, BlendArgs a) {
-  const unsigned grid = blend_grid_size(s, a.shared_simds != 0);
-  hipError_t e = prepare_queue(s, a, grid);
+  unsigned grid;
+  hipError_t e = persistent_launch(s, a, 1, &grid);
   if (e != hipSuccess) return e;
-  a.units = (int)blend_units(1, grid, s);
   const int split = forward_split(grid, 4u * (unsigned)(a.gx * a.gy), false);
   const dim3 g(grid), b(WAVE);
-#define GSR_TRACE_LAUNCH2(CC, FASTV)                                                                    \
-  do {                                                                                                  \
-    if (split == 1) hipLaunchKernelGGL((trace_weights_kernel<CC, 1, FASTV>), g, b, 0, s, a);             \
-    else if (split == 2) hipLaunchKernelGGL((trace_weights_kernel<CC, 2, FASTV>), g, b, 0, s, a);        \
-    else hipLaunchKernelGGL((trace_weights_kernel<CC, 4, FASTV>), g, b, 0, s, a);                        \
-  } while (0)
-#define GSR_TRACE_LAUNCH(CC)                                                         \
-  do {                                                                               \
-    if (a.fast_exp) GSR_TRACE_LAUNCH2(CC, true); else GSR_TRACE_LAUNCH2(CC, false);  \
-  } while (0)
-  switch (a.C) {
-    case 1: GSR_TRACE_LAUNCH(1); break;
-    case 2: GSR_TRACE_LAUNCH(2); break;
-    case 3: GSR_TRACE_LAUNCH(3); break;
-    default: return hipErrorInvalidValue;
-  }
-#undef GSR_TRACE_LAUNCH2
-#undef GSR_TRACE_LAUNCH
+  void (*kernel)(BlendArgs) = nullptr;  // (stays null for a C that is not listed)
+  with_constants([&](auto C, auto SPLIT, auto FAST) { kernel = trace_weights_kernel<C, SPLIT, FAST>; },
+                 OneOf<1, 2, 3>{a.C}, OneOf<1, 2, 4>{split}, a.fast_exp != 0);
+  if (kernel == nullptr) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kernel, g, b, 0, s, a);
   return hipGetLastError();
 }
 

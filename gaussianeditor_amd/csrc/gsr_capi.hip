@@ -315,6 +315,26 @@ inline BlendArgs make_blend_args(int W, int H, const Geom& g, const Binning& b, 
   }
   return a;
 }
+// A view's BlendArgs as the blend and trace entry points start from them: the carves of its three scratch buffers, what
+// make_blend_args takes from them, and the two flags every launch reads.  The entry point then sets what is its own.
+inline BlendArgs view_blend_args(int P, int64_t R, int W, int H, const void* geom, const void* binning, const void* image,
+                                 const float* bg, int queue_kind, unsigned flags) {
+  const Geom g = carve_geom(const_cast<void*>(geom), P);
+  const Binning b = carve_binning_view(binning, R, W, H);
+  const Image im = carve_image(const_cast<void*>(image), W, H);
+  BlendArgs a = make_blend_args(W, H, g, b, im, bg, queue_kind, R);
+  a.fast_exp = (flags & GSR_FLAG_FAST_EXP) ? 1 : 0;
+  a.shared_simds = (flags & GSR_FLAG_SHARED_SIMDS) ? 1 : 0;
+  return a;
+}
+// The auxiliary render: leave everything the backward of the MAIN render reads untouched.
+inline void keep_main_render_state(BlendArgs& a) {
+  a.final_T = nullptr;
+  a.n_contrib = nullptr;
+  a.work_est = nullptr;
+  a.work_maxc = nullptr;
+  a.ck_table = nullptr;
+}
 }  // namespace
 
 extern "C" {
@@ -586,14 +606,9 @@ int gsr_blend_forward(void* stream, int P, int64_t R, int W, int H, const float*
   if (P < 0 || R < 0 || W <= 0 || H <= 0 || !bg || !image || !out_color || !out_depth || (flags & ~VIEW_FLAGS))
     return GSR_ERR_BAD_ARGUMENT;
   if (R > 0 && (!geom || !binning)) return GSR_ERR_BAD_ARGUMENT;
-  const Geom g = carve_geom(const_cast<void*>(geom), P);
-  const Binning b = carve_binning_view(binning, R, W, H);
-  const Image im = carve_image(image, W, H);
-  BlendArgs a = make_blend_args(W, H, g, b, im, bg, 0, R);
+  BlendArgs a = view_blend_args(P, R, W, H, geom, binning, image, bg, 0, flags);
   a.out_color = out_color;
   a.out_depth = out_depth;
-  a.fast_exp = (flags & GSR_FLAG_FAST_EXP) ? 1 : 0;
-  a.shared_simds = (flags & GSR_FLAG_SHARED_SIMDS) ? 1 : 0;
   a.for_backward = (flags & GSR_FLAG_FORWARD_ONLY) ? 0 : 1;
   GSR_HIP(launch_blend_forward((hipStream_t)stream, a));
   return GSR_OK;
@@ -604,21 +619,11 @@ int gsr_blend_forward_aux(void* stream, int P, int64_t R, int W, int H, const fl
                           unsigned flags) {
   if (P < 0 || R < 0 || W <= 0 || H <= 0 || !bg || !image || !out_color || (flags & ~VIEW_FLAGS)) return GSR_ERR_BAD_ARGUMENT;
   if (R > 0 && (!geom || !binning || !colors)) return GSR_ERR_BAD_ARGUMENT;
-  const Geom g = carve_geom(const_cast<void*>(geom), P);
-  const Binning b = carve_binning_view(binning, R, W, H);
-  const Image im = carve_image(image, W, H);
-  BlendArgs a = make_blend_args(W, H, g, b, im, bg, 0, R);
+  BlendArgs a = view_blend_args(P, R, W, H, geom, binning, image, bg, 0, flags);
   a.colors3 = colors;
   a.out_color = out_color;
   a.out_depth = out_depth;
-  // leave everything the backward of the MAIN render reads untouched
-  a.final_T = nullptr;
-  a.n_contrib = nullptr;
-  a.work_est = nullptr;
-  a.work_maxc = nullptr;
-  a.ck_table = nullptr;
-  a.fast_exp = (flags & GSR_FLAG_FAST_EXP) ? 1 : 0;
-  a.shared_simds = (flags & GSR_FLAG_SHARED_SIMDS) ? 1 : 0;
+  keep_main_render_state(a);
   GSR_HIP(launch_blend_forward((hipStream_t)stream, a));
   return GSR_OK;
 }
@@ -632,10 +637,7 @@ int gsr_debug_blend_forward_profile(void* stream, int P, int64_t R, int W, int H
   if (max_records < n) return GSR_ERR_BAD_ARGUMENT;
   if (P < 0 || R < 0 || W <= 0 || H <= 0 || !bg || !image || !out_color || !out_depth) return GSR_ERR_BAD_ARGUMENT;
   if (R > 0 && (!geom || !binning)) return GSR_ERR_BAD_ARGUMENT;
-  const Geom g = carve_geom(const_cast<void*>(geom), P);
-  const Binning b = carve_binning_view(binning, R, W, H);
-  const Image im = carve_image(image, W, H);
-  BlendArgs a = make_blend_args(W, H, g, b, im, bg, 0, R);
+  BlendArgs a = view_blend_args(P, R, W, H, geom, binning, image, bg, 0, 0);  // (the profile entry points take no flags)
   a.out_color = out_color;
   a.out_depth = out_depth;
   a.profile = records;
@@ -664,17 +666,12 @@ static int blend_backward_impl(void* stream, int P, int64_t R, int W, int H, con
   // (the backward's work items carry the tile id in 20 bits, next to the half / segment fields: gsr_blend.hip BWD_ITEM_TILE)
   if ((int64_t)((W + TILE - 1) / TILE) * ((H + TILE - 1) / TILE) > (int64_t)GSR_MAX_TILES) return GSR_ERR_BAD_ARGUMENT;
   if (!bg || !geom || !binning || !image || !dL_dpix) return GSR_ERR_BAD_ARGUMENT;
-  const Geom g = carve_geom(const_cast<void*>(geom), P);
-  const Image im = carve_image(const_cast<void*>(image), W, H);
-  const Binning b = carve_binning_view(binning, R, W, H);
-  BlendArgs a = make_blend_args(W, H, g, b, im, bg, 1, R);
+  BlendArgs a = view_blend_args(P, R, W, H, geom, binning, image, bg, 1, flags);
   a.dL_dpix = dL_dpix;
   a.dL_ddepth = dL_ddepth;
   a.dL_dalpha = dL_dalpha;  // (the slot of out_color, which no backward kernel reads)
   a.acc = acc;
   a.touched = touched;
-  a.fast_exp = (flags & GSR_FLAG_FAST_EXP) ? 1 : 0;
-  a.shared_simds = (flags & GSR_FLAG_SHARED_SIMDS) ? 1 : 0;
   a.P = P;
   a.clear_grads = (flags & GSR_FLAG_CLEAR_GRADS) ? 1 : 0;
   a.abs_grad = (flags & GSR_FLAG_ABS_GRAD) ? 1 : 0;
@@ -823,10 +820,7 @@ int gsr_debug_blend_backward_profile(void* stream, int P, int64_t R, int W, int 
   if (max_records < n) return GSR_ERR_BAD_ARGUMENT;
   if (P < 0 || R <= 0 || W <= 0 || H <= 0 || !bg || !geom || !binning || !image || !dL_dpix) return GSR_ERR_BAD_ARGUMENT;
   if (!acc || ((uintptr_t)acc & 63u)) return GSR_ERR_BAD_ARGUMENT;
-  const Geom g = carve_geom(const_cast<void*>(geom), P);
-  const Binning b = carve_binning_view(binning, R, W, H);
-  const Image im = carve_image(const_cast<void*>(image), W, H);
-  BlendArgs a = make_blend_args(W, H, g, b, im, bg, 1, R);
+  BlendArgs a = view_blend_args(P, R, W, H, geom, binning, image, bg, 1, 0);  // (no flags, as the forward's)
   a.dL_dpix = dL_dpix;
   a.acc = acc;
   a.profile = records;
@@ -1049,16 +1043,11 @@ int gsr_trace_weights(void* stream, int P, int64_t R, int W, int H, int C, const
   if (P < 0 || R < 0 || W <= 0 || H <= 0 || !image || !image_weights || !weights || !cnt) return GSR_ERR_BAD_ARGUMENT;
   if (R == 0) return GSR_OK;
   if (!geom || !binning) return GSR_ERR_BAD_ARGUMENT;
-  const Geom g = carve_geom(const_cast<void*>(geom), P);
-  const Binning b = carve_binning_view(binning, R, W, H);
-  const Image im = carve_image(const_cast<void*>(image), W, H);
-  BlendArgs a = make_blend_args(W, H, g, b, im, nullptr, 2, R);
+  BlendArgs a = view_blend_args(P, R, W, H, geom, binning, image, nullptr, 2, flags);
   a.C = C;
   a.image_weights = image_weights;
   a.weights = weights;
   a.cnt = cnt;
-  a.fast_exp = (flags & GSR_FLAG_FAST_EXP) ? 1 : 0;
-  a.shared_simds = (flags & GSR_FLAG_SHARED_SIMDS) ? 1 : 0;
   GSR_HIP(launch_trace_weights((hipStream_t)stream, a));
   return GSR_OK;
 }
