@@ -83,6 +83,10 @@ SIGNATURES = {
     # dL_dalpha (1,H,W) behind dL_dpix
     "gsr_alpha_image": (c_int, [_P, c_int, c_int, _P, _P]),
     "gsr_blend_backward_alpha": (c_int, [_P, c_int, c_int64, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_uint]),
+    # feature image: (stream, P, R, W, H, C, geom, binning, image, features (P,C), out (C,H,W), flags); its backward:
+    # (stream, P, R, W, H, C, geom, binning, image, features, dL_dfeature_image (C,H,W), acc, dL_dfeatures (P,C), flags)
+    "gsr_blend_forward_features": (c_int, [_P, c_int, c_int64, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_uint]),
+    "gsr_blend_backward_features": (c_int, [_P, c_int, c_int64, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_uint]),
     # (... radii, geom, acc, dL_dmeans2D, dL_dopacity, dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drots, flags)
     "gsr_preprocess_backward": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_float, _P, _P, _P, _P, _P,
                                         c_float, c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_uint]),

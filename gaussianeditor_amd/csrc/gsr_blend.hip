@@ -1437,6 +1437,475 @@ __global__ void __launch_bounds__(WAVE) trace_weights_kernel(const BlendArgs a) 
   run_work_queue<SPLIT>(a, false, [&](uint32_t tile, uint32_t quad, bool) __attribute__((always_inline)) { trace_item<C, SPLIT, FAST>(a, tile, quad); });
 }
 
+// ----------------------------------------------------------------------------------
+// Feature rendering: per-Gaussian feature vectors of C channels, alpha-composited into a (C,H,W) image on background 0
+// (gsr_blend_forward_features), and its backward (gsr_blend_backward_features).  No reference counterpart (the reference
+// composites three channels); the N-D `colors` of current 3DGS rasterizers.
+// The channels are walked in BLOCKS of FEAT_BLOCK = 16 (one 64-byte line of a feature row): alpha and T of a (pixel, entry)
+// pair are evaluated once per block, not once per three channels as a chain of auxiliary renders would.
+// What the two kernels need beyond a view's BlendArgs travels as a second kernel argument: BlendArgs, and with it the
+// argument layout of every other kernel, keeps its size.
+// ----------------------------------------------------------------------------------
+constexpr int FEAT_BLOCK = 16;
+struct FeatureArgs {
+  const float* features;   // (P,C) row-major
+  float* out;              // forward: (C,H,W), fully written
+  const float* dL_dimage;  // backward: (C,H,W), the gradient of `out`
+  float* dL_dfeatures;     // backward: (P,C), added into (the caller zeroes it)
+  int C;
+};
+
+// One forward item: K12's traversal (survivors staged in pairs, alpha of two entries per packed instruction, K6's select
+// form of the transmittance chain), and per blended (pixel, entry) K6's accumulation C_c = fma(f_c, alpha T, C_c) for the 16
+// channels of the block -- channel c of the image equals, as floats, channel c % 3 of an auxiliary render of
+// features[:, 3 (c / 3) : + 3].  The accumulation is a lane-masked region, as K6's masked form: a feature of an entry the
+// pixel skips is never read into the sum (0 x NaN).
+template <bool FAST>
+__device__ __forceinline__ void feature_forward_item(const BlendArgs& a, const FeatureArgs& f, uint32_t tile, uint32_t quad) {
+  PixelWave pw;
+  ItemBox box;
+  if (!setup_item<1>(a, tile, quad, pw, box)) return;
+  (void)box;
+  const int lane = lane_id();
+  const uint2 range = a.ranges[pw.tile];
+  const float pfx = (float)pw.px, pfy = (float)pw.py;
+  const f32x2 pfx2 = {pfx, pfx}, pfy2 = {pfy, pfy};
+  const size_t pix = (size_t)pw.py * a.W + pw.px, HW = (size_t)a.H * a.W;
+  __shared__ __align__(16) float spair[WAVE / 2][12];
+  __shared__ __align__(16) float sfeat[WAVE][FEAT_BLOCK];
+  const uint64_t lt_mask = (1ull << lane) - 1ull;
+  const int C = f.C;
+  for (int c0 = 0; c0 < C; c0 += FEAT_BLOCK) {
+    const int nch = min(FEAT_BLOCK, C - c0);  // (the last block may be partial: its missing channels blend zeros)
+    float F[FEAT_BLOCK];
+#pragma unroll
+    for (int k = 0; k < FEAT_BLOCK; ++k) F[k] = 0.f;
+    float Ts = pw.inside ? 1.0f : -1.0f;
+    if (range.y > range.x) {
+      ChunkWalker<true> walk(a, range.x, range.y - range.x);
+      for (; walk.valid(); walk.advance()) {
+        const uint64_t live_m = __ballot(Ts > 0.0f);
+        if (live_m == 0) break;
+        const LiveBox lb = live_pixel_box(live_m, pfx - (float)(lane & 7), pfy - (float)(lane >> 3));
+        const bool keep = ((uint32_t)lane < walk.chunk_size()) && can_touch_quad(walk.cur.r0, walk.cur.r1, lb.x0, lb.y0, lb.w, lb.h);
+        const uint64_t km = __ballot(keep);
+        if (km == 0) continue;
+        const uint32_t n = (uint32_t)__popcll(km);
+        const uint32_t n4 = (n + GROUP - 1) & ~(uint32_t)(GROUP - 1);
+        __syncthreads();
+        if (keep) {
+          const uint32_t slot = (uint32_t)__popcll(km & lt_mask);
+          float* q = &spair[slot >> 1][slot & 1u];
+          q[0] = -0.5f * walk.cur.r0.x;
+          q[2] = -walk.cur.r0.y;
+          q[4] = -0.5f * walk.cur.r0.z;
+          q[6] = walk.cur.r0.w;
+          q[8] = walk.cur.r1.x;
+          q[10] = walk.cur.r1.y;
+          const float* __restrict__ fr = f.features + (size_t)walk.cur.id * (size_t)C + c0;
+#pragma unroll
+          for (int k = 0; k < FEAT_BLOCK; ++k) {
+            const float v = fr[min(k, nch - 1)];  // (unconditional and in bounds; a channel beyond the last one is zero)
+            sfeat[slot][k] = k < nch ? v : 0.f;
+          }
+        }
+        if ((uint32_t)lane >= n && (uint32_t)lane < n4) {
+          // null entries pad the survivors to a multiple of GROUP: opacity 0 => alpha 0 => never a hit
+          float* q = &spair[lane >> 1][lane & 1];
+          q[0] = q[2] = q[4] = q[6] = q[8] = q[10] = 0.f;
+        }
+        __syncthreads();
+        for (uint32_t j = 0; j < n4; j += GROUP) {
+          if (__all(Ts < 0.0f)) break;
+          float ae[GROUP], om[GROUP];
+#pragma unroll
+          for (int pp = 0; pp < GROUP / 2; ++pp) {
+            const float* q = &spair[(j >> 1) + pp][0];
+            const float4 q0 = *reinterpret_cast<const float4*>(q), q1 = *reinterpret_cast<const float4*>(q + 4),
+                         q2 = *reinterpret_cast<const float4*>(q + 8);
+            const f32x2 hA = {q0.x, q0.y}, nB = {q0.z, q0.w}, hC = {q1.x, q1.y}, op = {q1.z, q1.w};
+            const f32x2 dx = f32x2{q2.x, q2.y} - pfx2, dy = f32x2{q2.z, q2.w} - pfy2;
+            const f32x2 a_ = (hA * dx) * dx;  // blend_power_prescaled on both entries
+            const f32x2 s_ = __builtin_elementwise_fma(hC * dy, dy, a_);
+            const f32x2 power = __builtin_elementwise_fma(nB * dx, dy, s_);
+            const f32x2 ao = op * blend_exp2<FAST>(power);
+            const float a0 = fminf(0.99f, ao.x), a1 = fminf(0.99f, ao.y);
+            const float g0 = (power.x > 0.0f) ? 0.0f : a0, g1 = (power.y > 0.0f) ? 0.0f : a1;
+            const f32x2 a2 = {(g0 < 1.0f / 255.0f) ? 0.0f : g0, (g1 < 1.0f / 255.0f) ? 0.0f : g1};
+            const f32x2 o2 = f32x2{1.0f, 1.0f} - a2;
+            ae[2 * pp] = a2.x;
+            ae[2 * pp + 1] = a2.y;
+            om[2 * pp] = o2.x;
+            om[2 * pp + 1] = o2.y;
+          }
+#pragma unroll
+          for (int u = 0; u < GROUP; ++u) asm volatile("" : "+v"(ae[u]), "+v"(om[u]));
+#pragma unroll
+          for (int u = 0; u < GROUP; ++u) {
+            const float test_T = Ts * om[u];
+            const bool A = !(test_T < 0.0001f);
+            const float w = ae[u] * Ts;
+            if (A && ae[u] > 0.0f) {  // the pixel blends the entry: w = alpha T
+              const float4* fp = reinterpret_cast<const float4*>(&sfeat[j + u][0]);
+#pragma unroll
+              for (int k4 = 0; k4 < FEAT_BLOCK / 4; ++k4) {
+                const float4 v = fp[k4];
+                F[4 * k4] = __builtin_fmaf(v.x, w, F[4 * k4]);
+                F[4 * k4 + 1] = __builtin_fmaf(v.y, w, F[4 * k4 + 1]);
+                F[4 * k4 + 2] = __builtin_fmaf(v.z, w, F[4 * k4 + 2]);
+                F[4 * k4 + 3] = __builtin_fmaf(v.w, w, F[4 * k4 + 3]);
+              }
+            }
+            Ts = A ? test_T : -__builtin_fabsf(Ts);
+          }
+        }
+      }
+    }
+    if (pw.inside) {
+#pragma unroll
+      for (int k = 0; k < FEAT_BLOCK; ++k)
+        if (k < nch) f.out[(size_t)(c0 + k) * HW + pix] = F[k];
+    }
+  }
+}
+template <bool FAST>
+__global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(4, 4)))
+feature_forward_kernel(const BlendArgs a, const FeatureArgs f) {
+  run_work_queue<1>(a, true, [&](uint32_t tile, uint32_t quad, bool empty) __attribute__((always_inline)) {
+    if (!empty) {
+      feature_forward_item<FAST>(a, f, tile, quad);
+    } else {  // a tile no Gaussian touches: zeros
+      for (uint32_t q = 0; q < 4; ++q) {
+        PixelWave pw;
+        if (!setup_wave(a, tile, q, pw)) continue;
+        if (pw.inside) {
+          const size_t pix = (size_t)pw.py * a.W + pw.px, HW = (size_t)a.H * a.W;
+          for (int c = 0; c < f.C; ++c) f.out[(size_t)c * HW + pix] = 0.f;
+        }
+      }
+    }
+  });
+}
+
+// The feature backward: K7's workgroup (the four quadrant waves of a tile, or of half a heavy one), walking the first
+// n_contrib entries of every pixel back to front from final_T, once per channel block.  It needs NO checkpoints and its
+// work list holds NO list segments (the forward's checkpoints hold no features): views with long lists take longer than the
+// colour backward, as with gsr_blend_backward_depth.
+// Mathematics (background 0): F_c = sum_i f_ic alpha_i T_i.  With rec_c the colour behind entry i (the reference's
+// accum_rec recurrence, backward.cu:515),
+//   dL/dalpha_i = T_i sum_c (f_ic - rec_c) gF_c,      dL/df_ic = alpha_i T_i gF_c.
+// As in K7 the recurrence is linear and gF is constant for the pixel, so B = sum_c rec_c gF_c follows the same recurrence
+// with the scalar cdot = sum_c f_ic gF_c: one scalar of state per lane whatever the block's width.
+// Per entry a wave reduces the six raw geometry moments of q = G dL/dalpha (K7's moments 0 .. 5: q, q dx, q dy, q dx dx,
+// q dx dy, q dy dy) and the 16 feature terms; the four waves add both into one LDS row per chunk slot (22 floats in rows of
+// 23: odd), and the flush -- deferred by a chunk, as K7's -- turns a row into TWO memory-side requests: the geometry columns
+// ACC_MEAN2D, ACC_OPACITY, ACC_CONIC of the Gaussian's accumulator row in K7's conventions (the share of dL/dalpha is linear
+// in it: every channel block adds its own), and the 16 channels of the block on 16 adjacent lanes into dL_dfeatures.
+constexpr int FEAT_NM = 6;
+// Three workgroups per CU, not K7's four: next to K7's state a lane keeps the 16 pixel gradients of the block, and with
+// the 128 registers of four waves per SIMD the compiler spills 45 of them to scratch memory; with 168 it spills none.
+constexpr int FEAT_BWD_WAVES_PER_SIMD = 3;
+constexpr int FEAT_LDS_ROW = FEAT_NM + FEAT_BLOCK + 1;
+constexpr int FEAT_HALF = FEAT_BLOCK / 2;  // channels reduced at once: 8 x 4 entries, every total in two lanes
+static_assert(pack_lanes<FEAT_NM>().ok && pack_lanes<FEAT_HALF>().ok, "every moment / channel of every entry reaches a lane");
+// wave_sum4_pack<NK> of the outer product v[k][u] = m[u] g[k] without forming its 4 NK registers: the first stage pairs the
+// entries (u, u + 1) of one channel, so its selects move onto m (four for the whole product) and its output is two
+// products and a DPP add.  The lane that ends up with a value is pack_lanes<NK>()'s.
+template <int NK>
+__device__ __forceinline__ float wave_sum4_pack_outer(const float (&m)[GROUP], const float* g) {
+  const int lane = lane_id();
+  constexpr int N1 = NK * GROUP / 2, N2 = (N1 + 1) / 2, N3 = (N2 + 1) / 2, N4 = (N3 + 1) / 2, N5 = (N4 + 1) / 2;
+  static_assert((N5 + 1) / 2 == 1, "six halvings leave one register");
+  const bool second = (lane & 8) != 0;
+  const float keep0 = second ? m[1] : m[0], give0 = second ? m[0] : m[1];
+  const float keep1 = second ? m[3] : m[2], give1 = second ? m[2] : m[3];
+  auto other = [](float x) __attribute__((always_inline)) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), PackStage<8>::ctrl, 0xf, 0xf, true));
+  };
+  float z[N1];
+#pragma unroll
+  for (int k = 0; k < NK; ++k) {
+    z[2 * k] = keep0 * g[k] + other(give0 * g[k]);
+    z[2 * k + 1] = keep1 * g[k] + other(give1 * g[k]);
+  }
+  pack_stage<4, N1>(z, lane);
+  pack_stage<2, N2>(z, lane);
+  pack_stage<1, N3>(z, lane);
+  pack_stage<32, N4>(z, lane);
+  pack_stage<16, N5>(z, lane);
+  return z[0];
+}
+
+template <bool FAST>
+__device__ __forceinline__ void feature_backward_tile(const BlendArgs& a, const FeatureArgs& f, const uint4 item,
+                                                      float4 (*s0)[WAVE], float4 (*s1)[WAVE], float (*sfeat)[WAVE][FEAT_BLOCK],
+                                                      uint32_t (*sid)[WAVE], float4 (*sco)[WAVE],
+                                                      float (*sacc)[WAVE][FEAT_LDS_ROW]) {
+  const int w = (int)(threadIdx.x >> 6), lane = lane_id();
+  constexpr PackLanes tg = pack_lanes<FEAT_NM>(), tf = pack_lanes<FEAT_HALF>();
+  auto bit = [lane](uint64_t plane) __attribute__((always_inline)) { return (uint32_t)(plane >> (uint32_t)lane) & 1u; };
+  const uint32_t g_term = bit(tg.term_bit[0]) | bit(tg.term_bit[1]) << 1 | bit(tg.term_bit[2]) << 2 | bit(tg.term_bit[3]) << 3;
+  const uint32_t g_entry = bit(tg.entry_bit[0]) | bit(tg.entry_bit[1]) << 1;
+  const bool g_adds = bit(tg.adds) != 0u;
+  const uint32_t f_term = bit(tf.term_bit[0]) | bit(tf.term_bit[1]) << 1 | bit(tf.term_bit[2]) << 2 | bit(tf.term_bit[3]) << 3;
+  const uint32_t f_entry = bit(tf.entry_bit[0]) | bit(tf.entry_bit[1]) << 1;
+  const bool f_adds = bit(tf.adds) != 0u;
+  // the item: a whole tile (wave w = quadrant w) or half of one (K7's item codes; the work list is built without segments)
+  uint32_t tile = item.x;
+  const bool half_item = (tile & BWD_ITEM_HALF) != 0u;
+  const uint32_t part = (tile & BWD_ITEM_PART) ? 1u : 0u;
+  tile &= BWD_ITEM_TILE;
+  const uint32_t list_base = item.y, tile_max = item.z;
+  if (tile_max == 0) return;  // (uniform: nothing of the item's pixels ever contributed)
+  PixelWave pw;
+  const bool has_pixels = setup_wave(a, tile, half_item ? 2u * part + (uint32_t)(w >> 1) : (uint32_t)w, pw);
+  const float pfx = (float)pw.px, pfy = (float)pw.py;
+  const float qx0 = (float)(pw.px - (lane & 7)), qy0 = (float)(pw.py - (lane >> 3));
+  if (half_item) pw.inside = pw.inside && ((lane >> 5) == (w & 1));
+  const size_t HW = (size_t)a.H * a.W;
+  const bool live = has_pixels && pw.inside;
+  const size_t pix = live ? (size_t)pw.py * a.W + pw.px : (size_t)0;
+  const float T_final_ld = a.final_T[pix];
+  const uint32_t n_contrib_ld = a.n_contrib[pix];
+  const float T_final = live ? T_final_ld : 0.f;
+  const uint32_t last_contributor = live ? n_contrib_ld : 0u;
+  const uint32_t maxc = wave_max_u32_dpp(last_contributor);
+  const float ddelx_dx = 0.5f * a.W, ddely_dy = 0.5f * a.H;
+  const uint64_t lt_mask = (1ull << lane) - 1ull;
+  const int C = f.C;
+  // the features of a chunk are staged once for the four waves: wave w fetches the entries 16 w .. 16 w + 15, four channels a lane
+  const uint32_t fe = 16u * (uint32_t)w + ((uint32_t)lane >> 2), fc = 4u * ((uint32_t)lane & 3u);
+
+  for (int c0 = 0; c0 < C; c0 += FEAT_BLOCK) {
+    if (c0 != 0) __syncthreads();  // (the previous block's last flush read sid / sco / sacc; this block's first chunk writes them)
+    float gF[FEAT_BLOCK];
+#pragma unroll
+    for (int k = 0; k < FEAT_BLOCK; ++k) {
+      const float v = f.dL_dimage[(size_t)min(c0 + k, C - 1) * HW + pix];
+      gF[k] = (live && c0 + k < C) ? v : 0.f;
+    }
+    auto fetch = [&](uint32_t id_of_lane) __attribute__((always_inline)) {
+      const uint32_t id = (uint32_t)__shfl((int)id_of_lane, (int)fe);
+      const float* __restrict__ fr = f.features + (size_t)id * (size_t)C;
+      float4 r;
+      const int cc = c0 + (int)fc;
+      r.x = fr[min(cc, C - 1)];
+      r.y = fr[min(cc + 1, C - 1)];
+      r.z = fr[min(cc + 2, C - 1)];
+      r.w = fr[min(cc + 3, C - 1)];
+      r.x = cc < C ? r.x : 0.f;
+      r.y = cc + 1 < C ? r.y : 0.f;
+      r.z = cc + 2 < C ? r.z : 0.f;
+      r.w = cc + 3 < C ? r.w : 0.f;
+      return r;
+    };
+    ChunkWalker<false> walk(a, list_base, tile_max);
+    float4 fcur = fetch(walk.cur.id);
+    float T = T_final;
+    float B_acc = 0.f, last_cdot = 0.f, last_alpha = 0.f;
+
+    auto flush = [&](uint32_t fb, uint32_t fsize) __attribute__((always_inline)) {
+      const uint32_t col = (uint32_t)lane & 15u, sub = (uint32_t)lane >> 4;
+      // raw moments a geometry column reads (K7's flush): dL_dmean2D (1, 2); opacity 0; conic x / y / w: 3 / 4 / 5
+      const uint32_t ia = col == ACC_MEAN2D || col == ACC_MEAN2D + 1u ? 1u
+                          : col == ACC_OPACITY ? 0u
+                          : col == ACC_CONIC ? 3u : col == ACC_CONIC + 1u ? 4u : col == ACC_CONIC + 3u ? 5u
+                          : (uint32_t)FEAT_NM;  // FEAT_NM: the column is not written
+#pragma unroll
+      for (uint32_t jj = 0; jj < 4u; ++jj) {
+        const uint32_t p = 16u * (uint32_t)w + 4u * jj + sub;
+        if (16u * (uint32_t)w + 4u * jj >= fsize) break;  // (wave-uniform)
+        const bool in = p < fsize;
+        float* const row = sacc[fb][in ? p : 0u];
+        const bool used = in && ia < (uint32_t)FEAT_NM;
+        const float ma = used ? row[ia] : 0.f;
+        const float mb = used && ia == 1u ? row[2] : 0.f;
+        const float fv = in ? row[FEAT_NM + col] : 0.f;
+        const float4 co = sco[fb][in ? p : 0u];  // conic.x, conic.y, conic.z, opacity
+        const size_t id = sid[fb][in ? p : 0u];
+        float val;
+        bool nz;
+        if (ia == 1u) {  // backward.cu:545-546
+          const bool xcol = col == ACC_MEAN2D;
+          const float scale = xcol ? ddelx_dx : ddely_dy, c1 = xcol ? co.x : co.y, c2 = xcol ? co.y : co.z;
+          val = -(scale * co.w) * (c1 * ma + c2 * mb);
+          nz = ma != 0.f || mb != 0.f;
+        } else {  // backward.cu:549-551: -0.5 o t; opacity (:554): the moment itself
+          const bool conic = ia >= 3u && ia <= 5u;
+          val = conic ? (-0.5f * co.w) * ma : ma;
+          nz = ma != 0.f;
+        }
+        if (used && nz) unsafeAtomicAdd(&a.acc[id * ACC_ROW + col], val);
+        if (in && fv != 0.f && c0 + (int)col < C) unsafeAtomicAdd(&f.dL_dfeatures[id * (size_t)C + (size_t)c0 + col], fv);
+        if (in) {  // (every read of this instruction precedes it: one wave, program order)
+          row[col] = 0.f;
+          if (col < (uint32_t)(FEAT_NM + FEAT_BLOCK - 16)) row[16u + col] = 0.f;
+        }
+      }
+    };
+
+    uint32_t pend_size = 0u;
+    for (; walk.valid(); walk.advance()) {
+      const uint32_t csize = walk.chunk_size();
+      const uint32_t cb = walk.chunk & 1u;
+      if (w == 0 && (uint32_t)lane < csize) {
+        sid[cb][lane] = walk.cur.id;
+        sco[cb][lane] = walk.cur.r0;
+      }
+      *reinterpret_cast<float4*>(&sfeat[cb][fe][fc]) = fcur;
+      fcur = fetch(walk.nxt.id);  // (the next chunk's, in flight through this chunk's group loop)
+      const uint32_t pos = walk.lane_pos();
+      const uint32_t chunk_lo = tile_max - min(tile_max, (walk.chunk + 1u) * (uint32_t)WAVE);
+      const uint64_t live_m = __ballot(last_contributor > chunk_lo);
+      bool keep = false;
+      if (live_m != 0) {
+        const LiveBox lb = live_pixel_box(live_m, qx0, qy0);
+        keep = ((uint32_t)lane < csize) && (pos < maxc) && can_touch_quad(walk.cur.r0, walk.cur.r1, lb.x0, lb.y0, lb.w, lb.h);
+      }
+      const uint64_t m = __ballot(keep);
+      const uint32_t cnt = (uint32_t)__popcll(m);
+      const uint32_t cnt4 = (cnt + GROUP - 1) & ~(uint32_t)(GROUP - 1);
+      if (keep) {
+        const uint32_t slot = (uint32_t)__popcll(m & lt_mask);
+        s0[w][slot] = make_float4(-0.5f * walk.cur.r0.x, -walk.cur.r0.y, -0.5f * walk.cur.r0.z, walk.cur.r0.w);
+        // .z: the entry's index inside the chunk (= the lane that holds it): its LDS accumulator slot and feature row
+        s1[w][slot] = make_float4(walk.cur.r1.x, walk.cur.r1.y, __uint_as_float((uint32_t)lane), __uint_as_float(pos));
+      }
+      if ((uint32_t)lane >= cnt && (uint32_t)lane < cnt4) {
+        s0[w][lane] = make_float4(0.f, 0.f, 0.f, 0.f);  // null entry: alpha 0 => never contributes
+        s1[w][lane] = make_float4(0.f, 0.f, __uint_as_float(0u), __uint_as_float(0xffffffffu));
+      }
+      __syncthreads();  // (A) the chunk's features (and sid / sco) are staged for the four waves
+      if (pend_size != 0u) flush(cb ^ 1u, pend_size);
+      pend_size = csize;
+
+      for (uint32_t j = 0; j < cnt4; j += GROUP) {
+        float G[GROUP], al[GROUP], dxs[GROUP], dys[GROUP];
+        bool contrib[GROUP];
+        uint32_t cslot[GROUP];
+        bool any = false;
+#pragma unroll
+        for (int u = 0; u < GROUP; ++u) {
+          const float4 g = s1[w][j + u];
+          const float4 co = s0[w][j + u];
+          cslot[u] = __float_as_uint(g.z);
+          const uint32_t c = __float_as_uint(g.w);
+          dxs[u] = g.x - pfx;
+          dys[u] = g.y - pfy;
+          const float power = blend_power_prescaled(co.x, co.y, co.z, dxs[u], dys[u]);
+          G[u] = blend_exp<FAST>(power);
+          al[u] = fminf(0.99f, co.w * G[u]);
+          contrib[u] = (c < last_contributor) && !(power > 0.0f) && !(al[u] < 1.0f / 255.0f);
+          any = any || contrib[u];
+        }
+        if (!__any(any)) continue;  // wave-uniform
+
+        float v[FEAT_NM][GROUP], mD[GROUP], cdots[GROUP];
+        {
+#pragma clang fp contract(fast)  // gradients are tolerance-checked (<= 1e-5), not bit-compared
+          // cdot = sum_c f_c gF_c of the four entries, one entry's 16 staged features in registers at a time: the next
+          // entry's row address is pinned behind this entry's sum (all four rows in flight at once are 64 registers)
+#pragma unroll
+          for (int u = 0; u < GROUP; ++u) {
+            const float4* fp = reinterpret_cast<const float4*>(&sfeat[cb][cslot[u]][0]);
+            float cdot = 0.f;
+#pragma unroll
+            for (int k4 = 0; k4 < FEAT_BLOCK / 4; ++k4) {
+              const float4 fv = fp[k4];
+              cdot += fv.x * gF[4 * k4] + fv.y * gF[4 * k4 + 1] + fv.z * gF[4 * k4 + 2] + fv.w * gF[4 * k4 + 3];
+            }
+            cdots[u] = cdot;
+            if (u + 1 < GROUP) asm volatile("" : "+v"(cdots[u]), "+v"(cslot[u + 1]));
+          }
+#pragma unroll
+          for (int u = 0; u < GROUP; ++u) {
+            const bool on = contrib[u];
+            const float alpha = on ? al[u] : 0.f;
+            const float one_m = 1.f - alpha;
+            const float r0 = __builtin_amdgcn_rcpf(one_m);
+            const float inv_one_m = __builtin_fmaf(r0, __builtin_fmaf(-one_m, r0, 1.0f), r0);
+            const float cdot = cdots[u];
+            T = T * inv_one_m;                                 // T / (1 - alpha), backward.cu:503
+            B_acc = B_acc + last_alpha * (last_cdot - B_acc);  // accum_rec update, backward.cu:515
+            const float dL_dalpha = (cdot - B_acc) * T;        // (no background term: the feature image's background is 0)
+            last_alpha = alpha;
+            last_cdot = on ? cdot : last_cdot;
+            const float q = on ? G[u] * dL_dalpha : 0.f;
+            mD[u] = alpha * T;  // dF_c / df_c (0 for a skipped lane)
+            const float dx = dxs[u], dy = dys[u];
+            const float qx = q * dx, qy = q * dy;
+            v[0][u] = q;
+            v[1][u] = qx;
+            v[2][u] = qy;
+            v[3][u] = qx * dx;
+            v[4][u] = qx * dy;
+            v[5][u] = qy * dy;
+          }
+        }
+        float totg = wave_sum4_pack<FEAT_NM>(v);
+        asm volatile("" : "+v"(totg));
+        if (g_adds) atomicAdd(&sacc[cb][__float_as_uint(s1[w][j + g_entry].z)][g_term], totg);
+        // the 16 feature terms alpha T gF_c of the four entries, eight channels at a time (32 values: one per lane pair)
+        float* const frow = &sacc[cb][__float_as_uint(s1[w][j + f_entry].z)][FEAT_NM + f_term];
+#pragma unroll
+        for (int h = 0; h < FEAT_BLOCK / FEAT_HALF; ++h) {
+          float totf = wave_sum4_pack_outer<FEAT_HALF>(mD, gF + FEAT_HALF * h);
+          asm volatile("" : "+v"(totf));
+          if (f_adds) atomicAdd(frow + FEAT_HALF * h, totf);
+        }
+      }
+      __syncthreads();  // (B) every quadrant's contribution to this chunk is in sacc[cb]
+    }
+    asm volatile("" ::"v"(walk.nxt.r0.x), "v"(walk.nxt.r1.x), "v"(walk.id_next), "v"(walk.id_next2), "v"(fcur.x), "v"(fcur.y), "v"(fcur.z), "v"(fcur.w));
+    if (pend_size != 0u) flush((walk.chunk - 1u) & 1u, pend_size);
+  }
+}
+
+template <bool FAST>
+__global__ void __launch_bounds__(WAVE* BWD_WAVES) __attribute__((amdgpu_waves_per_eu(FEAT_BWD_WAVES_PER_SIMD, FEAT_BWD_WAVES_PER_SIMD)))
+feature_backward_kernel(const BlendArgs a, const FeatureArgs f) {
+  __shared__ float4 s0[BWD_WAVES][WAVE], s1[BWD_WAVES][WAVE];
+  __shared__ __align__(16) float sfeat[2][WAVE][FEAT_BLOCK];  // (sfeat, sid, sco, sacc: double-buffered by chunk parity)
+  __shared__ uint32_t sid[2][WAVE];
+  __shared__ float4 sco[2][WAVE];
+  __shared__ float sacc[2][WAVE][FEAT_LDS_ROW];
+  __shared__ uint32_t s_item;
+  for (int i = threadIdx.x; i < 2 * WAVE * FEAT_LDS_ROW; i += WAVE * BWD_WAVES) (&sacc[0][0][0])[i] = 0.f;
+  __syncthreads();
+  // item-granular queue, as K7: queue x (one per XCD) owns items x, x + 8, ... of the backward's work list
+  const uint32_t x = (uint32_t)__builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 20) & 7u;  // HW_REG_XCC_ID
+  const uint32_t nwork = a.bwd_meta[0];
+  const uint32_t n_x = nwork > x ? (nwork - x + 7u) / 8u : 0u;
+  uint32_t* head = a.queue + x * QUEUE_STRIDE;
+  // (always_inline: called, the item function would receive the argument blocks through scratch memory)
+  auto run_tile = [&](uint32_t index) __attribute__((always_inline)) {
+    const uint32_t code = scalar_load(a.bwd_order, index);
+    const uint32_t ctile = code & BWD_ITEM_TILE;
+    const uint2 crange = scalar_load(a.ranges, ctile);
+    const uint4 cmax = scalar_load(reinterpret_cast<const uint4*>(a.work_maxc), ctile);
+    const uint32_t r01 = max(cmax.x, cmax.y), r23 = max(cmax.z, cmax.w);
+    const uint32_t deep = (code & BWD_ITEM_HALF) ? ((code & BWD_ITEM_PART) ? r23 : r01) : max(r01, r23);
+    // (the depths are the forward's own: never beyond the tile's list)
+    const uint4 item = make_uint4(code, crange.x, min(deep, crange.y - crange.x), 0u);
+    feature_backward_tile<FAST>(a, f, item, s0, s1, sfeat, sid, sco, sacc);
+  };
+  uint32_t x0, base;
+  const uint32_t q0 = first_item_of_block((uint32_t)a.units, x0, base);
+  {
+    const uint32_t n0 = nwork > x0 ? (nwork - x0 + 7u) / 8u : 0u;
+    if (q0 < n0) run_tile(x0 + 8u * q0);
+  }
+  for (;;) {
+    __syncthreads();
+    if (threadIdx.x == 0) s_item = base + __hip_atomic_fetch_add(head, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    const uint32_t q = s_item;
+    if (q >= n_x) break;
+    run_tile(x + 8u * q);
+  }
+  if (a.self_reset && threadIdx.x == 0) retire_queue(a.queue);
+}
+
 // Work list of the backward blend: tiles ordered by the work the FORWARD blend measured for them (entries evaluated,
 // summed over the four quadrants; the backward revisits the same (pixel, entry) pairs), heaviest first, in buckets of
 // 16 entries; tiles in which the forward evaluated nothing have no contributor anywhere and are dropped.  The list
@@ -1884,6 +2353,35 @@ hipError_t launch_trace_weights(hipStream_t s, BlendArgs a) {
                  OneOf<1, 2, 3>{a.C}, OneOf<1, 2, 4>{split}, a.fast_exp != 0);
   if (kernel == nullptr) return hipErrorInvalidValue;
   hipLaunchKernelGGL(kernel, g, b, 0, s, a);
+  return hipGetLastError();
+}
+
+// The feature image and its backward (gsr_blend_forward_features / gsr_blend_backward_features): one launch each, plus the
+// backward's own work list -- built WITHOUT list segments and without clears, whatever the colour backward of the view left
+// in Image::bwd_order.
+hipError_t launch_feature_forward(hipStream_t s, BlendArgs a, const float* features, float* out, int C) {
+  unsigned grid;
+  hipError_t e = persistent_launch(s, a, 1, &grid);
+  if (e != hipSuccess) return e;
+  FeatureArgs f = {features, out, nullptr, nullptr, C};
+  hipLaunchKernelGGL(a.fast_exp ? feature_forward_kernel<true> : feature_forward_kernel<false>, dim3(grid), dim3(WAVE), 0, s, a, f);
+  return hipGetLastError();
+}
+hipError_t launch_feature_backward(hipStream_t s, BlendArgs a, const float* features, const float* dL_dimage,
+                                   float* dL_dfeatures, int C) {
+  // #CUs x 3 workgroups of 4 waves (FEAT_BWD_WAVES_PER_SIMD: what is resident), fewer where the view's launches are smaller
+  unsigned grid = min(blend_grid_size(s, a.shared_simds != 0) / BWD_WAVES, (unsigned)cus_of_stream(s) * FEAT_BWD_WAVES_PER_SIMD);
+  a.units = (int)blend_units(BWD_WAVES, grid, s);
+  hipError_t e = prepare_queue(s, a, grid);
+  if (e != hipSuccess) return e;
+  if (a.work_est == nullptr || a.work_maxc == nullptr || a.bwd_order == nullptr) return hipErrorInvalidValue;
+  const ClearArgs clear = {{nullptr, nullptr, nullptr, nullptr}, {0, 0, 0, 0}};
+  hipLaunchKernelGGL(backward_worklist_kernel<false>, dim3(1u), dim3(1024), 0, s, a.gx * a.gy, a.work_est, a.bwd_order,
+                     a.bwd_meta, grid, 10, clear, (const uint32_t*)nullptr, (const uint32_t*)nullptr,
+                     (const uint32_t*)nullptr, CkTable{}, 0u, 0);
+  FeatureArgs f = {features, nullptr, dL_dimage, dL_dfeatures, C};
+  hipLaunchKernelGGL(a.fast_exp ? feature_backward_kernel<true> : feature_backward_kernel<false>, dim3(grid),
+                     dim3(WAVE * BWD_WAVES), 0, s, a, f);
   return hipGetLastError();
 }
 

@@ -764,6 +764,44 @@ int gsr_alpha_image(void* stream, int W, int H, const void* image, float* out_al
   return GSR_OK;
 }
 
+// The feature image: the flags a view's blend entry points share, without the bits that describe another call of the view.
+static const unsigned FEATURE_FLAGS = GSR_FLAG_FAST_EXP | GSR_FLAG_ANTIALIAS | GSR_FLAG_TILE_BOUNDS_ALPHA | GSR_FLAG_SHARED_SIMDS;
+
+int gsr_blend_forward_features(void* stream, int P, int64_t R, int W, int H, int C, const void* geom, const void* binning,
+                               void* image, const float* features, float* out_features, unsigned flags) {
+  if (flags & ~FEATURE_FLAGS) return GSR_ERR_BAD_ARGUMENT;
+  if (C < 1 || C > GSR_MAX_FEATURE_CHANNELS || P < 0 || R < 0 || W <= 0 || H <= 0) return GSR_ERR_BAD_ARGUMENT;
+  if (!image || !features || !out_features || ((uintptr_t)out_features & 3u) || ((uintptr_t)features & 3u)) return GSR_ERR_BAD_ARGUMENT;
+  if (R > 0 && (!geom || !binning)) return GSR_ERR_BAD_ARGUMENT;
+  if (P == 0 || R == 0) {  // nothing is blended: the background, zero
+    GSR_HIP(hipMemsetAsync(out_features, 0, sizeof(float) * (size_t)C * (size_t)H * (size_t)W, (hipStream_t)stream));
+    return GSR_OK;
+  }
+  if (misaligned(geom) || misaligned(binning) || misaligned(image)) return GSR_ERR_BAD_ARGUMENT;
+  BlendArgs a = view_blend_args(P, R, W, H, geom, binning, image, nullptr, 0, flags);
+  keep_main_render_state(a);
+  GSR_HIP(launch_feature_forward((hipStream_t)stream, a, features, out_features, C));
+  return GSR_OK;
+}
+
+int gsr_blend_backward_features(void* stream, int P, int64_t R, int W, int H, int C, const void* geom, const void* binning,
+                                const void* image, const float* features, const float* dL_dfeature_image, float* acc,
+                                float* dL_dfeatures, unsigned flags) {
+  if (flags & ~FEATURE_FLAGS) return GSR_ERR_BAD_ARGUMENT;
+  if (C < 1 || C > GSR_MAX_FEATURE_CHANNELS || P < 0 || R < 0 || W <= 0 || H <= 0) return GSR_ERR_BAD_ARGUMENT;
+  if (!image || !features || !dL_dfeature_image || !dL_dfeatures || !acc || ((uintptr_t)acc & 63u)) return GSR_ERR_BAD_ARGUMENT;
+  if (((uintptr_t)features | (uintptr_t)dL_dfeature_image | (uintptr_t)dL_dfeatures) & 3u) return GSR_ERR_BAD_ARGUMENT;
+  if (R > 0 && (!geom || !binning)) return GSR_ERR_BAD_ARGUMENT;
+  if (P == 0 || R == 0) return GSR_OK;  // no pixel blends anything: nothing to add
+  if (misaligned(geom) || misaligned(binning) || misaligned(image)) return GSR_ERR_BAD_ARGUMENT;
+  if ((int64_t)((W + TILE - 1) / TILE) * ((H + TILE - 1) / TILE) > (int64_t)GSR_MAX_TILES) return GSR_ERR_BAD_ARGUMENT;
+  BlendArgs a = view_blend_args(P, R, W, H, geom, binning, image, nullptr, 1, flags);
+  a.acc = acc;
+  a.P = P;
+  GSR_HIP(launch_feature_backward((hipStream_t)stream, a, features, dL_dfeature_image, dL_dfeatures, C));
+  return GSR_OK;
+}
+
 // the flags K8+K9 reads (the persistent-rows form takes GSR_FLAG_ANTIALIAS alone)
 static const unsigned PRE_BWD_FLAGS = GSR_FLAG_ACC_SELF_CLEAN | GSR_FLAG_DEPTH_GRAD | GSR_FLAG_ANTIALIAS;
 

@@ -200,6 +200,10 @@ hipError_t launch_abs_grad_take(hipStream_t s, int P, float* acc, const uint8_t*
 // the alpha image (accumulated opacity) 1 - final_T of the image state a forward left (gsr_blend.hip)
 hipError_t launch_alpha_image(hipStream_t s, int W, int H, const float* final_T, float* out_alpha);
 hipError_t launch_trace_weights(hipStream_t s, BlendArgs a);
+// the feature image (C channels per Gaussian, composited once per 16-channel block) and its backward (gsr_blend.hip)
+hipError_t launch_feature_forward(hipStream_t s, BlendArgs a, const float* features, float* out, int C);
+hipError_t launch_feature_backward(hipStream_t s, BlendArgs a, const float* features, const float* dL_dimage,
+                                   float* dL_dfeatures, int C);
 
 // The camera gradient (pose_backward_kernel, gsr_pose.hip): between K7 and K8+K9, from the accumulator rows K7 left
 struct PoseArgs {

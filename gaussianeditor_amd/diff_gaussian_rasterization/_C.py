@@ -287,6 +287,53 @@ def alpha_image(imgBuffer, image_height, image_width):
     return out
 
 
+MAX_FEATURE_CHANNELS = 256  # include/gsr.h: GSR_MAX_FEATURE_CHANNELS
+#: the flags of a view the two feature entry points take (FLAG_FORWARD_ONLY of a render under no_grad describes another call)
+_FEATURE_FLAGS = options.FLAG_TILE_BOUNDS_ALPHA | options.FLAG_FAST_EXP | options.FLAG_SHARED_SIMDS | options.FLAG_ANTIALIAS
+
+
+def _check_features(features, P: int, dev, name: str = "features") -> int:
+    """`features`: a float32 (P, C) tensor on `dev`, 1 <= C <= MAX_FEATURE_CHANNELS; errors name the argument.  -> C"""
+    if not isinstance(features, torch.Tensor) or features.dtype != torch.float32:
+        raise RuntimeError(f"diff_gaussian_rasterization: `{name}` must be a float32 tensor, got "
+                           f"{getattr(features, 'dtype', type(features).__name__)}")
+    if features.dim() != 2 or int(features.size(0)) != P or not 1 <= int(features.size(1)) <= MAX_FEATURE_CHANNELS:
+        raise RuntimeError(f"diff_gaussian_rasterization: `{name}` must be a ({P}, C) tensor with 1 <= C <= "
+                           f"{MAX_FEATURE_CHANNELS}, got {tuple(features.shape)}")
+    _same_device(features, name, dev)
+    return int(features.size(1))
+
+
+def rasterize_features(features, num_rendered, geomBuffer, binningBuffer, imgBuffer, image_height, image_width, debug=False,
+                       flags=None):
+    """Extension (no reference counterpart; include/gsr.h gsr_blend_forward_features): the feature image (C,H,W) float32 of
+    the view whose state (`geomBuffer`, `binningBuffer`, `imgBuffer`, `num_rendered`) a rasterize_gaussians() call returned --
+    the per-Gaussian `features` (P,C), 1 <= C <= 256, composited with the view's alpha on background 0, all channels in one
+    walk per 16-channel block.  The saved state is left intact.  Its backward: rasterize_gaussians_backward(features=,
+    dL_dout_features=, feature_grad_out=)."""
+    flags = _flags(flags)
+    if not isinstance(features, torch.Tensor):
+        raise RuntimeError(f"diff_gaussian_rasterization: `features` must be a tensor, got {type(features).__name__}")
+    _require_cuda(features, "features")
+    dev = features.device
+    P = int(features.size(0)) if features.dim() == 2 else -1
+    C = _check_features(features, P if P >= 0 else 0, dev)
+    H, W = int(image_height), int(image_width)
+    if P == 0 or geomBuffer.numel() == 0:
+        return torch.zeros((C, H, W), dtype=torch.float32, device=dev)
+    features = _f32(features, "features", dev)
+    for name, buf in (("geomBuffer", geomBuffer), ("binningBuffer", binningBuffer), ("imgBuffer", imgBuffer)):
+        _on_device(buf, name, dev, torch.uint8)
+    out = torch.empty((C, H, W), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _native.check("gsr_blend_forward_features", _native.lib().gsr_blend_forward_features(
+            _stream(dev), P, int(num_rendered), W, H, C, geomBuffer.data_ptr(), _ptr(binningBuffer), imgBuffer.data_ptr(),
+            features.data_ptr(), out.data_ptr(), flags & _FEATURE_FLAGS))
+        if debug:
+            torch.cuda.synchronize(dev)
+    return out
+
+
 #: The blend backward's accumulator table kept ACROSS backwards (GSR_FLAG_ACC_SELF_CLEAN, include/gsr.h): one zeroed (P,16)
 #: buffer per (device, stream), checked out for the duration of a backward's two native calls and put back only when both were
 #: enqueued -- K8+K9 leaves it all zero again in stream order, so the next backward on that stream needs no clear (64 MB in
@@ -314,7 +361,8 @@ def _alloc(fn, name: str, shape, zero: bool, dev) -> torch.Tensor:
 def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
                                  viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
                                  geomBuffer, R, binningBuffer, imageBuffer, debug, flags=None, grad_allocator=None,
-                                 dL_dout_depth=None, abs_grad_out=None, dL_dout_alpha=None, pose_grad_out=None):
+                                 dL_dout_depth=None, abs_grad_out=None, dL_dout_alpha=None, pose_grad_out=None,
+                                 features=None, dL_dout_features=None, feature_grad_out=None):
     """RasterizeGaussiansBackwardCUDA, rasterize_points.cu:97-157 ->
     (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D | None, dL_dsh, dL_dscales, dL_drotations).
     `flags` (extension, keyword): the flags the forward of this view ran with; None = options.current_flags().
@@ -348,10 +396,40 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     gsr_pose_backward -- between the backward's two halves, after gsr_abs_grad_take; the eight returned gradients are what
     they are without it, and a backward without it makes exactly the calls it made before the keyword existed.  Not with the
     "row_state" mode.
+    `features`, `dL_dout_features`, `feature_grad_out` (extension, keywords; all three or none): the (P,C) float32 features
+    a rasterize_features() of this view was given, the (C,H,W) float32 gradient of its image, and a contiguous, ZEROED (P,C)
+    float32 tensor the gradient of the features is added into (like `abs_grad_out` it is the caller's; rows of Gaussians no
+    pixel blends keep their zeros).  Given, gsr_blend_backward_features runs between the two halves -- blend half,
+    gsr_abs_grad_take, gsr_blend_backward_features, gsr_pose_backward, K8+K9 -- and adds the feature image's share of the
+    geometry gradients into the accumulator rows: the eight returned gradients and the camera gradient of `pose_grad_out`
+    hold it; dL_dcolors / dL_dsh get no share, and `abs_grad_out` is what it is without the feature image (a sum of
+    absolute values cannot take a signed share afterwards: folding it in would need a fused kernel; not offered).  Not with
+    the grad_allocator's "sh_rgb" and "row_state" modes.  Without the keywords the backward makes exactly the native calls it
+    made before they existed.
     Every backward is issued as its two halves (a blend half, then a K8+K9 half), never through the fused gsr_backward."""
     flags = _flags(flags)
     dev = means3D.device
     P = int(means3D.size(0))
+    feat_C = 0
+    if features is not None or dL_dout_features is not None or feature_grad_out is not None:
+        if features is None or dL_dout_features is None or feature_grad_out is None:
+            raise RuntimeError("diff_gaussian_rasterization: `features`, `dL_dout_features` and `feature_grad_out` are given "
+                               "together or not at all")
+        feat_C = _check_features(features, P, dev)
+        hw = tuple(dL_dout_color.shape[1:]) if isinstance(dL_dout_color, torch.Tensor) and dL_dout_color.dim() == 3 else None
+        if not isinstance(dL_dout_features, torch.Tensor) or dL_dout_features.dtype != torch.float32:
+            raise RuntimeError("diff_gaussian_rasterization: `dL_dout_features` must be a float32 tensor, got "
+                               f"{getattr(dL_dout_features, 'dtype', type(dL_dout_features).__name__)}")
+        if hw is None or tuple(dL_dout_features.shape) != (feat_C,) + hw:
+            raise RuntimeError(f"diff_gaussian_rasterization: `dL_dout_features` must be a {(feat_C,) + (hw or ('H', 'W'))} "
+                               f"tensor, got {tuple(dL_dout_features.shape)}")
+        _same_device(dL_dout_features, "dL_dout_features", dev)
+        if not isinstance(feature_grad_out, torch.Tensor) or feature_grad_out.dtype != torch.float32:
+            raise RuntimeError("diff_gaussian_rasterization: `feature_grad_out` must be a float32 tensor")
+        if tuple(feature_grad_out.shape) != (P, feat_C) or not feature_grad_out.is_contiguous():
+            raise RuntimeError(f"diff_gaussian_rasterization: `feature_grad_out` must be a contiguous ({P}, {feat_C}) tensor, "
+                               f"got {tuple(feature_grad_out.shape)}")
+        _same_device(feature_grad_out, "feature_grad_out", dev)
     if dL_dout_alpha is not None:
         hw = tuple(dL_dout_color.shape[1:]) if isinstance(dL_dout_color, torch.Tensor) and dL_dout_color.dim() == 3 else None
         if not isinstance(dL_dout_alpha, torch.Tensor) or dL_dout_alpha.dtype != torch.float32:
@@ -394,6 +472,8 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
             raise RuntimeError(f"diff_gaussian_rasterization: `dL_dout_depth` must be a (1, {H}, {W}) tensor on {dev}, "
                                f"got {tuple(dL_ddepth.shape)} on {dL_ddepth.device}")
     dL_dalpha = None if dL_dout_alpha is None else _f32(dL_dout_alpha, "dL_dout_alpha", dev)
+    if feat_C:
+        features, dL_dfeat_img = _f32(features, "features", dev), _f32(dL_dout_features, "dL_dout_features", dev)
     _on_device(radii, "radii", dev, torch.int32)
     for name, buf in (("geomBuffer", geomBuffer), ("binningBuffer", binningBuffer), ("imageBuffer", imageBuffer)):
         _on_device(buf, name, dev, torch.uint8)
@@ -422,6 +502,9 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     # "rgb" exchange mode (multiview.py): an allocator that hands out a (P,3) "sh_rgb" tensor asks for the clamp-masked
     # colour gradient INSTEAD of the (P,M,3) SH gradient; dL_dsh is then returned as None and rebuilt after the exchange
     dL_drgb = grad_alloc("sh_rgb", (P, 3), False) if (grad_alloc is not None and M != 0) else None
+    if dL_drgb is not None and feat_C:
+        raise RuntimeError("diff_gaussian_rasterization: feature gradients are not supported with the colour-gradient exchange "
+                           "(the grad_allocator's \"sh_rgb\" mode)")
     dL_dsh = None if dL_drgb is not None else _alloc(grad_alloc, "sh", (P, M, 3), M == 0, dev)
     dL_dscales = _alloc(grad_alloc, "scales", (P, 3), not has_scales, dev)
     dL_drotations = _alloc(grad_alloc, "rotations", (P, 4), not has_scales, dev)
@@ -431,6 +514,9 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
         row_state = None
     if row_state is not None and dL_ddepth is not None:
         raise RuntimeError("diff_gaussian_rasterization: depth gradients are not supported with persistent gradient rows "
+                           "(the grad_allocator's \"row_state\" mode)")
+    if row_state is not None and feat_C:
+        raise RuntimeError("diff_gaussian_rasterization: feature gradients are not supported with persistent gradient rows "
                            "(the grad_allocator's \"row_state\" mode)")
     if row_state is not None and pose_grad_out is not None:
         raise RuntimeError("diff_gaussian_rasterization: camera gradients are not supported with persistent gradient rows "
@@ -478,6 +564,12 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
         if abs_grad_out is not None:  # moves the two columns out of the table (and zeroes them) in front of K8+K9
             _native.check("gsr_abs_grad_take", L.gsr_abs_grad_take(_stream(dev), P, acc.data_ptr(), touched.data_ptr(),
                                                                    abs_grad_out.data_ptr()))
+        if feat_C:  # adds the feature image's share into the rows K7 left (and dL/dfeatures into the caller's zeroed tensor)
+            _native.check("gsr_blend_backward_features", L.gsr_blend_backward_features(
+                _stream(dev), P, int(R), W, H, feat_C, geomBuffer.data_ptr(), _ptr(binningBuffer), imageBuffer.data_ptr(),
+                features.data_ptr(), dL_dfeat_img.data_ptr(), acc.data_ptr(), feature_grad_out.data_ptr(),
+                flags & _FEATURE_FLAGS))
+            torch.autograd.graph.increment_version(feature_grad_out)  # written through a raw pointer
         if pose_grad_out is not None:  # reads the rows K7 left, in front of K8+K9 (which may clean them); changes nothing
             nbytes = ctypes.c_size_t(0)
             _native.check("gsr_pose_workspace_size", L.gsr_pose_workspace_size(P, ctypes.byref(nbytes)))

@@ -62,7 +62,10 @@ def _call_native(fn, args, debug: bool, dump_path: str, message: str):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, aux_colors=None, return_alpha=False, viewmatrix=None, projmatrix=None, campos=None):
+                raster_settings, aux_colors=None, return_alpha=False, viewmatrix=None, projmatrix=None, campos=None,
+                features=None):
+        # (features: (P,C) per-Gaussian features, composited into a differentiable (C,H,W) image that is returned last --
+        #  passed by a render with `features=` only; every other render passes the argument tuple it always passed)
         # (viewmatrix, projmatrix, campos: rs.viewmatrix / rs.projmatrix / rs.campos once more, as inputs autograd can see --
         #  passed under FLAG_POSE_GRAD only, and only when one of them requires a gradient: _pose_inputs)
         rs = raster_settings
@@ -88,16 +91,23 @@ class _RasterizeGaussians(torch.autograd.Function):
         # view reuse (_reuse.py): a following colour-override render of this view runs the blend kernel on this state
         _reuse.remember(rs, flags, means3D, scales, rotations, opacities, cov3Ds_precomp, num_rendered, geomBuffer,
                         binningBuffer, imgBuffer, radii, depth)
+        ctx.gsr_features = features is not None
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
-                              binningBuffer, imgBuffer)
+                              binningBuffer, imgBuffer, *((features,) if features is not None else ()))
         ctx.mark_non_differentiable(radii)
         # radii / depth never carry a gradient: do not let autograd fill zero tensors for them on every backward
         ctx.set_materialize_grads(False)
         # extension: the alpha image 1 - final_T out of the image state K6 just left, a differentiable last output
         ctx.gsr_alpha = return_alpha
         alpha = (_C.alpha_image(imgBuffer, rs.image_height, rs.image_width),) if return_alpha else ()
+        if features is not None:
+            # extension: the feature image, one forward kernel on the state K6 just left; differentiable, the last output
+            alpha = alpha + (_call_native(
+                run(_C.rasterize_features), (features.detach(), num_rendered, geomBuffer, binningBuffer, imgBuffer,
+                                             rs.image_height, rs.image_width, rs.debug), rs.debug, "snapshot_fw.dump",
+                "\nAn error occured in forward. Please forward snapshot_fw.dump for debugging."),)
         if aux_colors is None:
-            return (color, radii, depth, alpha[0]) if return_alpha else (color, radii, depth)
+            return (color, radii, depth) + alpha
         # extension: a second, gradient-free image of the same view with other colours (K6 only)
         aux = _call_native(run(_C.rasterize_gaussians_aux),
                            (rs.bg, aux_colors.detach(), num_rendered, geomBuffer, binningBuffer, imgBuffer, rs.image_height,
@@ -107,25 +117,31 @@ class _RasterizeGaussians(torch.autograd.Function):
         return (color, radii, depth, aux) + alpha
 
     @staticmethod
-    def backward(ctx, grad_out_color, grad_radii, grad_depth, *grad_rest):  # (grad_rest: of aux and / or alpha, in that order)
+    def backward(ctx, grad_out_color, grad_radii, grad_depth, *grad_rest):  # (grad_rest: of aux, alpha, features, in that order)
         # grad_radii is ignored exactly as in the reference (:137, :155-177); so is grad_depth -- depth is a forward-only
         # output -- unless this render ran with FLAG_DEPTH_GRAD (gaussianeditor_amd.set_depth_grad)
         (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
-         imgBuffer) = ctx.saved_tensors
+         imgBuffer) = ctx.saved_tensors[:10]
+        feats = None
+        if ctx.gsr_features:  # the feature image is the last output, the alpha image the one in front of it
+            feats = (ctx.saved_tensors[10], grad_rest[-1])
+            grad_rest = grad_rest[:-1]
         return _backward(ctx, (means3D, sh, colors_precomp, scales, rotations, cov3Ds_precomp),
                          (ctx.num_rendered, radii, geomBuffer, binningBuffer, imgBuffer),
-                         (grad_out_color, grad_depth, grad_rest[-1] if ctx.gsr_alpha else None), dump=True,
+                         (grad_out_color, grad_depth, grad_rest[-1] if ctx.gsr_alpha else None), dump=True, features=feats,
                          grad_allocator=getattr(ctx, "gsr_grad_allocator", None))
 
 
-def _backward(ctx, inputs, state, grads, dump=False, **route_kw):
+def _backward(ctx, inputs, state, grads, dump=False, features=None, **route_kw):
     """The backward of both autograd functions: _C.rasterize_gaussians_backward on `inputs` (means3D, sh, colors_precomp, scales,
     rotations, cov3Ds_precomp) and the `state` their forward left (num_rendered, radii, geomBuffer, binningBuffer, imgBuffer),
     with `grads`, the gradients of the colour, depth and alpha outputs -> one gradient slot per forward() input (:213-225).
     The extension keywords are passed only where there is something to pass -- a depth gradient of a render that ran with
     FLAG_DEPTH_GRAD (depth is a forward-only output otherwise), the tensor for the absolute screen-space gradient under
     FLAG_ABS_GRAD (a new (P,3) one per backward, assigned to `means2D.absgrad`), a gradient of an alpha image that was
-    returned AND used; `route_kw` likewise -- so that every other backward is the reference's call, to any `_C` backend."""
+    returned AND used, `features` = (the features, the gradient of their image) of a render with `features=` whose feature
+    image was used (one more gradient slot then, the last); `route_kw` likewise -- so that every other backward is the
+    reference's call, to any `_C` backend."""
     rs, flags = ctx.raster_settings, ctx.gsr_flags
     means3D, sh, colors_precomp, scales, rotations, cov3Ds_precomp = inputs
     num_rendered, radii, geomBuffer, binningBuffer, imgBuffer = state
@@ -141,7 +157,11 @@ def _backward(ctx, inputs, state, grads, dump=False, **route_kw):
         abs_grad = kw["abs_grad_out"] = torch.empty((means3D.shape[0], 3), dtype=torch.float32, device=means3D.device)
     if grad_alpha is not None:
         kw["dL_dout_alpha"] = grad_alpha
-    if grad_out_color is None:  # only the depth and / or alpha output was used downstream
+    grad_features = None
+    if features is not None and features[1] is not None:
+        grad_features = torch.zeros_like(features[0], memory_format=torch.contiguous_format)  # (added into: zeroed here)
+        kw.update(features=features[0], dL_dout_features=features[1], feature_grad_out=grad_features)
+    if grad_out_color is None:  # only the depth, alpha and / or feature output was used downstream
         grad_out_color = torch.zeros((3, rs.image_height, rs.image_width), dtype=torch.float32, device=means3D.device)
     # argument order of _C.rasterize_gaussians_backward (rasterize_points.h:38-60)
     args = (rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
@@ -155,12 +175,13 @@ def _backward(ctx, inputs, state, grads, dump=False, **route_kw):
         ctx.gsr_means2D.absgrad = abs_grad
     out = (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
            grad_cov3Ds_precomp, None, None, None)
+    tail = () if features is None else (grad_features,)  # (input 14; the camera tensors keep 11 .. 13)
     if pose is None:
-        return out
+        return out + ((None, None, None) + tail if tail else ())
     # three more slots, in the layout of the tensors themselves; None for one that does not require a gradient
     need = ctx.needs_input_grad[11:14]
     parts = ((pose[:16], rs.viewmatrix), (pose[16:32], rs.projmatrix), (pose[32:], rs.campos))
-    return out + tuple(g.reshape(t.shape) if n else None for (g, t), n in zip(parts, need))
+    return out + tuple(g.reshape(t.shape) if n else None for (g, t), n in zip(parts, need)) + tail
 
 
 class _ReusedRender(torch.autograd.Function):
@@ -214,6 +235,15 @@ def _pose_inputs(rs):
     return cams
 
 
+def _rasterize_with_features(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                             raster_settings, aux_colors, return_alpha, features):
+    """A render with `features=`: always in full (never served by view reuse; it may be remembered), the features a
+    trailing input autograd sees, behind the camera tensors' slots."""
+    pose = _pose_inputs(raster_settings) or (None, None, None)
+    return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
+                                     raster_settings, aux_colors, bool(return_alpha), *pose, features)
+
+
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         raster_settings, return_alpha=False):
     # (return_alpha: the alpha image as an additional last value; the extra arguments only then, so that a call without it
@@ -264,13 +294,17 @@ class GaussianRasterizer(nn.Module):
             return _C.mark_visible(positions, rs.viewmatrix, rs.projmatrix)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, aux_colors=None, return_alpha=False):
-        """Reference signature (:258-309) plus two extensions.  With `aux_colors` (P,3) a second image of the same
+                cov3D_precomp=None, aux_colors=None, return_alpha=False, features=None):
+        """Reference signature (:258-309) plus three extensions.  With `aux_colors` (P,3) a second image of the same
         view, blended with those colours instead, is returned as a fourth value (forward only, no gradient).  It is
         what a second call with colors_precomp=aux_colors would render, at the cost of the blend kernel alone.
         With `return_alpha=True` the alpha image (1,H,W) -- accumulated opacity, 1 - the final transmittance -- is an
         additional LAST value, (color, radii, depth, alpha) or (color, radii, depth, aux, alpha), differentiable like the
-        colour.  The arity depends on these two arguments alone, never on process state."""
+        colour.  With `features` (P,C) float32, 1 <= C <= 256, the feature image (C,H,W) -- those per-Gaussian features
+        composited with the view's alpha on background 0, every 16 channels in one walk of the tile lists -- is appended
+        as the LAST value: (color, radii, depth[, aux][, alpha], feature_image).  It is differentiable with respect to
+        `features`, means3D, means2D, opacities and scales / rotations / cov3D_precomp, not with respect to shs /
+        colors_precomp.  The arity depends on these three arguments alone, never on process state."""
         if (shs is None) == (colors_precomp is None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")  # sic, :271-276
         has_sr = scales is not None or rotations is not None
@@ -282,6 +316,18 @@ class GaussianRasterizer(nn.Module):
         scales = _absent(means3D) if scales is None else scales
         rotations = _absent(means3D) if rotations is None else rotations
         cov3D_precomp = _absent(means3D) if cov3D_precomp is None else cov3D_precomp
+        if features is not None:
+            if not isinstance(features, torch.Tensor) or features.dtype != torch.float32:
+                raise RuntimeError("diff_gaussian_rasterization: `features` must be a float32 tensor, got "
+                                   f"{getattr(features, 'dtype', type(features).__name__)}")
+            if features.dim() != 2 or features.shape[0] != means3D.shape[0] or not 1 <= features.shape[1] <= 256:
+                raise RuntimeError(f"diff_gaussian_rasterization: `features` must be a ({means3D.shape[0]}, C) tensor with "
+                                   f"1 <= C <= 256, got {tuple(features.shape)}")
+            if features.device != means3D.device:
+                raise RuntimeError(f"diff_gaussian_rasterization: `features` is on {features.device} but `means3D` is on "
+                                   f"{means3D.device}")
+            return _rasterize_with_features(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+                                            cov3D_precomp, self.raster_settings, aux_colors, return_alpha, features)
         if aux_colors is not None:
             return rasterize_gaussians_with_aux(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                                 cov3D_precomp, self.raster_settings, aux_colors, return_alpha)

@@ -68,14 +68,17 @@ def camera2rasterizer(viewpoint_camera, bg_color: torch.Tensor, sh_degree: int =
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
-           semantic_color=None, return_alpha=None):
+           semantic_color=None, return_alpha=None, features=None):
     """gaussian_renderer/__init__.py:45-150.  Background tensor must be on the GPU.
 
     Extension: `semantic_color` (P,3) adds out["semantic"], the image the reference obtains from a SECOND
     render(..., override_color=semantic_color) of the same camera (threestudio/systems/GassuianEditor.py:183-191,
     webui.py:705-713); here it reuses the preprocessing, sort and tile ranges of this call.
     Extension: `return_alpha` adds out["alpha"], the (1,H,W) accumulated opacity 1 - final transmittance, with a gradient
-    (None: as FLAG_ALPHA_OUT of the calling thread says, gaussianeditor_amd.set_alpha_output; off by default)."""
+    (None: as FLAG_ALPHA_OUT of the calling thread says, gaussianeditor_amd.set_alpha_output; off by default).
+    Extension: `features` (P,C) float32, 1 <= C <= 256, adds out["features"], the (C,H,W) image of those per-Gaussian
+    features composited with this view's alpha on background 0, differentiable with respect to the features and the
+    geometry (GaussianRasterizer.forward)."""
     if return_alpha is None:
         return_alpha = bool(_options.current_flags() & _options.FLAG_ALPHA_OUT)
     xyz = pc.get_xyz
@@ -118,6 +121,7 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         cov3D_precomp=cov3D_precomp,
         **({} if semantic_color is None else {"aux_colors": semantic_color.float()}),
         **({"return_alpha": True} if return_alpha else {}),
+        **({} if features is None else {"features": features}),
     )
     rendered_image, radii, depth = outs[:3]
     out = {
@@ -130,7 +134,9 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     if semantic_color is not None:
         out["semantic"] = outs[3]
     if return_alpha:
-        out["alpha"] = outs[-1]
+        out["alpha"] = outs[-1 if features is None else -2]
+    if features is not None:
+        out["features"] = outs[-1]
     return out
 
 

@@ -69,7 +69,8 @@ extern "C" {
  * L1 + SSIM loss; nothing of the rasterizer changed).  Then, likewise additive: gsr_densify_stats,
  * gsr_densify_workspace_size, gsr_densify_select, gsr_densify_plans, gsr_densify_split_xyz and gsr_densify_keep (the
  * densification policy; nothing existing changed).  Then, likewise additive: gsr_pose_workspace_size and gsr_pose_backward
- * (the camera gradient; no new flag bit, nothing existing changed). */
+ * (the camera gradient; no new flag bit, nothing existing changed).  Then, likewise additive:
+ * GSR_MAX_FEATURE_CHANNELS, gsr_blend_forward_features and gsr_blend_backward_features (the feature image; no new flag bit). */
 #define GSR_ABI_VERSION 6
 /* The blend backward's accumulator table: GSR_ACC_ROW floats (one 64-byte line) per Gaussian, 64-byte aligned.  Columns:
  *   [GSR_ACC_MEAN2D] .x [+1] .y of dL_dmean2D      (backward.cu:545-546)
@@ -409,6 +410,40 @@ int gsr_alpha_image(void* stream, int W, int H, const void* image, float* out_al
 int gsr_blend_backward_alpha(void* stream, int P, int64_t R, int W, int H, const float* bg, const void* geom,
                              const void* binning, const void* image, const float* dL_dpix, const float* dL_ddepth,
                              const float* dL_dalpha, float* acc, uint8_t* touched, unsigned flags);
+
+/* Feature image (opt-in; no flag bit: the call says what is asked): per-Gaussian feature vectors of C channels, the N-D
+ * `colors` of current 3DGS rasterizers, alpha-composited through the geometry / binning state an earlier gsr_preprocess +
+ * gsr_bin left, with the alpha of gsr_blend_forward under the view's flags.  1 <= C <= GSR_MAX_FEATURE_CHANNELS; the
+ * channels are walked in blocks of 16 (the last one may be partial): alpha and T of a (pixel, entry) pair are evaluated once
+ * per block.  The reference has no such image.
+ * gsr_blend_forward_features: features (P,C) row-major -> out_features (C,H,W) = sum_i f_ic alpha_i T_i, fully written
+ *   (exact zeros where nothing is blended: the background is zero; a caller composites its own with gsr_alpha_image).
+ *   Channel c equals, as floats, channel c % 3 of gsr_blend_forward_aux with colors = features[:, 3 (c / 3) : + 3] (zero
+ *   padded) and bg = 0.  Like that render it leaves final_T / n_contrib in `image` untouched.  P == 0 or R == 0: zeros.
+ * gsr_blend_backward_features: dL_dfeature_image (C,H,W) in.  Walks the first n_contrib entries of every pixel back to
+ *   front from final_T and ADDS
+ *     - the geometry share of the feature image's gradient into the columns GSR_ACC_MEAN2D, GSR_ACC_OPACITY, GSR_ACC_CONIC
+ *       of `acc`, the accumulator table the view's colour backward adds into, in that backward's conventions
+ *       (GSR_ACC_COLOR, GSR_ACC_DEPTH and GSR_ACC_ABS2D are not written);
+ *     - dL/df into dL_dfeatures (P,C), which the caller zeroes (coarse-grained memory, as `acc`); rows of Gaussians no
+ *       pixel blends stay untouched.
+ *   Called AFTER the blend half of the view's colour backward (gsr_blend_backward[_depth|_alpha], which is what clears a
+ *   table that is not kept), after gsr_abs_grad_take if that is called, and BEFORE gsr_pose_backward and the view's K8+K9
+ *   entry point, on the same stream: the camera gradient and every geometry gradient then hold the feature image's share.
+ *   It only adds to rows of Gaussians in a tile list (radii > 0), so K8+K9 with GSR_FLAG_ACC_SELF_CLEAN leaves the table
+ *   zero as it does without it.  It uses no checkpoints and its work list holds no list segments (the checkpoints hold no
+ *   features): views with long lists take longer than gsr_blend_backward, as with gsr_blend_backward_depth.  The absolute
+ *   sums of GSR_FLAG_ABS_GRAD do not hold the feature image's share.  P == 0 or R == 0: nothing is launched.
+ * flags: 0 | GSR_FLAG_FAST_EXP | GSR_FLAG_ANTIALIAS | GSR_FLAG_TILE_BOUNDS_ALPHA | GSR_FLAG_SHARED_SIMDS, the view's (the last
+ *   three change nothing here: what is blended is already the effective opacity of the lists as they are); any other bit is
+ *   GSR_ERR_BAD_ARGUMENT.  Arguments are checked before any device work: a NULL pointer, C outside 1 .. 256 and an `acc`
+ *   that is not 64-byte aligned are GSR_ERR_BAD_ARGUMENT. */
+#define GSR_MAX_FEATURE_CHANNELS 256
+int gsr_blend_forward_features(void* stream, int P, int64_t R, int W, int H, int C, const void* geom, const void* binning,
+                               void* image, const float* features, float* out_features, unsigned flags);
+int gsr_blend_backward_features(void* stream, int P, int64_t R, int W, int H, int C, const void* geom, const void* binning,
+                                const void* image, const float* features, const float* dL_dfeature_image,
+                                float* acc, float* dL_dfeatures, unsigned flags);
 
 /* Multi-GPU exchange support (gaussianeditor_amd/multiview.py).  Per view the SH gradient is
  * rank one, dL_dsh[k] = c_k(dir) * dL_dRGB with dir = normalize(mean - campos) (backward.cu:44-98), so ranks exchange
