@@ -126,6 +126,25 @@ __device__ __forceinline__ uint32_t first_item_of_block(uint32_t units, uint32_t
   return (slot & 1u) ? (slot + 1u) * n - 1u - u : slot * n + u;
 }
 
+// HW_REG_XCC_ID[3:0]: the XCD the wave runs on (the queue it serves: & 7; the profile records keep all four bits)
+__device__ __forceinline__ uint32_t xcc_id() { return (uint32_t)__builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 20); }
+// A kernel argument's float once per kernel, in a scalar register: `bg` of K6 / K7.  (Read at its uses, hipcc cannot prove
+// that the image stores do not alias it: it re-loaded each component between two stores and waited for everything in flight
+// each time.)
+__device__ __forceinline__ float wave_uniform(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
+// The pixels of a whole tile, quadrant by quadrant: f(pixel index, H W) for every lane whose pixel lies inside the image (the
+// empty-tile items of the forward kernels: background only / zeros).
+template <class F>
+__device__ __forceinline__ void for_each_pixel_of_tile(const BlendArgs& a, uint32_t tile, F&& f) {
+  for (uint32_t q = 0; q < 4; ++q) {
+    PixelWave pw;
+    if (!setup_wave(a, tile, q, pw)) continue;
+    if (pw.inside) f((size_t)pw.py * a.W + pw.px, (size_t)a.H * a.W);
+  }
+}
+
 template <int SPLIT, class F>
 __device__ __forceinline__ void run_work_queue(const BlendArgs& a, bool with_empty, F&& item) {
   const uint32_t nwork = a.work_meta[0];
@@ -155,7 +174,7 @@ __device__ __forceinline__ void run_work_queue(const BlendArgs& a, bool with_emp
   const uint32_t q0 = first_item_of_block((uint32_t)a.units, x0, base);
   (void)run_item(x0, q0);
   // then serve the queue of the XCD the wave really runs on (HW_REG_XCC_ID; equal to x0 on this chip)
-  const uint32_t x = (uint32_t)__builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 20) & 7u;
+  const uint32_t x = xcc_id() & 7u;
   uint32_t* head = a.queue + x * QUEUE_STRIDE;
   for (;;) {
     uint32_t q = 0;
@@ -505,6 +524,118 @@ struct ChunkWalker {
   }
 };
 
+// ---- Shared traversal pieces: chunk_cull (all five blend kernels), pair_alpha (K6, K12, the feature forward), the walk ----
+// The chunk's cull test: may this lane's entry `e` of the chunk (`in_chunk`: the lane holds one the item walks) reach the
+// bounding box of the pixels that are still live (`live_m`, not 0; (ox, oy): origin of the wave's 8x8 lane grid)?
+__device__ __forceinline__ bool chunk_cull(uint64_t live_m, float ox, float oy, bool in_chunk, const Entry& e) {
+  const LiveBox lb = live_pixel_box(live_m, ox, oy);
+  return in_chunk && can_touch_quad(e.r0, e.r1, lb.x0, lb.y0, lb.w, lb.h);
+}
+// From the 12 geometry floats of a staged pair -- q0, q1, q2 = {hA0,hA1,nB0,nB1} {hC0,hC1,op0,op1} {x0,x1,y0,y1}, conic pre-scaled:
+// (-0.5 A, -B, -0.5 C), exact; K6's FWD_PAIR begins with them --: alpha of both entries for the pixel, ZERO where the pixel skips
+// the entry (power > 0 or alpha < 1/255), so that 1 - alpha = 1 and T (1 - alpha) = T exactly, and 1 - alpha.
+// blend_power_prescaled and the exponential on both entries at once (packed binary32, the scalar forms' roundings).
+// (The float4s BY VALUE: with `const float4&` parameters every K6 instantiation came out differently.)
+constexpr int PAIR_GEOM = 12;
+template <bool FAST>
+__device__ __forceinline__ void pair_alpha(const float4 q0, const float4 q1, const float4 q2, const f32x2 pfx2, const f32x2 pfy2,
+                                           float* ae, float* om) {
+  const f32x2 hA = {q0.x, q0.y}, nB = {q0.z, q0.w}, hC = {q1.x, q1.y}, op = {q1.z, q1.w};
+  const f32x2 dx = f32x2{q2.x, q2.y} - pfx2, dy = f32x2{q2.z, q2.w} - pfy2;
+  const f32x2 a_ = (hA * dx) * dx;
+  const f32x2 s_ = __builtin_elementwise_fma(hC * dy, dy, a_);
+  const f32x2 power = __builtin_elementwise_fma(nB * dx, dy, s_);
+  const f32x2 ao = op * blend_exp2<FAST>(power);
+  const float a0 = fminf(0.99f, ao.x), a1 = fminf(0.99f, ao.y);
+  const float g0 = (power.x > 0.0f) ? 0.0f : a0, g1 = (power.y > 0.0f) ? 0.0f : a1;
+  const f32x2 a2 = {(g0 < 1.0f / 255.0f) ? 0.0f : g0, (g1 < 1.0f / 255.0f) ? 0.0f : g1};
+  const f32x2 o2 = f32x2{1.0f, 1.0f} - a2;
+  ae[0] = a2.x;
+  ae[1] = a2.y;
+  om[0] = o2.x;
+  om[1] = o2.y;
+}
+// K12 and the feature forward: ONE walk over an item's list, front to back -- ChunkWalker, the cull against the live pixels'
+// box, survivors compacted in order and staged in pairs of PAIR_GEOM floats (the caller's `stage(slot, entry)` adds its
+// payload: an id, a feature row), four survivors per iteration evaluated two per packed instruction, the serial part on
+// selects as in K6's fast path: Ts = T for a live pixel, -T for one that is done.
+//   entry skipped for this pixel (ae = 0, om = 1): test_T = T exactly, no hit;
+//   T (1 - alpha) < 0.0001: the pixel is done BEFORE this entry counts (forward.cu:349-354, apply_weights.cu:318-323), Ts := -T;
+//   pixel done: test_T <= 0, nothing changes.
+// Per evaluated group `group(j, hit, w)` gets, for the entries j .. j + 3 of the chunk's survivors, whether this lane's pixel
+// blends the entry and, where it does, its weight alpha T (two arrays: K12 never forms the weights -- as the sign of one masked
+// weight array the test cost its groups four multiplies and selects); behind the chunk's groups `chunk_end(n)` gets the number of survivors whose groups
+// were evaluated (all of them unless every pixel saturated on the way).  (Rounds 1-5 of K12 walked one survivor per iteration
+// with a ballot, a branch and a 64-lane reduction per entry: 182 -> 122 us per 512 x 512 view at 10^6 Gaussians,
+// profiles/r06_j_trace_weights.md.)  One-wave workgroups: the barriers around the staging are free.
+template <bool FAST, class Stage, class Group, class ChunkEnd>
+__device__ __forceinline__ void walk_front_to_back(const BlendArgs& a, const PixelWave& pw, const uint2 range, Stage&& stage,
+                                                   Group&& group, ChunkEnd&& chunk_end) {
+  __shared__ __align__(16) float spair[WAVE / 2][PAIR_GEOM];
+  if (range.y <= range.x) return;
+  const int lane = lane_id();
+  const float pfx = (float)pw.px, pfy = (float)pw.py;
+  const f32x2 pfx2 = {pfx, pfx}, pfy2 = {pfy, pfy};
+  const uint64_t lt_mask = (1ull << lane) - 1ull;
+  float Ts = pw.inside ? 1.0f : -1.0f;
+  ChunkWalker<true> walk(a, range.x, range.y - range.x);
+  for (; walk.valid(); walk.advance()) {
+    const uint64_t live_m = __ballot(Ts > 0.0f);
+    if (live_m == 0) break;
+    const bool keep = chunk_cull(live_m, pfx - (float)(lane & 7), pfy - (float)(lane >> 3), (uint32_t)lane < walk.chunk_size(), walk.cur);
+    const uint64_t km = __ballot(keep);
+    if (km == 0) continue;
+    const uint32_t n = (uint32_t)__popcll(km);
+    const uint32_t n4 = (n + GROUP - 1) & ~(uint32_t)(GROUP - 1);
+    __syncthreads();
+    if (keep) {
+      const uint32_t slot = (uint32_t)__popcll(km & lt_mask);
+      float* q = &spair[slot >> 1][slot & 1u];
+      q[0] = -0.5f * walk.cur.r0.x;
+      q[2] = -walk.cur.r0.y;
+      q[4] = -0.5f * walk.cur.r0.z;
+      q[6] = walk.cur.r0.w;
+      q[8] = walk.cur.r1.x;
+      q[10] = walk.cur.r1.y;
+      stage(slot, walk.cur);
+    }
+    if ((uint32_t)lane >= n && (uint32_t)lane < n4) {
+      // null entries pad the survivors to a multiple of GROUP: opacity 0 => alpha 0 => never a hit
+      float* q = &spair[lane >> 1][lane & 1];
+      q[0] = q[2] = q[4] = q[6] = q[8] = q[10] = 0.f;
+    }
+    __syncthreads();
+    uint32_t evaluated = n;  // survivors whose groups were evaluated (all of them unless every pixel saturated on the way)
+    for (uint32_t j = 0; j < n4; j += GROUP) {
+      if (__all(Ts < 0.0f)) {
+        evaluated = j;
+        break;
+      }
+      float ae[GROUP], om[GROUP], w[GROUP];
+      bool hit[GROUP];
+#pragma unroll
+      for (int pp = 0; pp < GROUP / 2; ++pp) {
+        const float* q = &spair[(j >> 1) + pp][0];
+        pair_alpha<FAST>(*reinterpret_cast<const float4*>(q), *reinterpret_cast<const float4*>(q + 4),
+                         *reinterpret_cast<const float4*>(q + 8), pfx2, pfy2, ae + 2 * pp, om + 2 * pp);
+      }
+      // (the four footprints pinned ahead of the serial part, as in K6)
+#pragma unroll
+      for (int u = 0; u < GROUP; ++u) asm volatile("" : "+v"(ae[u]), "+v"(om[u]));
+#pragma unroll
+      for (int u = 0; u < GROUP; ++u) {
+        const float test_T = Ts * om[u];
+        const bool A = !(test_T < 0.0001f);
+        hit[u] = A && ae[u] > 0.0f;
+        w[u] = ae[u] * Ts;
+        Ts = A ? test_T : -__builtin_fabsf(Ts);
+      }
+      group(j, hit, w);
+    }
+    chunk_end(min(n, evaluated));
+  }
+}
+
 // ----------------------------------------------------------------------------------
 // K6: renderCUDA (forward), DGR/cuda_rasterizer/forward.cu:261-379.
 // ----------------------------------------------------------------------------------
@@ -589,8 +720,7 @@ __device__ __forceinline__ void forward_item(const BlendArgs& a, uint32_t tile, 
         tc0 = __builtin_amdgcn_s_memtime();
         prof_cyc[2]++;  // chunks walked
       }
-      const LiveBox lb = live_pixel_box(live_m, pfx - (float)(lane & 7), pfy - (float)(lane >> 3));
-      const bool keep = ((uint32_t)lane < walk.chunk_size()) && can_touch_quad(walk.cur.r0, walk.cur.r1, lb.x0, lb.y0, lb.w, lb.h);
+      const bool keep = chunk_cull(live_m, pfx - (float)(lane & 7), pfy - (float)(lane >> 3), (uint32_t)lane < walk.chunk_size(), walk.cur);
       const uint64_t m = __ballot(keep);
       if (PROFILE) prof_cyc[3] += __builtin_amdgcn_s_memtime() - tc0;  // wait for the chunk's records + cull
       if (m == 0) continue;
@@ -641,20 +771,9 @@ __device__ __forceinline__ void forward_item(const BlendArgs& a, uint32_t tile, 
                          q2 = *reinterpret_cast<const float4*>(q + 8), c0 = *reinterpret_cast<const float4*>(q + 12),
                          c1 = *reinterpret_cast<const float4*>(q + 16);
             const float2 ps = *reinterpret_cast<const float2*>(q + 20);
-            const f32x2 hA = {q0.x, q0.y}, nB = {q0.z, q0.w}, hC = {q1.x, q1.y}, op = {q1.z, q1.w};
-            const f32x2 dx = f32x2{q2.x, q2.y} - pfx2, dy = f32x2{q2.z, q2.w} - pfy2;
-            const f32x2 a_ = (hA * dx) * dx;
-            const f32x2 s_ = __builtin_elementwise_fma(hC * dy, dy, a_);
-            const f32x2 power = __builtin_elementwise_fma(nB * dx, dy, s_);
-            const f32x2 ao = op * blend_exp2<FAST>(power);
-            const float a0 = fminf(0.99f, ao.x), a1 = fminf(0.99f, ao.y);
-            const float g0 = (power.x > 0.0f) ? 0.0f : a0, g1 = (power.y > 0.0f) ? 0.0f : a1;
-            const f32x2 a2 = {(g0 < 1.0f / 255.0f) ? 0.0f : g0, (g1 < 1.0f / 255.0f) ? 0.0f : g1};
-            const f32x2 o2 = f32x2{1.0f, 1.0f} - a2;
-            ae[2 * pp] = a2.x;
-            ae[2 * pp + 1] = a2.y;
-            om[2 * pp] = o2.x;
-            om[2 * pp + 1] = o2.y;
+            // (the pair's loads all stand in front of the arithmetic, in this order: with the colour loads behind it the
+            //  CKPT and PROFILE kernels came out differently)
+            pair_alpha<FAST>(q0, q1, q2, pfx2, pfy2, ae + 2 * pp, om + 2 * pp);
             rg[2 * pp] = f32x2{c0.x, c0.y};
             bz[2 * pp] = f32x2{c0.z, c0.w};
             rg[2 * pp + 1] = f32x2{c1.x, c1.y};
@@ -666,6 +785,8 @@ __device__ __forceinline__ void forward_item(const BlendArgs& a, uint32_t tile, 
           for (int u = 0; u < GROUP; ++u) asm volatile("" : "+v"(ae[u]), "+v"(om[u]));
 #pragma unroll
           for (int u = 0; u < GROUP; ++u) {
+            // (the walk's Ts step, written out: as a helper -- by reference, a struct by value, a callback in the middle -- it
+            //  moved every K6 instantiation)
             const float test_T = Ts * om[u];
             const bool A = !(test_T < 0.0001f);
             const float w = ae[u] * Ts;
@@ -792,11 +913,7 @@ __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(4, 4)
   uint32_t prof_visited = 0, prof_items = 0;
   uint64_t prof_cyc[4] = {0, 0, 0, 0};
   if (PROFILE) t_start = __builtin_amdgcn_s_memtime();
-  // `bg` once per kernel, in scalar registers.  (Read at its uses, hipcc cannot prove that the image stores do not alias it:
-  // it re-loaded each component between two stores and waited for everything in flight each time.)
-  const float bg0 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, a.bg[0])));
-  const float bg1 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, a.bg[1])));
-  const float bg2 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, a.bg[2])));
+  const float bg0 = wave_uniform(a.bg[0]), bg1 = wave_uniform(a.bg[1]), bg2 = wave_uniform(a.bg[2]);
   // (always_inline: past a size threshold hipcc stops inlining the item function into the work loop's two call sites and
   //  CALLS it -- the 300-byte argument block then travels through scratch memory)
   run_work_queue<SPLIT>(a, true, [&](uint32_t tile, uint32_t quad, bool empty) __attribute__((always_inline)) {
@@ -805,21 +922,16 @@ __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(4, 4)
       forward_item<PROFILE, AUX, SPLIT, FAST, CKPT>(a, tile, quad, bg0, bg1, bg2, prof_visited, prof_cyc);
     } else {
       // a tile no Gaussian touches: background only (forward.cu:371-378 with an empty range)
-      for (uint32_t q = 0; q < 4; ++q) {
-        PixelWave pw;
-        if (!setup_wave(a, tile, q, pw)) continue;
-        if (pw.inside) {
-          const size_t pix = (size_t)pw.py * a.W + pw.px, HW = (size_t)a.H * a.W;
-          if (a.final_T != nullptr) {
-            a.final_T[pix] = 1.0f;
-            a.n_contrib[pix] = 0u;
-          }
-          a.out_color[pix] = __builtin_fmaf(1.0f, bg0, 0.f);
-          a.out_color[HW + pix] = __builtin_fmaf(1.0f, bg1, 0.f);
-          a.out_color[2 * HW + pix] = __builtin_fmaf(1.0f, bg2, 0.f);
-          if (a.out_depth != nullptr) a.out_depth[pix] = 0.f;
+      for_each_pixel_of_tile(a, tile, [&](size_t pix, size_t HW) __attribute__((always_inline)) {
+        if (a.final_T != nullptr) {
+          a.final_T[pix] = 1.0f;
+          a.n_contrib[pix] = 0u;
         }
-      }
+        a.out_color[pix] = __builtin_fmaf(1.0f, bg0, 0.f);
+        a.out_color[HW + pix] = __builtin_fmaf(1.0f, bg1, 0.f);
+        a.out_color[2 * HW + pix] = __builtin_fmaf(1.0f, bg2, 0.f);
+        if (a.out_depth != nullptr) a.out_depth[pix] = 0.f;
+      });
     }
   });
   if (PROFILE) {
@@ -834,8 +946,7 @@ __global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(4, 4)
       rec[7] = prof_cyc[3];  // cycles: chunk start -> cull ballot (includes the wait for the gathered records)
       rec[0] = t_start;
       rec[1] = t_end;
-      rec[2] = ((uint64_t)__builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 20) << 32) |  // HW_REG_XCC_ID[3:0]
-               (uint64_t)__builtin_amdgcn_s_getreg((32 - 1) << 11 | 0 << 6 | 4);              // HW_REG_HW_ID
+      rec[2] = ((uint64_t)xcc_id() << 32) | (uint64_t)__builtin_amdgcn_s_getreg((32 - 1) << 11 | 0 << 6 | 4);  // HW_REG_HW_ID
       rec[3] = ((uint64_t)prof_items << 32) | (uint64_t)prof_visited;
     }
   }
@@ -875,6 +986,64 @@ static_assert(CK_MAX <= 16, "a stride index must fit the item code's 4 bits");
 constexpr uint32_t BWD_ITEM_TILE = 0x000fffffu;   // (images of up to 2^20 tiles: GSR_MAX_TILES, checked by gsr_blend_backward)
 static_assert(BWD_ITEM_TILE + 1u == (uint32_t)GSR_MAX_TILES, "include/gsr.h states the backward's tile limit");
 
+// ---- What K7 and the feature backward share: the item's descriptor and the per-entry arithmetic ----
+// The item's descriptor from three SCALAR loads (tables of earlier kernels: the work list, the ranges, the walk depths the
+// forward left per quadrant; the scalar path does not queue behind the previous item's last atomics): code first, the other
+// two together.  x = code, y = first position of the tile's list, z = how deep the item's pixels reach into it (the forward's
+// work_maxc: of the whole tile, or of the half the item covers), w = length of the tile's list.  (Round 5's first form had
+// backward_worklist_kernel write whole descriptors: that one-block kernel is a chain of dependent round trips between the
+// forward and the backward -- 14 -> 16-18 us for what costs this kernel, whose waves wait behind three others, nothing
+// measurable.)
+__device__ __forceinline__ uint4 load_backward_item(const BlendArgs& a, uint32_t index) {
+  const uint32_t code = scalar_load(a.bwd_order, index);
+  const uint32_t ctile = code & BWD_ITEM_TILE;
+  const uint2 crange = scalar_load(a.ranges, ctile);
+  const uint4 cmax = scalar_load(reinterpret_cast<const uint4*>(a.work_maxc), ctile);
+  const uint32_t r01 = max(cmax.x, cmax.y), r23 = max(cmax.z, cmax.w);
+  return make_uint4(code, crange.x, (code & BWD_ITEM_HALF) ? ((code & BWD_ITEM_PART) ? r23 : r01) : max(r01, r23), crange.y - crange.x);
+}
+// 1 / (1 - alpha) of the transmittance chain (backward.cu:503): the reciprocal refined by one Newton step.  Along a list of
+// thousands of translucent entries the raw v_rcp_f32's error (1 ulp) accumulated to 1e-5 of a gradient
+// (profiles/r05_d_precision_fuzz.md).
+__device__ __forceinline__ float rcp_refined(float x) {
+  const float r0 = __builtin_amdgcn_rcpf(x);
+  return __builtin_fmaf(r0, __builtin_fmaf(-x, r0, 1.0f), r0);
+}
+// One entry of the collapsed colour recurrence, backward.cu:503-534: the reference keeps accum_rec[ch] and last_color[ch] per
+// channel and forms sum_ch (c[ch] - accum_rec[ch]) * dL_dpixel[ch]; the recurrence is linear and dL_dpixel is constant for the
+// pixel, so B = sum_ch accum_rec[ch] * dL_dpixel[ch] obeys the same recurrence with the scalar cdot = sum_ch c[ch] *
+// dL_dpixel[ch] in place of the colour.  A lane that does not contribute (`on` false, alpha = 0) runs the same arithmetic: its
+// transmittance is multiplied by rcp(1) = 1 exactly, the pending fold of (last_alpha, last_cdot) into B happens now instead
+// of at the lane's next contributor (same operands, same value; afterwards last_alpha = 0 makes the fold a no-op) -- three
+// selects per entry instead of six.  Hands back the new T and B and dL/dalpha WITHOUT the background's share (K7 adds its own);
+// the caller then sets last_alpha = alpha and keeps last_cdot by a select (last_cdot = on ? cdot : last_cdot: a NaN colour of
+// a skipped entry must not enter B as 0 * NaN).  State in and out BY VALUE: with `float&` parameters every K7 instantiation
+// came out differently.
+struct RecStep {
+  float T, B_acc, dL_dalpha;
+};
+__device__ __forceinline__ RecStep accum_rec_step(float T, float B_acc, float last_alpha, float last_cdot, float inv_one_m, float cdot) {
+#pragma clang fp contract(fast)  // gradients are tolerance-checked (<= 1e-5), not bit-compared: let a*b+c fuse here
+  RecStep r;
+  r.T = T * inv_one_m;                                 // T / (1 - alpha), backward.cu:503
+  r.B_acc = B_acc + last_alpha * (last_cdot - B_acc);  // accum_rec update, backward.cu:515
+  r.dL_dalpha = (cdot - r.B_acc) * r.T;
+  return r;
+}
+// The six raw geometry moments of q = G dL/dalpha of entry u of a group (dx, dy: the entry's mean relative to the pixel).  Per
+// lane only the MOMENTS are formed; every per-entry constant of backward.cu:538-554 (conic, opacity, 0.5*W, 0.5*H, -0.5) is
+// applied once per (tile, entry) by the flush.
+template <int NM>
+__device__ __forceinline__ void geometry_moments(float (&v)[NM][GROUP], int u, float q, float dx, float dy) {
+#pragma clang fp contract(fast)
+  const float qx = q * dx, qy = q * dy;
+  v[0][u] = q;
+  v[1][u] = qx;
+  v[2][u] = qy;
+  v[3][u] = qx * dx;
+  v[4][u] = qx * dy;
+  v[5][u] = qy * dy;
+}
 
 // One tile, processed by a 4-wave workgroup (wave w = quadrant w).  The four waves walk the tile's list
 // back to front in the SAME 64-entry chunks; each wave culls / compacts / evaluates the chunk for its own
@@ -1087,10 +1256,7 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
     const uint32_t chunk_lo = seg_hi - min(seg_hi - seg_lo, (walk.chunk + 1u) * (uint32_t)WAVE);
     const uint64_t live_m = __ballot(last_contributor > chunk_lo);
     bool keep = false;
-    if (live_m != 0) {
-      const LiveBox lb = live_pixel_box(live_m, qx0, qy0);
-      keep = ((uint32_t)lane < csize) && (pos < maxc) && can_touch_quad(walk.cur.r0, walk.cur.r1, lb.x0, lb.y0, lb.w, lb.h);
-    }
+    if (live_m != 0) keep = chunk_cull(live_m, qx0, qy0, ((uint32_t)lane < csize) && (pos < maxc), walk.cur);
     const uint64_t m = __ballot(keep);
     const uint32_t cnt = (uint32_t)__popcll(m);
     const uint32_t cnt4 = (cnt + GROUP - 1) & ~(uint32_t)(GROUP - 1);
@@ -1139,48 +1305,28 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
 #pragma clang fp contract(fast)  // gradients are tolerance-checked (<= 1e-5), not bit-compared: let a*b+c fuse here
 #pragma unroll
         for (int u = 0; u < GROUP; ++u) {
-          // backward.cu:503-534 with the colour recurrence collapsed: the reference keeps accum_rec[ch] and
-          // last_color[ch] per channel and forms sum_ch (c[ch] - accum_rec[ch]) * dL_dpixel[ch]; the recurrence is
-          // linear and dL_dpixel is constant for the pixel, so B = sum_ch accum_rec[ch] * dL_dpixel[ch] obeys the
-          // same recurrence with the scalar cdot = sum_ch c[ch] * dL_dpixel[ch] in place of the colour.  Lanes that
-          // do not contribute keep their state through selects and hand zeros on.
-          // A lane that does not contribute runs the same arithmetic with alpha = 0: its transmittance is multiplied
-          // by rcp(1) = 1 exactly, the pending fold of (last_alpha, last_cdot) into B happens now instead of at the
-          // lane's next contributor (same operands, same value; afterwards last_alpha = 0 makes the fold a no-op),
-          // and its moments are zero -- three selects per entry instead of six.
+          // (accum_rec_step: a lane that does not contribute keeps its state through selects and hands zeros on)
           const bool on = contrib[u];
           const float alpha = on ? al[u] : 0.f;
-          // 1 / (1 - alpha) of the transmittance chain (backward.cu:503): the reciprocal refined by one Newton step.  Along a
-          // list of thousands of translucent entries the raw v_rcp_f32's error (1 ulp) accumulated to 1e-5 of a gradient
-          // (profiles/r05_d_precision_fuzz.md).
-          const float one_m = 1.f - alpha;
-          const float r0 = __builtin_amdgcn_rcpf(one_m);
-          const float inv_one_m = __builtin_fmaf(r0, __builtin_fmaf(-one_m, r0, 1.0f), r0);
+          const float inv_one_m = rcp_refined(1.f - alpha);
           // (DEPTH: the depth channel joins the collapsed recurrence, d * dL_dD; its background is 0)
           const float cdot = DEPTH ? cols[u].x * dpx[0] + cols[u].y * dpx[1] + cols[u].z * dpx[2] + dep[u] * dpd
                                    : cols[u].x * dpx[0] + cols[u].y * dpx[1] + cols[u].z * dpx[2];
-          T = T * inv_one_m;                                      // T / (1 - alpha), backward.cu:503
-          B_acc = B_acc + last_alpha * (last_cdot - B_acc);       // accum_rec update, backward.cu:515
-          const float dL_dalpha = (cdot - B_acc) * T + neg_Tfinal_bg * inv_one_m;
+          const RecStep rs = accum_rec_step(T, B_acc, last_alpha, last_cdot, inv_one_m, cdot);
+          T = rs.T;
+          B_acc = rs.B_acc;
+          const float dL_dalpha = rs.dL_dalpha + neg_Tfinal_bg * inv_one_m;
           last_alpha = alpha;
-          last_cdot = on ? cdot : last_cdot;  // (kept by a select: a NaN colour of a skipped entry must not enter B as 0 * NaN)
-          // Per lane only the MOMENTS of q = G * dL/dalpha are formed; every per-entry constant of
-          // backward.cu:538-554 (conic, opacity, 0.5*W, 0.5*H, -0.5) is applied once per (tile, entry) by the flush.
+          last_cdot = on ? cdot : last_cdot;
           const float q = on ? G[u] * dL_dalpha : 0.f;
           const float mD = alpha * T;  // dchannel_dcolor (0 for a skipped lane)
-          const float dx = dxs[u], dy = dys[u];
-          const float qx = q * dx, qy = q * dy;
-          v[0][u] = q;
-          v[1][u] = qx;
-          v[2][u] = qy;
-          v[3][u] = qx * dx;
-          v[4][u] = qx * dy;
-          v[5][u] = qy * dy;
+          geometry_moments(v, u, q, dxs[u], dys[u]);
           v[6][u] = mD * dpx[0];
           v[7][u] = mD * dpx[1];
           v[8][u] = mD * dpx[2];
           if constexpr (DEPTH) v[9][u] = mD * dpd;  // dL/dd of the entry
           if constexpr (ABS) {  // |A qx + B qy|, |B qx + C qy| (cos_ = (-0.5 A, -B, -0.5 C): both signs flipped, exact scaling)
+            const float qx = v[1][u], qy = v[2][u];  // (moments 1, 2: q dx, q dy)
             v[IABS][u] = __builtin_fabsf(2.f * cos_[u].x * qx + cos_[u].y * qy);
             v[IABS + 1][u] = __builtin_fabsf(cos_[u].y * qx + 2.f * cos_[u].z * qy);
           }
@@ -1221,12 +1367,9 @@ blend_backward_kernel(const BlendArgs a) {
   // (element i was zeroed by thread i % 256, i.e. by any wave: with the deferred flush the placement-assigned first item
   // reaches its first ds_add_f32 without passing a workgroup barrier otherwise.  Once per kernel, not per item.)
   __syncthreads();
-  // `bg` once per kernel, in scalar registers
-  const float bg0 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, a.bg[0])));
-  const float bg1 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, a.bg[1])));
-  const float bg2 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, a.bg[2])));
+  const float bg0 = wave_uniform(a.bg[0]), bg1 = wave_uniform(a.bg[1]), bg2 = wave_uniform(a.bg[2]);
   // item-granular queue: queue x (one per XCD) owns items x, x+8, ... of the backward's work list
-  const uint32_t x = (uint32_t)__builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 20) & 7u;  // HW_REG_XCC_ID
+  const uint32_t x = xcc_id() & 7u;
   const uint32_t nwork = a.bwd_meta[0];
   const uint32_t n_x = nwork > x ? (nwork - x + 7u) / 8u : 0u;
   uint32_t* head = a.queue + x * QUEUE_STRIDE;
@@ -1237,18 +1380,7 @@ blend_backward_kernel(const BlendArgs a) {
   if (prof) t_begin = __builtin_amdgcn_s_memtime();
   auto run_tile = [&](uint32_t index) {
     if (prof) t_tile = __builtin_amdgcn_s_memtime();
-    // The item's descriptor -- code, first position of the tile's list, how deep the item's pixels reach into it -- from three
-    // SCALAR loads (tables of earlier kernels: the work list, the ranges, the walk depths the forward left per quadrant; the
-    // scalar path does not queue behind the previous item's last atomics): code first, the other two together.  (Round 5's
-    // first form had backward_worklist_kernel write whole descriptors: that one-block kernel is a chain of dependent round
-    // trips between the forward and the backward -- 14 -> 16-18 us for what costs this kernel, whose waves wait behind three
-    // others, nothing measurable.)
-    const uint32_t code = scalar_load(a.bwd_order, index);
-    const uint32_t ctile = code & BWD_ITEM_TILE;
-    const uint2 crange = scalar_load(a.ranges, ctile);
-    const uint4 cmax = scalar_load(reinterpret_cast<const uint4*>(a.work_maxc), ctile);
-    const uint32_t r01 = max(cmax.x, cmax.y), r23 = max(cmax.z, cmax.w);
-    const uint4 item = make_uint4(code, crange.x, (code & BWD_ITEM_HALF) ? ((code & BWD_ITEM_PART) ? r23 : r01) : max(r01, r23), 0u);
+    const uint4 item = load_backward_item(a, index);
     const uint32_t tile = item.x;
     const uint32_t tmax = backward_tile<FAST, SEG, DEPTH, ABS, ALPHA>(a, item, bg0, bg1, bg2, s0, s1, s2, sid, sco, sacc);
     if (prof) {
@@ -1296,8 +1428,7 @@ blend_backward_kernel(const BlendArgs a) {
     uint64_t* rec = a.profile + (size_t)blockIdx.x * 8;
     rec[0] = t_begin;
     rec[1] = __builtin_amdgcn_s_memtime();
-    rec[2] = ((uint64_t)__builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 20) << 32) |
-             (uint64_t)__builtin_amdgcn_s_getreg((32 - 1) << 11 | 0 << 6 | 4);
+    rec[2] = ((uint64_t)xcc_id() << 32) | (uint64_t)__builtin_amdgcn_s_getreg((32 - 1) << 11 | 0 << 6 | 4);  // | HW_REG_HW_ID
     rec[3] = ((uint64_t)ntiles << 32) | (uint64_t)west;
     rec[4] = longest;
     rec[5] = first;
@@ -1311,12 +1442,9 @@ blend_backward_kernel(const BlendArgs a) {
 // mask value(s) to weights[id] and C to cnt[id] (the reference increments cnt inside its
 // channel loop, apply_weights.cu:331-339).
 // ----------------------------------------------------------------------------------
-// The inner loop is K6's (round 6; rounds 1-5 walked one survivor per iteration with a ballot, a branch and a 64-lane reduction
-// per entry: 182 -> 122 us per 512 x 512 view at 10^6 Gaussians, profiles/r06_j_trace_weights.md): survivors are staged in pairs
-// and evaluated two per instruction (packed binary32, same roundings), four per iteration; the serial part -- transmittance,
-// saturation -- runs on selects (Ts = T for a live pixel, -T for one that is done), and what a pixel adds for the four entries
-// (its mask value per channel, and 1 for the count) is summed over the wave four values at a time (wave_sum4_to_rows: 10
-// instructions instead of 4 x 8).
+// The traversal is walk_front_to_back (K6's inner loop since round 6).  The payload: what a pixel adds for the four entries
+// of a group (its mask value per channel, and 1 for the count) is summed over the wave four values at a time
+// (wave_sum4_to_rows: 10 instructions instead of 4 x 8), and a chunk's totals leave with one atomic per (entry, channel).
 template <int C, int SPLIT, bool FAST>
 __device__ __forceinline__ void trace_item(const BlendArgs& a, uint32_t tile, uint32_t quad) {
   PixelWave pw;
@@ -1325,112 +1453,40 @@ __device__ __forceinline__ void trace_item(const BlendArgs& a, uint32_t tile, ui
   const int lane = lane_id();
   const uint2 range = a.ranges[pw.tile];
   if (range.y <= range.x) return;
-  const float pfx = (float)pw.px, pfy = (float)pw.py;
-  const f32x2 pfx2 = {pfx, pfx}, pfy2 = {pfy, pfy};
   (void)box;  // (the cull rectangle follows the pixels that are still live, live_pixel_box)
   const size_t pix = (size_t)pw.py * a.W + pw.px, HW = (size_t)a.H * a.W;
   float Cw[C];
 #pragma unroll
   for (int ch = 0; ch < C; ++ch) Cw[ch] = pw.inside ? a.image_weights[(size_t)ch * HW + pix] : 0.f;
-  float Ts = pw.inside ? 1.0f : -1.0f;
-
-  // a pair of survivors: {hA0,hA1,nB0,nB1} {hC0,hC1,op0,op1} {x0,x1,y0,y1} (conic pre-scaled: -0.5 A, -B, -0.5 C, exact)
-  __shared__ __align__(16) float spair[WAVE / 2][12];
   __shared__ uint32_t sid[WAVE];
   __shared__ float sacc[C][WAVE];
   __shared__ float scnt[WAVE];
-  const uint64_t lt_mask = (1ull << lane) - 1ull;
   const bool row_end = (lane & 15) == 15;
-  ChunkWalker<true> walk(a, range.x, range.y - range.x);
-  for (; walk.valid(); walk.advance()) {
-    const uint64_t live_m = __ballot(Ts > 0.0f);
-    if (live_m == 0) break;
-    const LiveBox lb = live_pixel_box(live_m, pfx - (float)(lane & 7), pfy - (float)(lane >> 3));
-    const bool keep = ((uint32_t)lane < walk.chunk_size()) && can_touch_quad(walk.cur.r0, walk.cur.r1, lb.x0, lb.y0, lb.w, lb.h);
-    const uint64_t km = __ballot(keep);
-    if (km == 0) continue;
-    const uint32_t n = (uint32_t)__popcll(km);
-    const uint32_t n4 = (n + GROUP - 1) & ~(uint32_t)(GROUP - 1);
-    __syncthreads();
-    if (keep) {
-      const uint32_t slot = (uint32_t)__popcll(km & lt_mask);
-      float* q = &spair[slot >> 1][slot & 1u];
-      q[0] = -0.5f * walk.cur.r0.x;
-      q[2] = -walk.cur.r0.y;
-      q[4] = -0.5f * walk.cur.r0.z;
-      q[6] = walk.cur.r0.w;
-      q[8] = walk.cur.r1.x;
-      q[10] = walk.cur.r1.y;
-      sid[slot] = walk.cur.id;
-    }
-    if ((uint32_t)lane >= n && (uint32_t)lane < n4) {
-      // null entries pad the survivors to a multiple of GROUP: opacity 0 => alpha 0 => never a hit
-      float* q = &spair[lane >> 1][lane & 1];
-      q[0] = q[2] = q[4] = q[6] = q[8] = q[10] = 0.f;
-    }
-    __syncthreads();
-    uint32_t flushed = n;  // entries whose totals this chunk wrote (all of them unless every pixel saturated on the way)
-    for (uint32_t j = 0; j < n4; j += GROUP) {
-      if (__all(Ts < 0.0f)) {
-        flushed = j;
-        break;
-      }
-      float ae[GROUP], om[GROUP];
+  walk_front_to_back<FAST>(
+      a, pw, range, [&](uint32_t slot, const Entry& e) __attribute__((always_inline)) { sid[slot] = e.id; },
+      [&](uint32_t j, const bool(&hit)[GROUP], const float(&)[GROUP]) __attribute__((always_inline)) {
+        const uint32_t e = j + ((uint32_t)lane >> 4);  // the entry whose totals end up in this lane's row
 #pragma unroll
-      for (int pp = 0; pp < GROUP / 2; ++pp) {
-        const float* q = &spair[(j >> 1) + pp][0];
-        const float4 q0 = *reinterpret_cast<const float4*>(q), q1 = *reinterpret_cast<const float4*>(q + 4),
-                     q2 = *reinterpret_cast<const float4*>(q + 8);
-        const f32x2 hA = {q0.x, q0.y}, nB = {q0.z, q0.w}, hC = {q1.x, q1.y}, op = {q1.z, q1.w};
-        const f32x2 dx = f32x2{q2.x, q2.y} - pfx2, dy = f32x2{q2.z, q2.w} - pfy2;
-        const f32x2 a_ = (hA * dx) * dx;  // blend_power_prescaled on both entries
-        const f32x2 s_ = __builtin_elementwise_fma(hC * dy, dy, a_);
-        const f32x2 power = __builtin_elementwise_fma(nB * dx, dy, s_);
-        const f32x2 ao = op * blend_exp2<FAST>(power);
-        const float a0 = fminf(0.99f, ao.x), a1 = fminf(0.99f, ao.y);
-        const float g0 = (power.x > 0.0f) ? 0.0f : a0, g1 = (power.y > 0.0f) ? 0.0f : a1;
-        const f32x2 a2 = {(g0 < 1.0f / 255.0f) ? 0.0f : g0, (g1 < 1.0f / 255.0f) ? 0.0f : g1};
-        const f32x2 o2 = f32x2{1.0f, 1.0f} - a2;
-        ae[2 * pp] = a2.x;
-        ae[2 * pp + 1] = a2.y;
-        om[2 * pp] = o2.x;
-        om[2 * pp + 1] = o2.y;
-      }
+        for (int ch = 0; ch < C; ++ch) {
+          const float z = wave_sum4_to_rows(hit[0] ? Cw[ch] : 0.f, hit[1] ? Cw[ch] : 0.f, hit[2] ? Cw[ch] : 0.f, hit[3] ? Cw[ch] : 0.f);
+          if (row_end) sacc[ch][e] = z;
+        }
+        const float zc = wave_sum4_to_rows(hit[0] ? 1.0f : 0.0f, hit[1] ? 1.0f : 0.0f, hit[2] ? 1.0f : 0.0f, hit[3] ? 1.0f : 0.0f);
+        if (row_end) scnt[e] = zc;
+      },
+      [&](uint32_t evaluated) __attribute__((always_inline)) {
+        __syncthreads();
+        // (the groups behind a break wrote nothing: their slots hold an earlier chunk's values)
+        if ((uint32_t)lane < evaluated) {
+          const int cn = (int)scnt[lane] * C;
+          if (cn != 0) {
+            const size_t id = sid[lane];
 #pragma unroll
-      for (int u = 0; u < GROUP; ++u) asm volatile("" : "+v"(ae[u]), "+v"(om[u]));
-      // entry skipped for this pixel (power > 0 or alpha < 1/255): alpha := 0, test_T = T exactly, no hit;
-      // T (1 - alpha) < 0.0001: the pixel is done BEFORE this entry counts (apply_weights.cu:318-323), Ts := -T;
-      // pixel done: test_T <= 0, nothing changes.
-      float h[GROUP];
-#pragma unroll
-      for (int u = 0; u < GROUP; ++u) {
-        const float test_T = Ts * om[u];
-        const bool A = !(test_T < 0.0001f);
-        h[u] = (A && ae[u] > 0.0f) ? 1.0f : 0.0f;
-        Ts = A ? test_T : -__builtin_fabsf(Ts);
-      }
-      const uint32_t e = j + ((uint32_t)lane >> 4);  // the entry whose totals end up in this lane's row
-#pragma unroll
-      for (int ch = 0; ch < C; ++ch) {
-        const float z = wave_sum4_to_rows(h[0] > 0.f ? Cw[ch] : 0.f, h[1] > 0.f ? Cw[ch] : 0.f,
-                                                                    h[2] > 0.f ? Cw[ch] : 0.f, h[3] > 0.f ? Cw[ch] : 0.f);
-        if (row_end) sacc[ch][e] = z;
-      }
-      const float zc = wave_sum4_to_rows(h[0], h[1], h[2], h[3]);
-      if (row_end) scnt[e] = zc;
-    }
-    __syncthreads();
-    // (the groups behind a break wrote nothing: their slots hold an earlier chunk's values)
-    if ((uint32_t)lane < min(n, flushed)) {
-      const int cn = (int)scnt[lane] * C;
-      if (cn != 0) {
-        const size_t id = sid[lane];
-#pragma unroll
-        for (int ch = 0; ch < C; ++ch) unsafeAtomicAdd(&a.weights[id * C + ch], sacc[ch][lane]);
-        atomicAdd(&a.cnt[id], cn);
-      }
-    }
-  }
+            for (int ch = 0; ch < C; ++ch) unsafeAtomicAdd(&a.weights[id * C + ch], sacc[ch][lane]);
+            atomicAdd(&a.cnt[id], cn);
+          }
+        }
+      });
 }
 template <int C, int SPLIT, bool FAST>
 __global__ void __launch_bounds__(WAVE) trace_weights_kernel(const BlendArgs a) {
@@ -1455,112 +1511,52 @@ struct FeatureArgs {
   int C;
 };
 
-// One forward item: K12's traversal (survivors staged in pairs, alpha of two entries per packed instruction, K6's select
-// form of the transmittance chain), and per blended (pixel, entry) K6's accumulation C_c = fma(f_c, alpha T, C_c) for the 16
-// channels of the block -- channel c of the image equals, as floats, channel c % 3 of an auxiliary render of
-// features[:, 3 (c / 3) : + 3].  The accumulation is a lane-masked region, as K6's masked form: a feature of an entry the
-// pixel skips is never read into the sum (0 x NaN).
+// One forward item: walk_front_to_back once per channel block, and per blended (pixel, entry) K6's accumulation
+// C_c = fma(f_c, alpha T, C_c) for the 16 channels of the block -- channel c of the image equals, as floats, channel c % 3 of an
+// auxiliary render of features[:, 3 (c / 3) : + 3].  The accumulation is a lane-masked region, as K6's masked form: a feature of
+// an entry the pixel skips is never read into the sum (0 x NaN).
 template <bool FAST>
 __device__ __forceinline__ void feature_forward_item(const BlendArgs& a, const FeatureArgs& f, uint32_t tile, uint32_t quad) {
   PixelWave pw;
   ItemBox box;
   if (!setup_item<1>(a, tile, quad, pw, box)) return;
   (void)box;
-  const int lane = lane_id();
   const uint2 range = a.ranges[pw.tile];
-  const float pfx = (float)pw.px, pfy = (float)pw.py;
-  const f32x2 pfx2 = {pfx, pfx}, pfy2 = {pfy, pfy};
   const size_t pix = (size_t)pw.py * a.W + pw.px, HW = (size_t)a.H * a.W;
-  __shared__ __align__(16) float spair[WAVE / 2][12];
   __shared__ __align__(16) float sfeat[WAVE][FEAT_BLOCK];
-  const uint64_t lt_mask = (1ull << lane) - 1ull;
   const int C = f.C;
   for (int c0 = 0; c0 < C; c0 += FEAT_BLOCK) {
     const int nch = min(FEAT_BLOCK, C - c0);  // (the last block may be partial: its missing channels blend zeros)
     float F[FEAT_BLOCK];
 #pragma unroll
     for (int k = 0; k < FEAT_BLOCK; ++k) F[k] = 0.f;
-    float Ts = pw.inside ? 1.0f : -1.0f;
-    if (range.y > range.x) {
-      ChunkWalker<true> walk(a, range.x, range.y - range.x);
-      for (; walk.valid(); walk.advance()) {
-        const uint64_t live_m = __ballot(Ts > 0.0f);
-        if (live_m == 0) break;
-        const LiveBox lb = live_pixel_box(live_m, pfx - (float)(lane & 7), pfy - (float)(lane >> 3));
-        const bool keep = ((uint32_t)lane < walk.chunk_size()) && can_touch_quad(walk.cur.r0, walk.cur.r1, lb.x0, lb.y0, lb.w, lb.h);
-        const uint64_t km = __ballot(keep);
-        if (km == 0) continue;
-        const uint32_t n = (uint32_t)__popcll(km);
-        const uint32_t n4 = (n + GROUP - 1) & ~(uint32_t)(GROUP - 1);
-        __syncthreads();
-        if (keep) {
-          const uint32_t slot = (uint32_t)__popcll(km & lt_mask);
-          float* q = &spair[slot >> 1][slot & 1u];
-          q[0] = -0.5f * walk.cur.r0.x;
-          q[2] = -walk.cur.r0.y;
-          q[4] = -0.5f * walk.cur.r0.z;
-          q[6] = walk.cur.r0.w;
-          q[8] = walk.cur.r1.x;
-          q[10] = walk.cur.r1.y;
-          const float* __restrict__ fr = f.features + (size_t)walk.cur.id * (size_t)C + c0;
+    walk_front_to_back<FAST>(
+        a, pw, range,
+        [&](uint32_t slot, const Entry& e) __attribute__((always_inline)) {
+          const float* __restrict__ fr = f.features + (size_t)e.id * (size_t)C + c0;
 #pragma unroll
           for (int k = 0; k < FEAT_BLOCK; ++k) {
             const float v = fr[min(k, nch - 1)];  // (unconditional and in bounds; a channel beyond the last one is zero)
             sfeat[slot][k] = k < nch ? v : 0.f;
           }
-        }
-        if ((uint32_t)lane >= n && (uint32_t)lane < n4) {
-          // null entries pad the survivors to a multiple of GROUP: opacity 0 => alpha 0 => never a hit
-          float* q = &spair[lane >> 1][lane & 1];
-          q[0] = q[2] = q[4] = q[6] = q[8] = q[10] = 0.f;
-        }
-        __syncthreads();
-        for (uint32_t j = 0; j < n4; j += GROUP) {
-          if (__all(Ts < 0.0f)) break;
-          float ae[GROUP], om[GROUP];
-#pragma unroll
-          for (int pp = 0; pp < GROUP / 2; ++pp) {
-            const float* q = &spair[(j >> 1) + pp][0];
-            const float4 q0 = *reinterpret_cast<const float4*>(q), q1 = *reinterpret_cast<const float4*>(q + 4),
-                         q2 = *reinterpret_cast<const float4*>(q + 8);
-            const f32x2 hA = {q0.x, q0.y}, nB = {q0.z, q0.w}, hC = {q1.x, q1.y}, op = {q1.z, q1.w};
-            const f32x2 dx = f32x2{q2.x, q2.y} - pfx2, dy = f32x2{q2.z, q2.w} - pfy2;
-            const f32x2 a_ = (hA * dx) * dx;  // blend_power_prescaled on both entries
-            const f32x2 s_ = __builtin_elementwise_fma(hC * dy, dy, a_);
-            const f32x2 power = __builtin_elementwise_fma(nB * dx, dy, s_);
-            const f32x2 ao = op * blend_exp2<FAST>(power);
-            const float a0 = fminf(0.99f, ao.x), a1 = fminf(0.99f, ao.y);
-            const float g0 = (power.x > 0.0f) ? 0.0f : a0, g1 = (power.y > 0.0f) ? 0.0f : a1;
-            const f32x2 a2 = {(g0 < 1.0f / 255.0f) ? 0.0f : g0, (g1 < 1.0f / 255.0f) ? 0.0f : g1};
-            const f32x2 o2 = f32x2{1.0f, 1.0f} - a2;
-            ae[2 * pp] = a2.x;
-            ae[2 * pp + 1] = a2.y;
-            om[2 * pp] = o2.x;
-            om[2 * pp + 1] = o2.y;
-          }
-#pragma unroll
-          for (int u = 0; u < GROUP; ++u) asm volatile("" : "+v"(ae[u]), "+v"(om[u]));
+        },
+        [&](uint32_t j, const bool(&hit)[GROUP], const float(&w)[GROUP]) __attribute__((always_inline)) {
 #pragma unroll
           for (int u = 0; u < GROUP; ++u) {
-            const float test_T = Ts * om[u];
-            const bool A = !(test_T < 0.0001f);
-            const float w = ae[u] * Ts;
-            if (A && ae[u] > 0.0f) {  // the pixel blends the entry: w = alpha T
+            if (hit[u]) {  // the pixel blends the entry: w = alpha T
               const float4* fp = reinterpret_cast<const float4*>(&sfeat[j + u][0]);
 #pragma unroll
               for (int k4 = 0; k4 < FEAT_BLOCK / 4; ++k4) {
                 const float4 v = fp[k4];
-                F[4 * k4] = __builtin_fmaf(v.x, w, F[4 * k4]);
-                F[4 * k4 + 1] = __builtin_fmaf(v.y, w, F[4 * k4 + 1]);
-                F[4 * k4 + 2] = __builtin_fmaf(v.z, w, F[4 * k4 + 2]);
-                F[4 * k4 + 3] = __builtin_fmaf(v.w, w, F[4 * k4 + 3]);
+                F[4 * k4] = __builtin_fmaf(v.x, w[u], F[4 * k4]);
+                F[4 * k4 + 1] = __builtin_fmaf(v.y, w[u], F[4 * k4 + 1]);
+                F[4 * k4 + 2] = __builtin_fmaf(v.z, w[u], F[4 * k4 + 2]);
+                F[4 * k4 + 3] = __builtin_fmaf(v.w, w[u], F[4 * k4 + 3]);
               }
             }
-            Ts = A ? test_T : -__builtin_fabsf(Ts);
           }
-        }
-      }
-    }
+        },
+        [](uint32_t) __attribute__((always_inline)) {});
     if (pw.inside) {
 #pragma unroll
       for (int k = 0; k < FEAT_BLOCK; ++k)
@@ -1575,14 +1571,9 @@ feature_forward_kernel(const BlendArgs a, const FeatureArgs f) {
     if (!empty) {
       feature_forward_item<FAST>(a, f, tile, quad);
     } else {  // a tile no Gaussian touches: zeros
-      for (uint32_t q = 0; q < 4; ++q) {
-        PixelWave pw;
-        if (!setup_wave(a, tile, q, pw)) continue;
-        if (pw.inside) {
-          const size_t pix = (size_t)pw.py * a.W + pw.px, HW = (size_t)a.H * a.W;
-          for (int c = 0; c < f.C; ++c) f.out[(size_t)c * HW + pix] = 0.f;
-        }
-      }
+      for_each_pixel_of_tile(a, tile, [&](size_t pix, size_t HW) __attribute__((always_inline)) {
+        for (int c = 0; c < f.C; ++c) f.out[(size_t)c * HW + pix] = 0.f;
+      });
     }
   });
 }
@@ -1758,10 +1749,7 @@ __device__ __forceinline__ void feature_backward_tile(const BlendArgs& a, const 
       const uint32_t chunk_lo = tile_max - min(tile_max, (walk.chunk + 1u) * (uint32_t)WAVE);
       const uint64_t live_m = __ballot(last_contributor > chunk_lo);
       bool keep = false;
-      if (live_m != 0) {
-        const LiveBox lb = live_pixel_box(live_m, qx0, qy0);
-        keep = ((uint32_t)lane < csize) && (pos < maxc) && can_touch_quad(walk.cur.r0, walk.cur.r1, lb.x0, lb.y0, lb.w, lb.h);
-      }
+      if (live_m != 0) keep = chunk_cull(live_m, qx0, qy0, ((uint32_t)lane < csize) && (pos < maxc), walk.cur);
       const uint64_t m = __ballot(keep);
       const uint32_t cnt = (uint32_t)__popcll(m);
       const uint32_t cnt4 = (cnt + GROUP - 1) & ~(uint32_t)(GROUP - 1);
@@ -1821,25 +1809,15 @@ __device__ __forceinline__ void feature_backward_tile(const BlendArgs& a, const 
           for (int u = 0; u < GROUP; ++u) {
             const bool on = contrib[u];
             const float alpha = on ? al[u] : 0.f;
-            const float one_m = 1.f - alpha;
-            const float r0 = __builtin_amdgcn_rcpf(one_m);
-            const float inv_one_m = __builtin_fmaf(r0, __builtin_fmaf(-one_m, r0, 1.0f), r0);
-            const float cdot = cdots[u];
-            T = T * inv_one_m;                                 // T / (1 - alpha), backward.cu:503
-            B_acc = B_acc + last_alpha * (last_cdot - B_acc);  // accum_rec update, backward.cu:515
-            const float dL_dalpha = (cdot - B_acc) * T;        // (no background term: the feature image's background is 0)
+            // (no background term: the feature image's background is 0)
+            const RecStep rs = accum_rec_step(T, B_acc, last_alpha, last_cdot, rcp_refined(1.f - alpha), cdots[u]);
+            T = rs.T;
+            B_acc = rs.B_acc;
             last_alpha = alpha;
-            last_cdot = on ? cdot : last_cdot;
-            const float q = on ? G[u] * dL_dalpha : 0.f;
+            last_cdot = on ? cdots[u] : last_cdot;
+            const float q = on ? G[u] * rs.dL_dalpha : 0.f;
             mD[u] = alpha * T;  // dF_c / df_c (0 for a skipped lane)
-            const float dx = dxs[u], dy = dys[u];
-            const float qx = q * dx, qy = q * dy;
-            v[0][u] = q;
-            v[1][u] = qx;
-            v[2][u] = qy;
-            v[3][u] = qx * dx;
-            v[4][u] = qx * dy;
-            v[5][u] = qy * dy;
+            geometry_moments(v, u, q, dxs[u], dys[u]);
           }
         }
         float totg = wave_sum4_pack<FEAT_NM>(v);
@@ -1873,20 +1851,14 @@ feature_backward_kernel(const BlendArgs a, const FeatureArgs f) {
   for (int i = threadIdx.x; i < 2 * WAVE * FEAT_LDS_ROW; i += WAVE * BWD_WAVES) (&sacc[0][0][0])[i] = 0.f;
   __syncthreads();
   // item-granular queue, as K7: queue x (one per XCD) owns items x, x + 8, ... of the backward's work list
-  const uint32_t x = (uint32_t)__builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 20) & 7u;  // HW_REG_XCC_ID
+  const uint32_t x = xcc_id() & 7u;
   const uint32_t nwork = a.bwd_meta[0];
   const uint32_t n_x = nwork > x ? (nwork - x + 7u) / 8u : 0u;
   uint32_t* head = a.queue + x * QUEUE_STRIDE;
   // (always_inline: called, the item function would receive the argument blocks through scratch memory)
   auto run_tile = [&](uint32_t index) __attribute__((always_inline)) {
-    const uint32_t code = scalar_load(a.bwd_order, index);
-    const uint32_t ctile = code & BWD_ITEM_TILE;
-    const uint2 crange = scalar_load(a.ranges, ctile);
-    const uint4 cmax = scalar_load(reinterpret_cast<const uint4*>(a.work_maxc), ctile);
-    const uint32_t r01 = max(cmax.x, cmax.y), r23 = max(cmax.z, cmax.w);
-    const uint32_t deep = (code & BWD_ITEM_HALF) ? ((code & BWD_ITEM_PART) ? r23 : r01) : max(r01, r23);
-    // (the depths are the forward's own: never beyond the tile's list)
-    const uint4 item = make_uint4(code, crange.x, min(deep, crange.y - crange.x), 0u);
+    uint4 item = load_backward_item(a, index);
+    item.z = min(item.z, item.w);  // (the depths are the forward's own: never beyond the tile's list)
     feature_backward_tile<FAST>(a, f, item, s0, s1, sfeat, sid, sco, sacc);
   };
   uint32_t x0, base;
@@ -2244,6 +2216,21 @@ static std::atomic<uint64_t> g_bwd_launches[32];
 void blend_backward_launch_counts(uint64_t counts[32]) {
   for (int i = 0; i < 32; ++i) counts[i] = g_bwd_launches[i].load(std::memory_order_relaxed);
 }
+// The backward's own work list, ordered by the work the forward measured (backward_worklist_kernel): `grid` workgroups will
+// serve it; `fill_blocks` extra blocks clear what `clear` names; seg_share: 0 -- no list segments --, or the threshold in 1/8 of
+// a fair share above which a tile is cut into them (the view's checkpoint tables must be there).
+static void launch_backward_worklist(hipStream_t s, const BlendArgs& a, unsigned grid, const ClearArgs& clear, unsigned fill_blocks,
+                                     int seg_share) {
+  constexpr int halves = 10;  // tiles above 1.25 fair shares are cut in two: measured best (sweep 6..16)
+  if (seg_share > 0)
+    hipLaunchKernelGGL(backward_worklist_kernel<true>, dim3(1u + fill_blocks), dim3(1024), 0, s, a.gx * a.gy, a.work_est,
+                       a.bwd_order, a.bwd_meta, grid, halves, clear, (const uint32_t*)a.tile_maxc,
+                       (const uint32_t*)a.ck_table, (const uint32_t*)a.ck_work, a.ck_pos, (uint32_t)a.ck_slots, seg_share);
+  else
+    hipLaunchKernelGGL(backward_worklist_kernel<false>, dim3(1u + fill_blocks), dim3(1024), 0, s, a.gx * a.gy, a.work_est,
+                       a.bwd_order, a.bwd_meta, grid, halves, clear, (const uint32_t*)nullptr,
+                       (const uint32_t*)nullptr, (const uint32_t*)nullptr, CkTable{}, 0u, 0);
+}
 hipError_t launch_blend_backward(hipStream_t s, BlendArgs a) {
   // #CUs x 4 workgroups of 4 waves: the same 4 waves per SIMD as the forward
   unsigned grid;
@@ -2260,8 +2247,6 @@ hipError_t launch_blend_backward(hipStream_t s, BlendArgs a) {
   }
   if (a.work_est == nullptr || a.work_maxc == nullptr || a.bwd_order == nullptr) return hipErrorInvalidValue;
   {
-    // its own work list, ordered by the work the forward measured
-    constexpr int halves = 10;  // tiles above 1.25 fair shares are cut in two: measured best (sweep 6..16)
     const unsigned fill_blocks = a.clear_grads ? 2u * (unsigned)cus_of_stream(s) : (a.touched != nullptr ? 16u : 0u);  // (1 .. 8 per CU: the same 14 us)
     // GSR_BWD_SEG: tiles above this many eighths of a fair share are cut into list segments where the forward left
     // checkpoints (0: never; tests use 1)
@@ -2271,14 +2256,7 @@ hipError_t launch_blend_backward(hipStream_t s, BlendArgs a) {
     //  best, 8-40 % slower where pixels walk deep; removed: profiles/r06_m_fine_checkpoints.md.)
     // (a depth backward: no segments -- the checkpoints hold no depth behind a segment, backward_tile)
     seg_items = a.ck_table != nullptr && a.ck_chunks > 0 && seg_share > 0 && a.dL_ddepth == nullptr;
-    if (seg_items)
-      hipLaunchKernelGGL(backward_worklist_kernel<true>, dim3(1u + fill_blocks), dim3(1024), 0, s, a.gx * a.gy, a.work_est,
-                         a.bwd_order, a.bwd_meta, grid, halves, clear, (const uint32_t*)a.tile_maxc,
-                         (const uint32_t*)a.ck_table, (const uint32_t*)a.ck_work, a.ck_pos, (uint32_t)a.ck_slots, seg_share);
-    else
-      hipLaunchKernelGGL(backward_worklist_kernel<false>, dim3(1u + fill_blocks), dim3(1024), 0, s, a.gx * a.gy, a.work_est,
-                         a.bwd_order, a.bwd_meta, grid, halves, clear, (const uint32_t*)nullptr,
-                         (const uint32_t*)nullptr, (const uint32_t*)nullptr, CkTable{}, 0u, 0);
+    launch_backward_worklist(s, a, grid, clear, fill_blocks, seg_items ? seg_share : 0);
   }
   const dim3 g(grid), b(WAVE * BWD_WAVES);
   // (dL_dalpha: gsr_blend_backward_alpha -- the ALPHA twin of whatever the call would launch without it)
@@ -2364,7 +2342,9 @@ hipError_t launch_feature_forward(hipStream_t s, BlendArgs a, const float* featu
   hipError_t e = persistent_launch(s, a, 1, &grid);
   if (e != hipSuccess) return e;
   FeatureArgs f = {features, out, nullptr, nullptr, C};
-  hipLaunchKernelGGL(a.fast_exp ? feature_forward_kernel<true> : feature_forward_kernel<false>, dim3(grid), dim3(WAVE), 0, s, a, f);
+  void (*kernel)(BlendArgs, FeatureArgs) = nullptr;
+  with_constants([&](auto FAST) { kernel = feature_forward_kernel<FAST>; }, a.fast_exp != 0);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(WAVE), 0, s, a, f);
   return hipGetLastError();
 }
 hipError_t launch_feature_backward(hipStream_t s, BlendArgs a, const float* features, const float* dL_dimage,
@@ -2375,13 +2355,11 @@ hipError_t launch_feature_backward(hipStream_t s, BlendArgs a, const float* feat
   hipError_t e = prepare_queue(s, a, grid);
   if (e != hipSuccess) return e;
   if (a.work_est == nullptr || a.work_maxc == nullptr || a.bwd_order == nullptr) return hipErrorInvalidValue;
-  const ClearArgs clear = {{nullptr, nullptr, nullptr, nullptr}, {0, 0, 0, 0}};
-  hipLaunchKernelGGL(backward_worklist_kernel<false>, dim3(1u), dim3(1024), 0, s, a.gx * a.gy, a.work_est, a.bwd_order,
-                     a.bwd_meta, grid, 10, clear, (const uint32_t*)nullptr, (const uint32_t*)nullptr,
-                     (const uint32_t*)nullptr, CkTable{}, 0u, 0);
+  launch_backward_worklist(s, a, grid, ClearArgs{{nullptr, nullptr, nullptr, nullptr}, {0, 0, 0, 0}}, 0u, 0);
   FeatureArgs f = {features, nullptr, dL_dimage, dL_dfeatures, C};
-  hipLaunchKernelGGL(a.fast_exp ? feature_backward_kernel<true> : feature_backward_kernel<false>, dim3(grid),
-                     dim3(WAVE * BWD_WAVES), 0, s, a, f);
+  void (*kernel)(BlendArgs, FeatureArgs) = nullptr;
+  with_constants([&](auto FAST) { kernel = feature_backward_kernel<FAST>; }, a.fast_exp != 0);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(WAVE * BWD_WAVES), 0, s, a, f);
   return hipGetLastError();
 }
 

@@ -45,6 +45,37 @@ def feature_case(name, C=None):
     return _cache[(name, C)]
 
 
+def small_gaussian_case(C=5):
+    """(case, feats, row): one 16 x 16 image -- one tile --, eight Gaussians, C channels.  Gaussian `row` is SMALL: isotropic,
+    screen-space sigma 0.7 px (the 0.3 px^2 dilation included), opacity 0.9, centred on pixel (2.3, 2.4).  It passes the cull of
+    its 8 x 8 quadrant and reaches alpha >= 1/255 only within sigma sqrt(2 ln(0.9 * 255)) = 2.3 px: most of the quadrant's pixels
+    evaluate the entry and skip it."""
+    import math
+
+    W = H = 16
+    case = make_case(8, W, H, s0=0.4)
+    sc, cam = dict(case["sc"]), case["cam"]
+    row, z, sigma, px, py = 0, 4.0, 0.7, 2.3, 2.4
+    focal = W / (2.0 * case["tfx"])
+    p_cam = torch.tensor([((2.0 * px + 1.0) / W - 1.0) * case["tfx"] * z, ((2.0 * py + 1.0) / H - 1.0) * case["tfy"] * z, z, 1.0])
+    xyz, scaling, rotation, opacity = (sc[k].clone() for k in ("xyz", "scaling", "rotation", "opacity"))
+    xyz[row] = (p_cam @ cam.world_view_transform.inverse())[:3]
+    scaling[row] = math.sqrt(sigma * sigma - 0.3) * z / focal
+    rotation[row] = torch.tensor([1.0, 0.0, 0.0, 0.0])
+    opacity[row] = 0.9
+    sc.update(xyz=xyz.contiguous(), scaling=scaling.contiguous(), rotation=rotation.contiguous(), opacity=opacity.contiguous())
+    return dict(case, sc=sc), make_features(8, C, seed=5), row
+
+
+def oracle_blend_mask(O, case, row):
+    """(H,W) bool: the pixels where the CPU oracle blends Gaussian `row` -- where the image of the features that are 1 for
+    that Gaussian and 0 for every other is not zero (a blended entry adds alpha T >= 1e-4 / 255 > 0)."""
+    P = case["sc"]["xyz"].shape[0]
+    one_hot = torch.zeros(P, 1)
+    one_hot[row] = 1.0
+    return oracle_feature_image(O, case, one_hot)[0] != 0.0
+
+
 def slices(feats, GF=None):
     """The three-channel slices: (k, n channels, colours (P,3) zero padded, pixel gradient (3,H,W) zero padded | None)."""
     P, C = feats.shape

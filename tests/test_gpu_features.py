@@ -164,6 +164,28 @@ def test_feature_image_under_a_mode_the_oracle_lacks(flag):
     assert not np.array_equal(_bits(got), _bits(_features(st0, feats, case["H"], case["W"])))  # (the mode is really on)
 
 
+def test_a_skipped_entrys_features_never_enter_a_pixels_sum(oracle):
+    """The accumulation is a masked region, not 0 * f: a Gaussian whose features are all NaN makes NaN exactly the pixels that
+    blend it (the CPU oracle's set), and every other pixel -- most of the entry's quadrant evaluates it and skips it -- is
+    bit-equal to the render with that row zeroed."""
+    from gaussianeditor_amd.diff_gaussian_rasterization import _reuse
+
+    case, feats, row = FH.small_gaussian_case(C=5)
+    blends = FH.oracle_blend_mask(oracle, case, row)
+    assert 0 < int(blends.sum()) < 64 and not blends[8:, :].any() and not blends[:, 8:].any()  # (inside its 8 x 8 quadrant)
+    nan_feats, zero_feats = feats.clone(), feats.clone()
+    nan_feats[row] = float("nan")
+    zero_feats[row] = 0.0
+    hits = _reuse.stats["hits"]
+    got = FH.run_hip(case, feats=nan_feats)[1]["features"]
+    ref = FH.run_hip(case, feats=zero_feats)[1]["features"]
+    assert _reuse.stats["hits"] == hits  # (neither render was served by view reuse)
+    assert got.shape == ref.shape == (5, 16, 16) and not np.isnan(ref).any() and np.abs(ref).max() > 0.05
+    for c in range(5):
+        assert np.array_equal(np.isnan(got[c]), blends), c
+    assert np.array_equal(_bits(got[:, ~blends]), _bits(ref[:, ~blends]))
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # backward
 def _check(oracle, name, tag, colour=True, depth=False, alpha=False, **kw):
