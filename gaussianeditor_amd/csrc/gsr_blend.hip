@@ -265,16 +265,86 @@ __device__ __forceinline__ float wave_sum4_to_rows(float a, float b, float c, fl
 //   across the rows, 32 and 16: one v_permlane32_swap / v_permlane16_swap and one add per pair, no select (the swap itself
 //   leaves the first register's two halves in the lower lanes and the second's in the upper ones).
 // For NM = 9: 36 -> 18 -> 9 -> 5 -> 3 -> 2 -> 1 registers, 35 DPP adds, 66 selects and 3 swaps where one chain per value
-// took 36 DPP adds and 27 swaps.  Afterwards lane i holds the complete wave total of ONE value, pack_lanes<NM>() says which.
+// took 36 DPP adds and 27 swaps (MASKED, below: 62 DPP adds and 12 selects).  Afterwards lane i holds the complete wave total of ONE value, pack_lanes<NM>() says which.
 template <int S> struct PackStage {
   static_assert(S == 8 || S == 4 || S == 2 || S == 1 || S == 32 || S == 16, "distances inside a wave");
   static constexpr int ctrl = S == 8 ? 0x128 : S == 4 ? 0x141 : S == 2 ? 0x4E : 0xB1;
   static constexpr int partner(int lane) { return S == 4 ? lane ^ 7 : lane ^ S; }
   static constexpr bool second(int lane) { return (lane & S) != 0; }
 };
-template <int S, int N>
+// MASKED (K7): at distances 8 and 4 the choice is made by the add's own destination write instead of by two selects.  Bits 3
+// and 2 of the lane number are bank-granular (a DPP bank: four adjacent lanes of a row), so for a pair (a, b)
+//     v_add_f32_dpp a, a, a row_ror:8 bank_mask:0x3        lanes with bit 3 clear: a + a of the partner
+//     v_add_f32_dpp a, b, b row_ror:8 bank_mask:0xc        lanes with bit 3 set:   b + b of the partner
+// leaves in `a` what the two selects and the add leave in the pair's result: the same adds on the same operands in the same
+// lanes (distance 4: row_half_mirror, masks 0x5 / 0xa).  The destination is `a` in both: the second add reads `b` alone.
+// hipcc does not form the masked add from __builtin_amdgcn_update_dpp (it keeps a masked v_mov_b32_dpp beside the adds),
+// hence the asm; it cannot see into the string either, so every statement opens with the two wait states a DPP read of a
+// VGPR needs after a VALU write of it (s_nop 1, what hipcc puts there itself), and takes up to ten pairs (the 30-operand
+// limit of a statement) to pay them once per twenty adds.  A pair reads nothing that its own statement writes.
+#define GSR_MP_ADD(i, CTRL, M0, M1)                                                             \
+  "v_add_f32_dpp %[a" #i "], %[a" #i "], %[a" #i "] " CTRL " row_mask:0xf bank_mask:" M0 "\n\t" \
+  "v_add_f32_dpp %[a" #i "], %[b" #i "], %[b" #i "] " CTRL " row_mask:0xf bank_mask:" M1 "\n\t"
+#define GSR_MP_A(i) [a##i] "+v"(z[2 * (p0 + i)])
+#define GSR_MP_B(i) [b##i] "v"(z[2 * (p0 + i) + 1])
+#define GSR_MP_S1(C, M0, M1) GSR_MP_ADD(0, C, M0, M1)
+#define GSR_MP_A1 GSR_MP_A(0)
+#define GSR_MP_B1 GSR_MP_B(0)
+#define GSR_MP_S2(C, M0, M1) GSR_MP_S1(C, M0, M1) GSR_MP_ADD(1, C, M0, M1)
+#define GSR_MP_A2 GSR_MP_A1, GSR_MP_A(1)
+#define GSR_MP_B2 GSR_MP_B1, GSR_MP_B(1)
+#define GSR_MP_S3(C, M0, M1) GSR_MP_S2(C, M0, M1) GSR_MP_ADD(2, C, M0, M1)
+#define GSR_MP_A3 GSR_MP_A2, GSR_MP_A(2)
+#define GSR_MP_B3 GSR_MP_B2, GSR_MP_B(2)
+#define GSR_MP_S4(C, M0, M1) GSR_MP_S3(C, M0, M1) GSR_MP_ADD(3, C, M0, M1)
+#define GSR_MP_A4 GSR_MP_A3, GSR_MP_A(3)
+#define GSR_MP_B4 GSR_MP_B3, GSR_MP_B(3)
+#define GSR_MP_S5(C, M0, M1) GSR_MP_S4(C, M0, M1) GSR_MP_ADD(4, C, M0, M1)
+#define GSR_MP_A5 GSR_MP_A4, GSR_MP_A(4)
+#define GSR_MP_B5 GSR_MP_B4, GSR_MP_B(4)
+#define GSR_MP_S6(C, M0, M1) GSR_MP_S5(C, M0, M1) GSR_MP_ADD(5, C, M0, M1)
+#define GSR_MP_A6 GSR_MP_A5, GSR_MP_A(5)
+#define GSR_MP_B6 GSR_MP_B5, GSR_MP_B(5)
+#define GSR_MP_S7(C, M0, M1) GSR_MP_S6(C, M0, M1) GSR_MP_ADD(6, C, M0, M1)
+#define GSR_MP_A7 GSR_MP_A6, GSR_MP_A(6)
+#define GSR_MP_B7 GSR_MP_B6, GSR_MP_B(6)
+#define GSR_MP_S8(C, M0, M1) GSR_MP_S7(C, M0, M1) GSR_MP_ADD(7, C, M0, M1)
+#define GSR_MP_A8 GSR_MP_A7, GSR_MP_A(7)
+#define GSR_MP_B8 GSR_MP_B7, GSR_MP_B(7)
+#define GSR_MP_S9(C, M0, M1) GSR_MP_S8(C, M0, M1) GSR_MP_ADD(8, C, M0, M1)
+#define GSR_MP_A9 GSR_MP_A8, GSR_MP_A(8)
+#define GSR_MP_B9 GSR_MP_B8, GSR_MP_B(8)
+#define GSR_MP_S10(C, M0, M1) GSR_MP_S9(C, M0, M1) GSR_MP_ADD(9, C, M0, M1)
+#define GSR_MP_A10 GSR_MP_A9, GSR_MP_A(9)
+#define GSR_MP_B10 GSR_MP_B9, GSR_MP_B(9)
+#define GSR_MP_CASE(K)                                                                                                   \
+  if constexpr (COUNT == K) {                                                                                            \
+    if constexpr (S == 8) asm("s_nop 1\n\t" GSR_MP_S##K("row_ror:8", "0x3", "0xc") : GSR_MP_A##K : GSR_MP_B##K);          \
+    else asm("s_nop 1\n\t" GSR_MP_S##K("row_half_mirror", "0x5", "0xa") : GSR_MP_A##K : GSR_MP_B##K);                     \
+  }
+// pairs p0 .. p0 + COUNT - 1 of z: z[2 p] <- the pair's result
+template <int S, int COUNT>
+__device__ __forceinline__ void masked_pairs(float* z, int p0) {
+  static_assert((S == 8 || S == 4) && COUNT >= 1 && COUNT <= 10, "a row stage whose bit is bank-granular; one statement");
+  GSR_MP_CASE(1) GSR_MP_CASE(2) GSR_MP_CASE(3) GSR_MP_CASE(4) GSR_MP_CASE(5)
+  GSR_MP_CASE(6) GSR_MP_CASE(7) GSR_MP_CASE(8) GSR_MP_CASE(9) GSR_MP_CASE(10)
+}
+template <int S, int PAIRS, int P0 = 0>
+__device__ __forceinline__ void masked_stage(float* z) {
+  if constexpr (PAIRS > 0) {
+    constexpr int count = PAIRS < 10 ? PAIRS : 10;
+    masked_pairs<S, count>(z, P0);
+    masked_stage<S, PAIRS - count, P0 + count>(z);
+  }
+}
+template <int S, int N, bool MASKED = false>
 __device__ __forceinline__ void pack_stage(float* z, int lane) {
-  if constexpr (S >= 16) {
+  if constexpr (MASKED && (S == 8 || S == 4)) {
+    masked_stage<S, N / 2>(z);
+#pragma unroll
+    for (int p = 1; p < N / 2; ++p) z[p] = z[2 * p];
+    if (N & 1) z[N / 2] = dpp_add<PackStage<S>::ctrl>(z[N - 1]);
+  } else if constexpr (S >= 16) {
     auto fold = [](float a, float b) __attribute__((always_inline)) {
       const unsigned ua = __builtin_bit_cast(unsigned, a), ub = __builtin_bit_cast(unsigned, b);
       // (the two results go through scalars: __builtin_bit_cast applied to r[1] itself reads r[0] with this compiler)
@@ -305,7 +375,7 @@ __device__ __forceinline__ void pack_stage(float* z, int lane) {
     if (N & 1) z[N / 2] = z[N - 1] + other(z[N - 1]);
   }
 }
-template <int NM>
+template <int NM, bool MASKED = false>
 __device__ __forceinline__ float wave_sum4_pack(const float (&v)[NM][GROUP]) {
   static_assert(GROUP == 4 && NM >= 1 && NM <= 16, "4 NM values, at most one per lane");
   const int lane = lane_id();
@@ -316,8 +386,8 @@ __device__ __forceinline__ float wave_sum4_pack(const float (&v)[NM][GROUP]) {
   for (int k = 0; k < NM; ++k)
 #pragma unroll
     for (int u = 0; u < GROUP; ++u) z[GROUP * k + u] = v[k][u];
-  pack_stage<8, N0>(z, lane);
-  pack_stage<4, N1>(z, lane);
+  pack_stage<8, N0, MASKED>(z, lane);
+  pack_stage<4, N1, MASKED>(z, lane);
   pack_stage<2, N2>(z, lane);
   pack_stage<1, N3>(z, lane);
   pack_stage<32, N4>(z, lane);
@@ -1336,7 +1406,8 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
       // and ONE ds_add_f32 (the lowest lane of every total, 4 NM lanes) adds the RAW moments to the tile-level
       // accumulator of the entry's chunk slot (they are relative to the entry's own mean, so the quadrants' sums simply
       // add; the flush turns them into the reference's terms).  A null entry adds zeros to slot 0.
-      float tot = wave_sum4_pack<NM>(v);
+      // (masked row stages except with ABS: those kernels sit at 128 VGPRs and the ten-pair statements make them spill)
+      float tot = wave_sum4_pack<NM, !ABS>(v);
       // (keeps the reduction whole in front of the masked tail)
       asm volatile("" : "+v"(tot));
       if (tail_adds) {
