@@ -47,6 +47,19 @@ class DensifyResult(ctypes.Structure):
     _fields_ = [("nonzero", c_int64), ("n_clone", c_int64), ("n_split", c_int64), ("threshold", c_float)]
 
 
+class McmcRecord(ctypes.Structure):
+    """gsr_mcmc_record (include/gsr.h)."""
+    _fields_ = [("n_dead", c_int64), ("n_alive", c_int64), ("n_draws", c_int64), ("total", ctypes.c_uint64)]
+
+
+class McmcTensor(ctypes.Structure):
+    """gsr_mcmc_tensor (include/gsr.h)."""
+    _fields_ = [("base", _P), ("dst", _P), ("values", _P), ("row_bytes", c_int64), ("role", ctypes.c_int32)]
+
+
+#: roles of a gsr_mcmc_tensor (include/gsr.h: GSR_MCMC_*)
+MCMC_COPY, MCMC_VALUE, MCMC_ZERO = 0, 1, 2
+
 #: every symbol include/gsr.h declares, with (restype, argtypes)
 SIGNATURES = {
     "gsr_abi_version": (c_int, []),
@@ -127,6 +140,16 @@ SIGNATURES = {
     "gsr_densify_plans": (c_int, [_P, c_int64, POINTER(_P), POINTER(_P)]),
     "gsr_densify_split_xyz": (c_int, [_P, c_int64, _P, _P, _P, _P, _P, c_int64, c_int, _P, _P]),
     "gsr_densify_keep": (c_int, [_P, c_int64, _P, _P, _P, _P, _P, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P]),
+    # the 3DGS-MCMC strategy (gaussianeditor_amd/mcmc.py): (stream, P, xyz, scaling_raw, rotation_raw, opacity_raw, noise,
+    # mask | NULL, k, x0, scaler); (P, bytes); (stream, P, n, opacity, mask | NULL, min_opacity, u, draws_from_dead, workspace,
+    # dead_sel, dead_idx, src, count, ratio, record); (stream, P, n, src, ratio, opacity, scaling_raw, min_opacity,
+    # new_opacity_raw, new_scaling_raw); (stream, P, n, src, dst_idx | NULL, dst_rows, num_tensors, tensors)
+    "gsr_mcmc_noise": (c_int, [_P, c_int64, _P, _P, _P, _P, _P, _P, ctypes.c_double, ctypes.c_double, ctypes.c_double]),
+    "gsr_mcmc_workspace_size": (c_int, [c_int64, POINTER(c_size_t)]),
+    "gsr_mcmc_sample": (c_int, [_P, c_int64, c_int64, _P, _P, ctypes.c_double, _P, c_int, _P, _P, _P, _P, _P, _P,
+                                POINTER(McmcRecord)]),
+    "gsr_mcmc_relocation_values": (c_int, [_P, c_int64, c_int64, _P, _P, _P, _P, ctypes.c_double, _P, _P]),
+    "gsr_mcmc_scatter": (c_int, [_P, c_int64, c_int64, _P, _P, c_int64, c_int, POINTER(McmcTensor)]),
     "gsr_adam_step": (c_int, [_P, c_int, POINTER(AdamTensor), c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P,
                             _P]),
     "gsr_adam_step_rows": (c_int, [_P, c_int, POINTER(AdamTensor), c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P,

@@ -1246,6 +1246,70 @@ int gsr_densify_keep(void* stream, int64_t P, const float* opacity, const float*
   return GSR_OK;
 }
 
+int gsr_mcmc_noise(void* stream, int64_t P, float* xyz, const float* scaling_raw, const float* rotation_raw,
+                   const float* opacity_raw, const float* noise, const uint8_t* mask, double k, double x0, double scaler) {
+  if (P < 0 || P > 0x7fffffffll) return GSR_ERR_BAD_ARGUMENT;
+  if (P == 0) return GSR_OK;
+  if (!xyz || !scaling_raw || !rotation_raw || !opacity_raw || !noise) return GSR_ERR_BAD_ARGUMENT;
+  if ((((uintptr_t)xyz | (uintptr_t)scaling_raw | (uintptr_t)opacity_raw | (uintptr_t)noise) & 3u) != 0 ||
+      ((uintptr_t)rotation_raw & 15u) != 0)
+    return GSR_ERR_BAD_ARGUMENT;
+  GSR_HIP(launch_mcmc_noise((hipStream_t)stream, P, xyz, scaling_raw, rotation_raw, opacity_raw, noise, mask, k, x0, scaler));
+  return GSR_OK;
+}
+
+int gsr_mcmc_workspace_size(int64_t P, size_t* bytes) {
+  if (P < 0 || P > 0x7fffffffll || !bytes) return GSR_ERR_BAD_ARGUMENT;
+  *bytes = mcmc_workspace_bytes(P);
+  return GSR_OK;
+}
+
+int gsr_mcmc_sample(void* stream, int64_t P, int64_t n, const float* opacity, const uint8_t* mask, double min_opacity,
+                    const float* u, int draws_from_dead, void* workspace, uint8_t* dead_sel, int32_t* dead_idx, int32_t* src,
+                    int32_t* count, int32_t* ratio, gsr_mcmc_record* record_host) {
+  if (!record_host) return GSR_ERR_BAD_ARGUMENT;
+  memset(record_host, 0, sizeof(*record_host));
+  if (P < 0 || P > 0x7fffffffll || n < 0 || n > 0x7fffffffll) return GSR_ERR_BAD_ARGUMENT;
+  if (P == 0) return GSR_OK;  // (no row to draw: nothing is written, the record stays zero)
+  if (!opacity || !workspace || !dead_sel || !dead_idx || !count || ((uintptr_t)workspace & 7u) != 0)
+    return GSR_ERR_BAD_ARGUMENT;
+  if (n > 0 && (!u || !src || !ratio)) return GSR_ERR_BAD_ARGUMENT;
+  hipStream_t s = (hipStream_t)stream;
+  GSR_HIP(launch_mcmc_sample(s, P, n, opacity, mask, (float)min_opacity, u, draws_from_dead, workspace, dead_sel, dead_idx, src,
+                             count, ratio));
+  GSR_HIP(hipMemcpyAsync(record_host, mcmc_record_ptr(workspace, P), sizeof(*record_host), hipMemcpyDeviceToHost, s));
+  GSR_HIP(hipStreamSynchronize(s));
+  return GSR_OK;
+}
+
+int gsr_mcmc_relocation_values(void* stream, int64_t P, int64_t n, const int32_t* src, const int32_t* ratio,
+                               const float* opacity, const float* scaling_raw, double min_opacity, float* new_opacity_raw,
+                               float* new_scaling_raw) {
+  if (P < 0 || P > 0x7fffffffll || n < 0 || n > 0x7fffffffll) return GSR_ERR_BAD_ARGUMENT;
+  if (P == 0 || n == 0) return GSR_OK;
+  if (!src || !ratio || !opacity || !scaling_raw || !new_opacity_raw || !new_scaling_raw) return GSR_ERR_BAD_ARGUMENT;
+  GSR_HIP(launch_mcmc_values((hipStream_t)stream, P, n, src, ratio, opacity, scaling_raw, (float)min_opacity, new_opacity_raw,
+                             new_scaling_raw));
+  return GSR_OK;
+}
+
+int gsr_mcmc_scatter(void* stream, int64_t P, int64_t n, const int32_t* src, const int32_t* dst_idx, int64_t dst_rows,
+                     int num_tensors, const gsr_mcmc_tensor* tensors) {
+  if (P < 0 || P > 0x7fffffffll || n < 0 || n > 0x7fffffffll || dst_rows < 0 || num_tensors < 0 || num_tensors > 32)
+    return GSR_ERR_BAD_ARGUMENT;
+  if (P == 0 || n == 0 || num_tensors == 0) return GSR_OK;
+  if (!src || !tensors) return GSR_ERR_BAD_ARGUMENT;
+  for (int i = 0; i < num_tensors; ++i) {
+    const gsr_mcmc_tensor& t = tensors[i];
+    if (t.role < GSR_MCMC_COPY || t.role > GSR_MCMC_ZERO || t.row_bytes < 4 || t.row_bytes > (1 << 20) || (t.row_bytes & 3) != 0)
+      return GSR_ERR_BAD_ARGUMENT;
+    if (!t.base || (t.role != GSR_MCMC_ZERO && !t.dst) || (t.role == GSR_MCMC_VALUE && !t.values)) return GSR_ERR_BAD_ARGUMENT;
+    if ((((uintptr_t)t.base | (uintptr_t)t.dst | (uintptr_t)t.values) & 3u) != 0) return GSR_ERR_BAD_ARGUMENT;
+  }
+  GSR_HIP(launch_mcmc_scatter((hipStream_t)stream, P, n, src, dst_idx, dst_rows, num_tensors, tensors));
+  return GSR_OK;
+}
+
 int gsr_debug_cov3d(void* stream, int P, const float* scales, float scale_modifier, const float* rotations, float* cov3D) {
   if (P <= 0) return GSR_OK;
   if (!scales || !rotations || !cov3D) return GSR_ERR_BAD_ARGUMENT;

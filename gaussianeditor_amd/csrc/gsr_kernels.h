@@ -186,6 +186,20 @@ hipError_t launch_densify_split_xyz(hipStream_t s, int64_t P, const float* xyz, 
 hipError_t launch_densify_keep(hipStream_t s, int64_t P, const float* opacity, const float* scaling, const float* max_radii,
                                const uint8_t* mask, const uint8_t* drop, float min_opacity, float max_screen, float big_ws,
                                uint8_t* keep);
+// the 3DGS-MCMC strategy (gsr_mcmc.hip)
+hipError_t launch_mcmc_noise(hipStream_t s, int64_t P, float* xyz, const float* scaling_raw, const float* rotation_raw,
+                             const float* opacity_raw, const float* noise, const uint8_t* mask, double k, double x0,
+                             double scaler);
+size_t mcmc_workspace_bytes(int64_t P);
+const gsr_mcmc_record* mcmc_record_ptr(void* workspace, int64_t P);
+hipError_t launch_mcmc_sample(hipStream_t s, int64_t P, int64_t n, const float* opacity, const uint8_t* mask,
+                              float min_opacity, const float* u, int draws_from_dead, void* workspace, uint8_t* dead_sel,
+                              int32_t* dead_idx, int32_t* src, int32_t* count, int32_t* ratio);
+hipError_t launch_mcmc_values(hipStream_t s, int64_t P, int64_t n, const int32_t* src, const int32_t* ratio,
+                              const float* opacity, const float* scaling_raw, float min_opacity, float* new_opacity_raw,
+                              float* new_scaling_raw);
+hipError_t launch_mcmc_scatter(hipStream_t s, int64_t P, int64_t n, const int32_t* src, const int32_t* dst_idx,
+                               int64_t dst_rows, int nt, const gsr_mcmc_tensor* tensors);
 hipError_t launch_adam_step(hipStream_t s, int nt, const gsr_adam_tensor* tensors, long long step, double beta1,
                             double beta2, double eps, const uint8_t* row_mask, const float* row_weight,
                             const uint8_t* grad_valid = nullptr);

@@ -70,7 +70,9 @@ extern "C" {
  * gsr_densify_workspace_size, gsr_densify_select, gsr_densify_plans, gsr_densify_split_xyz and gsr_densify_keep (the
  * densification policy; nothing existing changed).  Then, likewise additive: gsr_pose_workspace_size and gsr_pose_backward
  * (the camera gradient; no new flag bit, nothing existing changed).  Then, likewise additive:
- * GSR_MAX_FEATURE_CHANNELS, gsr_blend_forward_features and gsr_blend_backward_features (the feature image; no new flag bit). */
+ * GSR_MAX_FEATURE_CHANNELS, gsr_blend_forward_features and gsr_blend_backward_features (the feature image; no new flag bit).
+ * Then, likewise additive: gsr_mcmc_noise, gsr_mcmc_workspace_size, gsr_mcmc_sample, gsr_mcmc_relocation_values and
+ * gsr_mcmc_scatter (the 3DGS-MCMC strategy; no new flag bit, nothing existing changed). */
 #define GSR_ABI_VERSION 6
 /* The blend backward's accumulator table: GSR_ACC_ROW floats (one 64-byte line) per Gaussian, 64-byte aligned.  Columns:
  *   [GSR_ACC_MEAN2D] .x [+1] .y of dL_dmean2D      (backward.cu:545-546)
@@ -726,6 +728,81 @@ int gsr_densify_split_xyz(void* stream, int64_t P, const float* xyz, const float
 int gsr_densify_keep(void* stream, int64_t P, const float* opacity, const float* scaling, const float* max_radii2D,
                      const uint8_t* mask, const uint8_t* drop, double min_opacity, double max_screen_size, double extent,
                      uint8_t* keep);
+
+/* ---- the 3DGS-MCMC strategy (Kheradmand et al. 2024): noise, draws, relocation values, scatter ----
+ * No entry point allocates; each checks its arguments before it touches the device (NULL pointers, negative sizes, a
+ * misaligned workspace or tensor: GSR_ERR_BAD_ARGUMENT); P == 0 or n == 0 is a valid empty call.  Integer atomics only:
+ * every output is the same bits on every run.  P <= 2^31 - 1 (row numbers are int32).
+ *
+ * gsr_mcmc_noise: the positional noise of one training step, in place, one launch, no workspace, no readback.  xyz (P,3),
+ * scaling_raw (P,3), rotation_raw (P,4; 16-byte aligned), opacity_raw (P) the RAW parameters, noise (P,3) standard normal
+ * numbers drawn by the caller, mask (P) u8 or NULL.  Per row with mask != 0, in binary64 from the binary32 inputs, every
+ * operator one IEEE operation, rounded once at the store:
+ *   o = 1 / (1 + exp(-opacity_raw));  s = exp(scaling_raw);  n = sqrt(((r0*r0 + r1*r1) + r2*r2) + r3*r3), q = rot / n;
+ *   R = build_rotation(q) as gsr_densify_split_xyz writes its nine entries;  g = 1 / (1 + exp(k * (o - (1 - x0))));
+ *   v = (noise * g) * scaler;  w_c = (s_c*s_c) * ((R_0c*v_0 + R_1c*v_1) + R_2c*v_2)   [= diag(s^2) R^T v];
+ *   xyz_a = (float)(xyz_a + ((R_a0*w_0 + R_a1*w_1) + R_a2*w_2))                        [= xyz + R diag(s^2) R^T v].
+ * Rows with mask == 0 are neither read nor written. */
+int gsr_mcmc_noise(void* stream, int64_t P, float* xyz, const float* scaling_raw, const float* rotation_raw,
+                   const float* opacity_raw, const float* noise, const uint8_t* mask, double k, double x0, double scaler);
+
+/* gsr_mcmc_sample: classification and the opacity-weighted draws.  opacity (P) f32 ACTIVATED, mask (P) u8 or NULL (all
+ * rows), u (n) f32 in [0,1) drawn by the caller (torch.rand: multiples of 2^-24).
+ *   dead_j = mask_j && opacity_j <= (float)min_opacity;  alive_j = mask_j && opacity_j > (float)min_opacity  (a NaN is
+ *   neither);  k_j = (uint32)(opacity_j * 2^23) truncated (at most 2^23) for alive rows, 0 otherwise;  S_j = the inclusive
+ *   64-bit prefix sum of k, total = S_{P-1}.
+ *   draw r < n_draws: m = (uint64)(u_r * 2^24) (at most 2^24 - 1; a NaN or negative u draws as 0),
+ *   t = (m * total) >> 24 from the full 128-bit product, src_r = the smallest j with S_j > t.
+ * n_draws = n, or with draws_from_dead != 0 min(n_dead, n) (relocation: one draw per dead row, decided on the device).
+ * Outputs: dead_sel (P) u8; dead_idx (P) i32, its first n_dead entries the dead rows ascending (the rest untouched);
+ * src (n) i32, -1 for r >= n_draws or when total == 0; count (P) i32 = draws of row j; ratio (n) i32 =
+ * min(count[src_r] + 1, 51), 0 where src_r == -1.  workspace: gsr_mcmc_workspace_size(P) bytes of device scratch, 8-byte
+ * aligned.  *record_host is read back once, the only host synchronisation of the call; total == 0 with draws requested
+ * shows there (every src is -1). */
+typedef struct gsr_mcmc_record {
+  int64_t n_dead;
+  int64_t n_alive;
+  int64_t n_draws;
+  uint64_t total;
+} gsr_mcmc_record;
+int gsr_mcmc_workspace_size(int64_t P, size_t* bytes);
+int gsr_mcmc_sample(void* stream, int64_t P, int64_t n, const float* opacity, const uint8_t* mask, double min_opacity,
+                    const float* u, int draws_from_dead, void* workspace, uint8_t* dead_sel, int32_t* dead_idx, int32_t* src,
+                    int32_t* count, int32_t* ratio, gsr_mcmc_record* record_host);
+
+/* gsr_mcmc_relocation_values: for draw r with source s = src_r and N = ratio_r (clamped to 1..51), in binary64 from the
+ * binary32 inputs, rounded at the stores:
+ *   o = min(opacity_s, 1 - 2^-24);  o' = 1 - pow(1 - o, 1 / N);
+ *   denom = sum_{i=1..N} sum_{k=0..i-1} C(i-1,k) (-1)^k o'^(k+1) / sqrt(k+1)   (added in this order; the power by repeated
+ *   products; term = (C * power) / sqrt(k+1));  f = o / denom;  o' clamped to [(float)min_opacity, 1 - 2^-23];
+ *   new_opacity_raw_r = log(o' / (1 - o'));  new_scaling_raw_r,c = log(exp(scaling_raw_s,c) * f).
+ * opacity (P) ACTIVATED, scaling_raw (P,3) RAW; outputs (n) and (n,3), zeros where src_r is not a row.  Only inputs are
+ * read and only draw-indexed outputs written: the outputs may not alias the inputs. */
+int gsr_mcmc_relocation_values(void* stream, int64_t P, int64_t n, const int32_t* src, const int32_t* ratio,
+                               const float* opacity, const float* scaling_raw, double min_opacity, float* new_opacity_raw,
+                               float* new_scaling_raw);
+
+/* gsr_mcmc_scatter: the row writes of relocation and growth for up to 32 tensors, one launch per role in use.  Draw r has the source
+ * row s = src_r of `base` (P rows) and the destination row d = dst_idx_r (dst_idx != NULL) or r of `dst` (dst_rows rows;
+ * relocation: dst == base, dst_idx = the dead rows; growth: dst = the rows to append, dst_idx = NULL).
+ *   GSR_MCMC_COPY   dst[d] = base[s]
+ *   GSR_MCMC_VALUE  dst[d] = base[s] = values[r]        (values: (n) rows of row_bytes)
+ *   GSR_MCMC_ZERO   base[s] = 0                          (dst unused)
+ * Draws with src_r outside [0, P) write nothing, a d outside [0, dst_rows) no destination row.  The caller guarantees what
+ * gsr_mcmc_sample's outputs have: no source row is a destination row, and the draws of one source carry equal values.
+ * row_bytes a multiple of 4 up to 2^20, pointers 4-byte aligned. */
+#define GSR_MCMC_COPY 0
+#define GSR_MCMC_VALUE 1
+#define GSR_MCMC_ZERO 2
+typedef struct gsr_mcmc_tensor {
+  void* base;
+  void* dst;
+  const void* values;
+  int64_t row_bytes;
+  int32_t role;
+} gsr_mcmc_tensor;
+int gsr_mcmc_scatter(void* stream, int64_t P, int64_t n, const int32_t* src, const int32_t* dst_idx, int64_t dst_rows,
+                     int num_tensors, const gsr_mcmc_tensor* tensors);
 
 /* ---- the training loss: fused L1 + SSIM of two images, and its gradient ----
  * Replaces l1_loss / ssim of gaussiansplatting/utils/loss_utils.py:17-63 and the loss line of the reference's trainers,
