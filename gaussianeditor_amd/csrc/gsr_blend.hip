@@ -1270,38 +1270,49 @@ __device__ __forceinline__ uint32_t backward_tile(const BlendArgs& a, const uint
                         : DEPTH && col == ACC_DEPTH ? 9u
                         : ABS && (col == ACC_ABS2D || col == ACC_ABS2D + 1u) ? (uint32_t)IABS + (col - ACC_ABS2D)
                         : (uint32_t)NM;  // NM: the column is not used
+    // ONE exec region around the arithmetic of a flush instruction: the atomic's (the row mask's store and the zeroing are
+    // masked stores behind it).  A lane's role follows from its column alone -- which moments it reads, which of the entry's
+    // constants it multiplies by --, so the LDS reads are unconditional (a column without a moment reads moment 0 and adds
+    // nothing; a column with one moment reads it twice), the candidate terms are each the expression the column's own
+    // branch used to hold, operation for operation, and selects choose: a compare -> exec -> VALU turn costs about three
+    // selects (tools/microbench/issue_rate.hip), and the dispatch on the column was a chain of up to nine exec regions per
+    // instruction (profiles/k7_flush_used_slots_ab.md: 224 -> 122 s_*_saveexec in blend_backward_kernel<0,0,0,0,0>).
+    // No 0 * x stands in for "not this column": a non-finite constant of the entry reaches no column that did not multiply
+    // by it before.
+    const bool has = ia < (uint32_t)NM, mean = ia == 1u, xcol = col == ACC_MEAN2D;
+    const bool absc = ABS && has && ia >= (uint32_t)IABS, conic = ia >= 3u && ia <= 5u;
+    const uint32_t ra = has ? ia : 0u, rb = mean ? 2u : ra;
+    const float scale = (xcol || (ABS && col == ACC_ABS2D)) ? ddelx_dx : ddely_dy;
+    const uint32_t w16 = (uint32_t)__builtin_amdgcn_readfirstlane(16 * w);  // (scalar: the loop's exit is a scalar branch)
 #pragma unroll
     for (uint32_t jj = 0; jj < 4u; ++jj) {
-      const uint32_t p = 16u * (uint32_t)w + 4u * jj + sub;
-      if (16u * (uint32_t)w + 4u * jj >= fsize) break;  // (wave-uniform: slots >= fsize are never added to)
-      float* const row = sacc[fb][p];
-      const bool used = p < fsize && ia < (uint32_t)NM;
-      const float ma = used ? row[ia] : 0.f;
-      const float mb = used && ia == 1u ? row[2] : 0.f;
+      const uint32_t p = w16 + 4u * jj + sub;
+      if (w16 + 4u * jj >= fsize) break;  // (wave-uniform: slots >= fsize are never added to)
+      float* const row = sacc[fb][p];  // (p < 64: a slot >= fsize of the last, partial chunk holds zeros and a stale entry)
+      const float ma = row[ra], mb = row[rb];
       const float4 co = sco[fb][p];  // conic.x, conic.y, conic.z, opacity
-      float val;
-      bool nz;
-      if (ia == 1u) {
-        // backward.cu:545-546: dL_dmean2D = -o (A t1 + B t2, B t1 + C t2) * (0.5 W, 0.5 H)
-        const bool xcol = col == ACC_MEAN2D;
-        const float scale = xcol ? ddelx_dx : ddely_dy, c1 = xcol ? co.x : co.y, c2 = xcol ? co.y : co.z;
-        val = -(scale * co.w) * (c1 * ma + c2 * mb);
-        nz = ma != 0.f || mb != 0.f;
-      } else if (ABS && ia >= (uint32_t)IABS) {
-        // the per-pixel terms of dL_dmean2D in absolute value: |o| 0.5 W sum |A qx + B qy|, |o| 0.5 H sum |B qx + C qy|
-        val = ((col == ACC_ABS2D ? ddelx_dx : ddely_dy) * __builtin_fabsf(co.w)) * ma;
-        nz = ma != 0.f;
-      } else {
-        const bool conic = ia >= 3u && ia <= 5u;  // backward.cu:549-551: -0.5 o t; opacity (:554), colour (:523), depth: the moment itself
-        val = conic ? (-0.5f * co.w) * ma : ma;
-        nz = ma != 0.f;
-      }
-      if (used && nz) unsafeAtomicAdd(&a.acc[(size_t)sid[fb][p] * ACC_ROW + col], val);
+      const uint32_t id = sid[fb][p];
+      // backward.cu:545-546: dL_dmean2D = -o (A t1 + B t2, B t1 + C t2) * (0.5 W, 0.5 H)
+      const float c1 = xcol ? co.x : co.y, c2 = xcol ? co.y : co.z;
+      float v_mean = -(scale * co.w) * (c1 * ma + c2 * mb);
+      // the per-pixel terms of dL_dmean2D in absolute value: |o| 0.5 W sum |A qx + B qy|, |o| 0.5 H sum |B qx + C qy|
+      float v_abs = (scale * __builtin_fabsf(co.w)) * ma;
+      // backward.cu:549-551: -0.5 o t; opacity (:554), colour (:523), depth: the moment itself
+      float v_conic = (-0.5f * co.w) * ma;
+      // (keeps the candidates in front of the selects: left alone, hipcc sinks each into a branch on its column again)
+      if constexpr (ABS) asm volatile("" : "+v"(v_mean), "+v"(v_abs), "+v"(v_conic));
+      else asm volatile("" : "+v"(v_mean), "+v"(v_conic));
+      const float val = mean ? v_mean : absc ? v_abs : conic ? v_conic : ma;
+      const bool add = has && p < fsize && (ma != 0.f || mb != 0.f);  // (exact zeros are skipped)
+      if (add) unsafeAtomicAdd(&a.acc[(size_t)id * ACC_ROW + col], val);
       if (a.touched != nullptr) {  // (wave-uniform) the exchange's row mask, without a pass over the table: lane 15 of a
-        const uint64_t nzm = __ballot(used && nz);  // group marks the group's Gaussian if any of its columns was added to
-        if (col == 15u && p < fsize && ((nzm >> (16u * sub)) & 0xffffull) != 0ull) a.touched[sid[fb][p]] = 1;
+        const uint64_t nzm = __ballot(add);  // group marks the group's Gaussian if any of its columns was added to
+        if (col == 15u && ((nzm >> (16u * sub)) & 0xffffull) != 0ull) a.touched[id] = 1;
       }
-      if (p < fsize && col < (uint32_t)NM) row[col] = 0.f;  // (every read of this instruction precedes it: one wave, program order)
+      // (every read of this instruction precedes it: one wave, program order.  The rows >= fsize are zero already: the
+      // store's mask is the column's alone.  And the store races with no ds_add_f32: fb is the idle parity -- this
+      // iteration's groups add to the other buffer, and the next adds to fb lie behind barrier (B))
+      if (col < (uint32_t)NM) row[col] = 0.f;
     }
   };
 

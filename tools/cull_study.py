@@ -4,12 +4,17 @@ For a sample of tiles of synth-v1 (1 M Gaussians, 1080p, view 0) and each 8x8 qu
 (up to the quadrant's largest n_contrib), how many pass (a) the present box test (can_touch_quad), (b) an exact test of
 the alpha >= 1/255 ellipse against the quadrant's pixel-centre rectangle, (c) have a pixel that really blends them.
 
-    python tools/cull_study.py [P] [tiles_sampled] [s0] [--live]
+    python tools/cull_study.py [P] [tiles_sampled] [s0] [--live] [--slots] [--v2]
 
 --live adds the study behind `live_pixel_box` (gsr_blend.hip): for every quadrant item of the view, the entries the exact
 test keeps against the whole quadrant and against the bounding box of the pixels that are still live when a chunk starts
 (approximated by n_contrib: a pixel is live at least up to its last contributor), for the 300 items with the most
 evaluated entries, the 20 longest of those, and 600 random items; plus how well the list length predicts an item's work.
+
+--slots adds the study behind K7's flush (backward_tile): for every 64-entry chunk the backward walks of the sampled tiles
+(back to front from the tile's deepest contributor, as ChunkWalker<false> does), the number of distinct chunk slots that at
+least one quadrant keeps -- the exact test against the live pixels' box, or slot 0 where a quadrant pads its last group with
+null entries -- i.e. the slots the flush has to visit.  --v2 takes synth-v2 instead of synth-v1.
 """
 import math
 import os
@@ -27,7 +32,11 @@ P = int(_pos[0]) if len(_pos) > 0 else 1_000_000
 NT = int(_pos[1]) if len(_pos) > 1 else 300
 s0 = float(_pos[2]) if len(_pos) > 2 else 0.01
 W, H = 1920, 1080
-sc = synth_scene(P, seed=0, s0=s0)
+if "--v2" in sys.argv:
+    from gaussianeditor_amd.synth import synth_scene_v2  # noqa: E402
+    sc = synth_scene_v2(P, seed=0)
+else:
+    sc = synth_scene(P, seed=0, s0=s0)
 cam = ring_cameras(8, W, H)[0]
 tfx, tfy = math.tan(cam.FoVx / 2), math.tan(cam.FoVy / 2)
 n = lambda t: t.numpy()  # noqa: E731
@@ -152,5 +161,47 @@ def _live_study():
     study(items[np.random.default_rng(1).choice(len(items), min(600, len(items)), replace=False)], "random")
 
 
+def _slots_study():
+    used, kept_pairs, chunks_of_tile = [], 0, []
+    for t in tiles:
+        ty, tx = divmod(int(t), gx)
+        ids = binning["point_list"][ranges[t, 0]:ranges[t, 1]]
+        quads = []
+        for q in range(4):
+            x0, y0 = tx * 16 + 8 * (q & 1), ty * 16 + 8 * (q >> 1)
+            if x0 < W and y0 < H:
+                quads.append((x0, y0, ncontrib[y0:y0 + 8, x0:x0 + 8].astype(np.int64)))
+        tile_max = max(int(nc.max()) for (_x, _y, nc) in quads)
+        nchunks = 0
+        for hi in range(tile_max, 0, -64):  # chunk = positions [lo, hi), lane l holds position lo + l
+            lo = max(hi - 64, 0)
+            g = ids[lo:hi]
+            union = np.zeros(len(g), dtype=bool)
+            for (x0, y0, nc) in quads:
+                ys, xs = np.nonzero(nc > lo)  # the pixels whose last contributor lies above the chunk's lowest position
+                if len(ys) == 0:
+                    continue
+                keep = _exact_mask(g, x0 + xs.min(), y0 + ys.min(), xs.max() - xs.min(), ys.max() - ys.min())
+                keep &= (lo + np.arange(len(g))) < int(nc.max())
+                kept_pairs += int(keep.sum())
+                union |= keep
+                if keep.sum() % 4:
+                    union[0] = True  # the null entries that fill the quadrant's last group add their zeros to slot 0
+            used.append(int(union.sum()))
+            nchunks += 1
+        chunks_of_tile.append(nchunks)
+    used = np.array(used)
+    edges = [0, 1, 5, 9, 13, 17, 25, 33, 49, 65]
+    hist = np.histogram(used, bins=edges)[0]
+    print("slots study: %d tiles, %d tile-chunks (mean %.1f, max %d per tile), %d (quadrant, entry) pairs kept" % (
+        len(tiles), len(used), np.mean(chunks_of_tile), max(chunks_of_tile), kept_pairs))
+    print("distinct used slots per tile-chunk: mean %.2f, median %.0f, p90 %.0f, p99 %.0f, max %d; flush instructions "
+          "ceil(nu / 4): mean %.2f of 16" % (used.mean(), np.median(used), np.percentile(used, 90), np.percentile(used, 99),
+                                             used.max(), np.ceil(used / 4).mean()))
+    print("histogram  " + "  ".join("%d-%d: %.3f" % (edges[i], edges[i + 1] - 1, hist[i] / len(used)) for i in range(len(hist))))
+
+
 if "--live" in sys.argv:
     _live_study()
+if "--slots" in sys.argv:
+    _slots_study()
