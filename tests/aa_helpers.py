@@ -8,6 +8,8 @@ autograd then carries the h-term to means3D, scales, rotations and cov3D_precomp
 come from the float32 oracle in reference tile bounds, which do not depend on the opacity.  The float32 oracle at the
 product's effective opacities (rec0.w) supplies n_contrib / final_T for the flipped-pixel masks.
 """
+import functools
+
 import numpy as np
 import torch
 
@@ -106,35 +108,37 @@ def coverage(final_T, W, H):
 NEW_CASES = ["sub_pixel", "floor", "edit_view"]
 
 
-def regime(name):
+def regime(name, camera=None):
     """The cases of f64_regimes.regime() and three that only the flag has: sub_pixel (many visible rows with
-    0.05 < h < 0.9), floor (needles whose r lies below the floor) and edit_view (a 512 x 512 view with long lists)."""
+    0.05 < h < 0.9), floor (needles whose r lies below the floor) and edit_view (a 512 x 512 view with long lists).
+    `camera`: as in f64_regimes.regime."""
+    mk = functools.partial(make_case, camera=camera)
     if name == "saturated":
         # under the flag an opacity of 0.998 becomes o h < 0.99 on most footprints: larger Gaussians (h ~ 0.997) and
         # opacities in [0.9995, 0.99999] keep o h G > 0.99 near their centres (~130 saturated pairs, ~10 000 stopped pixels)
-        r = R.regime(name)
+        r = R.regime(name, camera=camera)
         sc = dict(r["case"]["sc"], scaling=(r["case"]["sc"]["scaling"] * 2.5).contiguous())
         u = torch.rand(sc["xyz"].shape[0], 1, generator=torch.Generator().manual_seed(62))
         sc["opacity"] = (0.9995 + 0.00049 * u).contiguous()
         r["case"]["sc"] = sc
         return r
     if name in R.CASES:
-        return R.regime(name)
+        return R.regime(name, camera=camera)
     D, sm = 3, 1.0
     if name == "sub_pixel":
         # small Gaussians far from a low-resolution camera: most footprints are below a pixel
-        case = make_case(3000, 120, 88, seed=91, s0=0.006, view=1, scale_xyz=0.8, bg=(0.2, 0.5, 0.7))
+        case = mk(3000, 120, 88, seed=91, s0=0.006, view=1, scale_xyz=0.8, bg=(0.2, 0.5, 0.7))
     elif name == "floor":
         # half of the Gaussians are needles (scales 0.01 x 1e-6 x 1e-6): their footprints are lines a few pixels long whose
         # det(S) / det(S + w I) lies far below the floor -- and short enough that float32's x y - z^2 stays far below it too
         # (its rounding is ~1e-7 x y / D < 1e-8 here)
-        case = make_case(3000, 200, 136, seed=93, s0=0.04, view=2, scale_xyz=0.8, bg=(0.2, 0.5, 0.7))
+        case = mk(3000, 200, 136, seed=93, s0=0.04, view=2, scale_xyz=0.8, bg=(0.2, 0.5, 0.7))
         s = case["sc"]["scaling"].clone()
         s[:1500] = torch.tensor([0.01, 1e-6, 1e-6])
         case["sc"]["scaling"] = s.contiguous()
     elif name == "edit_view":
         # mean list ~330 entries per tile, ~200 of the 1 024 tiles longer than 256 (cut into segments when forced)
-        case = make_case(8000, 512, 512, seed=95, s0=0.1, view=0, scale_xyz=0.6, bg=(0.2, 0.5, 0.7))
+        case = mk(8000, 512, 512, seed=95, s0=0.1, view=0, scale_xyz=0.6, bg=(0.2, 0.5, 0.7))
     else:
         raise KeyError(name)
     case["D"] = D

@@ -14,6 +14,8 @@ except the first):
 Rows that may be masked are counted and bounded: Gaussians under pixels whose float64 and float32 discrete decisions differ
 (helpers.flipped_pixels / gaussians_under), and Gaussians within float rounding of the 1.3 tan(fov) cone edge.
 """
+import functools
+
 import numpy as np
 import torch
 
@@ -29,34 +31,38 @@ SH_CASES = ["sh_D0", "sh_D1", "sh_D2", "sh_D3", "clamped_colours", "scale_mod_0.
             "unnormalised_quat"]
 
 
-def _v2_case(P, W, H, seed, view=3):
+def _v2_case(P, W, H, seed, view=3, camera=None):
     """A synth-v2 scene seen from a ring camera inside its dome: every view from inside a scene has Gaussians beside and
     behind the camera, and some of them beyond the 1.3 tan(fov) cone still touch the image."""
     from gaussianeditor_amd.synth import synth_scene_v2
 
-    case = make_case(P, W, H, seed=seed, view=view, nviews=8, bg=(0.2, 0.5, 0.7))
+    case = make_case(P, W, H, seed=seed, view=view, nviews=8, bg=(0.2, 0.5, 0.7), camera=camera)
     case["sc"] = synth_scene_v2(P, seed=seed)
     return case
 
 
-def regime(name):
-    """-> dict(name, case, D, sm, colors_precomp, cov3D_precomp, G, GD): the case `name` of CASES."""
+def regime(name, camera=None, seed=None):
+    """-> dict(name, case, D, sm, colors_precomp, cov3D_precomp, G, GD): the case `name` of CASES.  `camera`: a name of
+    camera_cases.CAMERAS, the case seen through that general camera built on its ring camera (None: the ring camera);
+    `seed`: another scene seed than the case's own (the pose comparison needs scenes without a flipped pixel)."""
     D, sm, cols, cov, GD = 3, 1.0, None, None, None
+    mk, v2 = functools.partial(make_case, camera=camera), functools.partial(_v2_case, camera=camera)
+    own = lambda default: default if seed is None else seed  # noqa: E731
     if name.startswith("sh_D"):
         D = int(name[-1])
-        case = make_case(3000, 200, 136, seed=21 + D, s0=0.04, view=1, scale_xyz=0.8, bg=(0.2, 0.5, 0.7))
+        case = mk(3000, 200, 136, seed=own(21 + D), s0=0.04, view=1, scale_xyz=0.8, bg=(0.2, 0.5, 0.7))
     elif name == "clamped_colours":
-        case = make_case(3000, 184, 120, seed=31, s0=0.04, view=2, scale_xyz=0.8, bg=(0.3, 0.1, 0.6))
+        case = mk(3000, 184, 120, seed=own(31), s0=0.04, view=2, scale_xyz=0.8, bg=(0.3, 0.1, 0.6))
         f = case["sc"]["features"].clone()
         f[:, 0] -= 1.5  # the DC term pulls rgb = 0.28 * dc + 0.5 + ... below zero for a good share of the channels
         case["sc"]["features"] = f.contiguous()
     elif name.startswith("scale_mod_"):
         sm = float(name.split("_")[-1])
-        case = make_case(2500, 168, 152, seed=41 if sm < 1 else 42, s0=0.05, view=0, scale_xyz=0.8, bg=(0.2, 0.5, 0.7))
+        case = mk(2500, 168, 152, seed=own(41 if sm < 1 else 42), s0=0.05, view=0, scale_xyz=0.8, bg=(0.2, 0.5, 0.7))
     elif name in ("colors_precomp", "cov3D_precomp", "both_precomp"):
         from oracle import cpu
 
-        case = make_case(2500, 200, 120, seed=51, s0=0.05, view=3, scale_xyz=0.8, bg=(0.2, 0.5, 0.7))
+        case = mk(2500, 200, 120, seed=own(51), s0=0.05, view=3, scale_xyz=0.8, bg=(0.2, 0.5, 0.7))
         if name != "cov3D_precomp":
             cols = torch.rand(2500, 3, generator=torch.Generator().manual_seed(52)).contiguous()
         if name != "colors_precomp":
@@ -68,20 +74,20 @@ def regime(name):
                                                case["cam"].camera_center, case["bg"], case["W"], case["H"], case["tfx"],
                                                case["tfy"], 1.0, 3)["cov3D"].copy())
     elif name == "off_cone":
-        case = _v2_case(4000, 216, 120, seed=11)
+        case = v2(4000, 216, 120, seed=own(11))
     elif name == "saturated":
         # o in [0.998, 0.9999]: o*G > 0.99 within ~0.14 sigma of a centre.  A pixel stops after two such instances, so the
         # saturated pairs are a fixed small share of the image whatever the density: hence the larger image
-        case = make_case(800, 248, 200, seed=61, s0=0.1, view=1, scale_xyz=0.7, bg=(0.2, 0.5, 0.7))
+        case = mk(800, 248, 200, seed=own(61), s0=0.1, view=1, scale_xyz=0.7, bg=(0.2, 0.5, 0.7))
         u = torch.rand(800, 1, generator=torch.Generator().manual_seed(62))
         case["sc"]["opacity"] = (0.998 + 0.0019 * u).contiguous()
     elif name == "unnormalised_quat":
-        case = make_case(3000, 200, 136, seed=71, s0=0.025, view=2, scale_xyz=0.8, bg=(0.2, 0.5, 0.7))
+        case = mk(3000, 200, 136, seed=own(71), s0=0.025, view=2, scale_xyz=0.8, bg=(0.2, 0.5, 0.7))
         g = torch.Generator().manual_seed(72)
         norms = torch.exp(torch.empty(3000, 1).uniform_(float(np.log(0.5)), float(np.log(2.0)), generator=g))
         case["sc"]["rotation"] = (case["sc"]["rotation"] * norms).contiguous()
     elif name == "depth":
-        case = _v2_case(4000, 200, 136, seed=13, view=5)
+        case = v2(4000, 200, 136, seed=own(13), view=5)
         GD = seed_gradient(136, 200, 81)[:1] * 136 * 200
     else:
         raise KeyError(name)

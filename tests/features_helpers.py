@@ -34,15 +34,16 @@ def feature_gradient(H, W, C):
     return g[:C].contiguous()
 
 
-def feature_case(name, C=None):
-    """(case, G, GF, feats) of CASES[name] (with another channel count if `C` is given) -- built once, never modified."""
+def feature_case(name, C=None, camera=None):
+    """(case, G, GF, feats) of CASES[name] (with another channel count if `C` is given, through the camera `camera` of
+    camera_cases.CAMERAS if one is) -- built once, never modified."""
     kw = CASES[name]
     C = kw["C"] if C is None else C
-    if (name, C) not in _cache:
-        case = make_case(kw["P"], kw["W"], kw["H"], s0=kw["s0"])
+    if (name, C, camera) not in _cache:
+        case = make_case(kw["P"], kw["W"], kw["H"], s0=kw["s0"], camera=camera)
         H, W = case["H"], case["W"]
-        _cache[(name, C)] = (case, seed_gradient(H, W, 3) * H * W, feature_gradient(H, W, C), make_features(kw["P"], C))
-    return _cache[(name, C)]
+        _cache[(name, C, camera)] = (case, seed_gradient(H, W, 3) * H * W, feature_gradient(H, W, C), make_features(kw["P"], C))
+    return _cache[(name, C, camera)]
 
 
 def small_gaussian_case(C=5):

@@ -8,12 +8,18 @@ import torch
 from gaussianeditor_amd.synth import ring_cameras, seed_gradient, synth_scene
 
 
-def make_case(P, W, H, seed=1, s0=0.03, view=0, nviews=4, sh_degree=3, scale_xyz=1.0, bg=(0.1, 0.2, 0.3)):
+def make_case(P, W, H, seed=1, s0=0.03, view=0, nviews=4, sh_degree=3, scale_xyz=1.0, bg=(0.1, 0.2, 0.3), camera=None):
+    """`camera`: a name of camera_cases.CAMERAS -- the ring camera with unequal focal lengths, roll and / or an off-centre
+    principal axis -- or None for the ring camera itself."""
     sc = synth_scene(P, seed=seed, s0=s0, sh_degree=sh_degree)
     sc["xyz"] = (sc["xyz"] * scale_xyz).contiguous()
     cam = ring_cameras(nviews, W, H)[view]
-    case = dict(sc=sc, cam=cam, W=W, H=H, tfx=math.tan(cam.FoVx / 2), tfy=math.tan(cam.FoVy / 2),
-                bg=torch.tensor(bg, dtype=torch.float32), D=sh_degree)
+    tfx, tfy = math.tan(cam.FoVx / 2), math.tan(cam.FoVy / 2)
+    if camera is not None:
+        from camera_cases import named_camera
+
+        cam, tfx, tfy = named_camera(camera, cam, W, H)
+    case = dict(sc=sc, cam=cam, W=W, H=H, tfx=tfx, tfy=tfy, bg=torch.tensor(bg, dtype=torch.float32), D=sh_degree)
     return case
 
 

@@ -32,6 +32,9 @@ Bars.
     never below TOL.
   * translation identity: per component 7e-7 x sum_i |dL/dmu_i|, 4 x the worst ratio (1.7e-7) the float32 oracle shows
     against float64 on this identity; on the scene of identity_case() the oracle shows IDENTITY_ORACLE_RATIO.
+  * general cameras (camera_cases.py: unequal focal lengths, roll, off-centre axis; rows of camera_cases.POSE_PAIRS): the
+    same bars.  tools/pose_bars.py --camera NAME shows campos reference figures of at most 3.49e-06 (below
+    CAMPOS_ORACLE_WORST) and an identity ratio of 1.5e-7 under `all` (below 1.7e-7); the tables are in DESIGN.md section 19.
 """
 import numpy as np
 import torch
@@ -47,13 +50,14 @@ IDENTITY_TOL = 7e-7
 IDENTITY_ORACLE_RATIO = 4.8e-8  # re-measured on identity_case() (tools/pose_bars.py); other seeds / views: DESIGN.md section 19
 
 
-def pose_regime(name):
-    """The regime `name` of POSE_CASES: a case of f64_regimes, `off_cone+depth` = off_cone with a depth gradient."""
+def pose_regime(name, camera=None, seed=None):
+    """The regime `name` of POSE_CASES: a case of f64_regimes, `off_cone+depth` = off_cone with a depth gradient.  `camera`,
+    `seed`: as in f64_regimes.regime."""
     if name == "off_cone+depth":
-        r = R.regime("off_cone")
+        r = R.regime("off_cone", camera=camera, seed=seed)
         H, W = r["case"]["H"], r["case"]["W"]
         return dict(r, GD=seed_gradient(H, W, 81)[:1] * H * W)
-    return R.regime(name)
+    return R.regime(name, camera=camera, seed=seed)
 
 
 class LeafCam:
@@ -104,11 +108,12 @@ def assert_pose_close(got, want, tag, colors_precomp=False):
 
 
 # ---- translation identity -------------------------------------------------------------------------------------------
-def identity_case(P=2000, W=136, H=120, seed=11, view=0):
-    """A synth-v2 view from inside the scene's dome (Gaussians beside and behind the camera, some off the cone)."""
+def identity_case(P=2000, W=136, H=120, seed=11, view=0, camera=None):
+    """A synth-v2 view from inside the scene's dome (Gaussians beside and behind the camera, some off the cone); `camera`: a
+    name of camera_cases.CAMERAS, the view through that general camera."""
     from gaussianeditor_amd.synth import synth_scene_v2
 
-    case = make_case(P, W, H, seed=seed, view=view, nviews=8, bg=(0.2, 0.5, 0.7))
+    case = make_case(P, W, H, seed=seed, view=view, nviews=8, bg=(0.2, 0.5, 0.7), camera=camera)
     case["sc"] = synth_scene_v2(P, seed=seed)
     return case
 

@@ -26,13 +26,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _cache = {}
 
 
-def _case(name="p2000"):
-    """(case, G, GA) -- built once per process, never modified."""
-    if name not in _cache:
+def _case(name="p2000", camera=None):
+    """(case, G, GA) -- built once per process, never modified.  `camera`: a name of camera_cases.CAMERAS."""
+    if (name, camera) not in _cache:
         P, W, H, s0 = {"p2000": (2000, 64, 64, 0.05), "p20000": (20000, 64, 64, 0.03), "ragged": (2000, 70, 45, 0.05)}[name]
-        case = make_case(P, W, H, s0=s0)
-        _cache[name] = (case, seed_gradient(H, W, 3) * H * W, seed_gradient(H, W, 5)[:1] * H * W)
-    return _cache[name]
+        case = make_case(P, W, H, s0=s0, camera=camera)
+        _cache[name, camera] = (case, seed_gradient(H, W, 3) * H * W, seed_gradient(H, W, 5)[:1] * H * W)
+    return _cache[name, camera]
 
 
 def _forward_state(case, flags=0, **kw):
@@ -153,8 +153,8 @@ def test_alpha_of_a_render_served_by_view_reuse(oracle):
 
 # ---------------------------------------------------------------------------------------------------------------------
 # backward
-def _check(oracle, name, tag, alpha_only=False, with_depth=False, **kw):
-    case, G, GA = _case(name)
+def _check(oracle, name, tag, alpha_only=False, with_depth=False, camera=None, **kw):
+    case, G, GA = _case(name, camera)
     H, W = case["H"], case["W"]
     G = None if alpha_only else G
     GD = seed_gradient(H, W, 7)[:1] * H * W if with_depth else None

@@ -61,9 +61,13 @@ def _rec0w(case, flags=0, **kw):
 @pytest.mark.parametrize("bounds", ["reference", "alpha"])
 @pytest.mark.parametrize("name", ["sub_pixel", "floor", "off_cone"])
 def test_forward_is_the_plain_forward_at_rec0w(name, bounds):
+    _check_forward_at_rec0w(name, bounds)
+
+
+def _check_forward_at_rec0w(name, bounds, camera=None):
     from gaussianeditor_amd import options
 
-    r = A.regime(name)
+    r = A.regime(name, camera=camera)
     case = r["case"]
     P, W, H = case["sc"]["xyz"].shape[0], case["W"], case["H"]
     tb = options.FLAG_TILE_BOUNDS_ALPHA if bounds == "alpha" else 0
@@ -121,12 +125,12 @@ def test_antialiasing_changes_sub_pixel_images_and_keeps_their_mass():
 
 # ---- 3. / 4. backward against float64 autograd ----------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
-def _expectation(name):
+def _expectation(name, camera=None):
     """-> (regime, float32 oracle forward at the product's rec0.w, float64 gradients, stats, masked rows)."""
     from oracle import cpu
 
     cpu.build()
-    r = A.regime(name)
+    r = A.regime(name, camera=camera)
     ow = _rec0w(r["case"], D=r["D"], colors_precomp=r["colors_precomp"], cov3D_precomp=r["cov3D_precomp"], sm=r["sm"])
     sc = dict(r["case"]["sc"], opacity=torch.from_numpy(ow).reshape(-1, 1))
     f = oracle_forward(cpu, dict(r["case"], sc=sc), colors_precomp=r["colors_precomp"], cov3D_precomp=r["cov3D_precomp"],
@@ -137,11 +141,11 @@ def _expectation(name):
     return r, f, want, stats, masked, geom
 
 
-def _check(name, route):
+def _check(name, route, camera=None):
     from gaussianeditor_amd import options
     from test_gpu_f64_regimes import _bucket, _l1
 
-    r, f, want, stats, masked, geom = _expectation(name)
+    r, f, want, stats, masked, geom = _expectation(name, camera)
     with options.override(options.current_flags() | _aa()):
         got = _l1(r) if route == "l1" else _bucket(r, route)
     assert all(np.isfinite(v).all() for v in got.values()), (name, route, "a gradient entry was never written")

@@ -25,16 +25,17 @@ BUCKET_KEYS = dict(means3D="dL_dmeans3D", sh="dL_dsh", opacities="dL_dopacity", 
 
 
 @functools.lru_cache(maxsize=None)
-def _expectation(name):
-    """-> (regime, float32 oracle forward, float64 gradients, render_f64 stats, masked rows): computed once per case."""
+def _expectation(name, camera=None):
+    """-> (regime, float32 oracle forward, float64 gradients, render_f64 stats, masked rows): computed once per case (and
+    per camera of camera_cases.CAMERAS; None: the case's ring camera)."""
     from oracle import cpu
 
     cpu.build()
-    r = R.regime(name)
+    r = R.regime(name, camera=camera)
     f, _ = R.oracle_run(cpu, r)
     want, stats, _ = R.f64_run(f, r)
     masked, report = R.masked_rows(r, f, stats)
-    print(f"[{name}] {report}")
+    print(f"[{name}{'' if camera is None else ', ' + camera}] {report}")
     return r, f, want, stats, masked
 
 
@@ -110,8 +111,8 @@ def _bucket(r, mode):
     return {BUCKET_KEYS[k]: v.cpu().numpy() for k, v in grads.items()}
 
 
-def _check(name, route):
-    r, f, want, stats, masked = _expectation(name)
+def _check(name, route, camera=None):
+    r, f, want, stats, masked = _expectation(name, camera)
     got = _l1(r) if route == "l1" else _bucket(r, route)
     assert all(np.isfinite(v).all() for v in got.values()), (name, route, "a gradient entry was never written")
     R.regime_count(r, f, want, stats, got=got)

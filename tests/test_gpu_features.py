@@ -188,8 +188,8 @@ def test_a_skipped_entrys_features_never_enter_a_pixels_sum(oracle):
 
 # ---------------------------------------------------------------------------------------------------------------------
 # backward
-def _check(oracle, name, tag, colour=True, depth=False, alpha=False, **kw):
-    case, G, GF, feats = FH.feature_case(name)
+def _check(oracle, name, tag, colour=True, depth=False, alpha=False, camera=None, **kw):
+    case, G, GF, feats = FH.feature_case(name, camera=camera)
     H, W = case["H"], case["W"]
     G = G if colour else None
     GD = seed_gradient(H, W, 81)[:1] * H * W if depth else None

@@ -169,7 +169,11 @@ def test_backward_run_to_run_spread():
 
 
 def test_mark_visible(oracle):
-    case = make_case(5000, 64, 64, seed=10, scale_xyz=4.0)
+    _check_mark_visible(oracle)
+
+
+def _check_mark_visible(oracle, camera=None):
+    case = make_case(5000, 64, 64, seed=10, scale_xyz=4.0, camera=camera)
     cam = case["cam"]
     ref = oracle.mark_visible(case["sc"]["xyz"], cam.world_view_transform, cam.full_proj_transform)
     got = _c().mark_visible(case["sc"]["xyz"].to(DEV), cam.world_view_transform.to(DEV), cam.full_proj_transform.to(DEV))
@@ -179,10 +183,14 @@ def test_mark_visible(oracle):
 
 @pytest.mark.parametrize("C,W,H", [(1, 256, 256), (1, 250, 131), (2, 128, 96), (3, 100, 100)])
 def test_apply_weights(oracle, C, W, H):
+    _check_apply_weights(oracle, C, W, H)
+
+
+def _check_apply_weights(oracle, C, W, H, camera=None):
     from gaussianeditor_amd.diff_gaussian_rasterization import GaussianRasterizer
 
     P = 6000
-    case = make_case(P, W, H, seed=11, s0=0.04)
+    case = make_case(P, W, H, seed=11, s0=0.04, camera=camera)
     sc, cam = case["sc"], case["cam"]
     gen = torch.Generator().manual_seed(12)
     mask = (torch.rand(C, H, W, generator=gen) > 0.5).float()  # 0/1 masks: sums are exact in any order

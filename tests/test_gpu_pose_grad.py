@@ -95,11 +95,11 @@ def _product_pose(r, flags_extra=0):
 
 
 @functools.lru_cache(maxsize=None)
-def _expectation(name):
+def _expectation(name, camera=None, seed=None):
     from oracle import cpu
 
     cpu.build()  # (the cov3D_precomp regime takes its covariances from the oracle's forward)
-    r = PH.pose_regime(name)
+    r = PH.pose_regime(name, camera=camera, seed=seed)
     f = _product_forward_state(r)
     want_cam, want, stats = PH.f64_pose(f, r)
     flips = flipped_pixels(stats["n_contrib"].numpy(), stats["final_T"].numpy(), f["n_contrib"], f["final_T"])

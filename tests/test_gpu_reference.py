@@ -38,7 +38,10 @@ CASES = [(10000, 256, 256, 0.03, 1), (3000, 250, 131, 0.05, 2), (20000, 512, 512
 
 @pytest.mark.parametrize("P,W,H,s0,seed", CASES)
 def test_oracle_is_pinned_by_reference_nofma(oracle, P, W, H, s0, seed):
-    case = make_case(P, W, H, seed=seed, s0=s0)
+    _check_oracle_is_pinned(oracle, make_case(P, W, H, seed=seed, s0=s0))
+
+
+def _check_oracle_is_pinned(oracle, case):
     f = oracle_forward(oracle, case)
     r = _ref_forward(_ref("nofma"), case)
     vis = f["radii"] > 0
@@ -68,10 +71,13 @@ def test_oracle_is_pinned_by_reference_nofma(oracle, P, W, H, s0, seed):
 @pytest.mark.parametrize("P,W,H,s0,seed", CASES)
 def test_product_vs_reference_fma(P, W, H, s0, seed):
     """The HIP path against the reference as hipcc builds it by default (contraction on)."""
+    _check_product_vs_reference_fma(make_case(P, W, H, seed=seed, s0=s0), seed)
+
+
+def _check_product_vs_reference_fma(case, seed):
     from gaussianeditor_amd.diff_gaussian_rasterization import GaussianRasterizer
 
-    case = make_case(P, W, H, seed=seed, s0=s0)
-    sc = case["sc"]
+    sc, P, W, H = case["sc"], case["sc"]["xyz"].shape[0], case["W"], case["H"]
     r = _ref_forward(_ref("fma"), case)
     leaf = lambda t: t.to(DEV).clone().requires_grad_(True)  # noqa: E731
     xyz, op, sh, scl, rot = leaf(sc["xyz"]), leaf(sc["opacity"]), leaf(sc["features"]), leaf(sc["scaling"]), leaf(sc["rotation"])
@@ -113,18 +119,21 @@ def test_product_vs_reference_fma(P, W, H, s0, seed):
 
 def test_product_vs_reference_nofma_integers():
     """Against the contraction-free reference build the product's integer outputs are bit-exact."""
+    _check_product_vs_reference_nofma_integers(make_case(20000, 512, 512, seed=4, s0=0.02))
+
+
+def _check_product_vs_reference_nofma_integers(case):
     from gaussianeditor_amd.diff_gaussian_rasterization import _C
 
-    case = make_case(20000, 512, 512, seed=4, s0=0.02)
-    sc, cam = case["sc"], case["cam"]
+    sc, cam, P, W, H = case["sc"], case["cam"], case["sc"]["xyz"].shape[0], case["W"], case["H"]
     r = _ref_forward(_ref("nofma"), case)
     e = torch.empty(0, device=DEV)
     d = lambda t: t.to(DEV)  # noqa: E731
     R, color, depth, radii, geom, binning, img = _C.rasterize_gaussians(
         d(case["bg"]), d(sc["xyz"]), e, d(sc["opacity"]), d(sc["scaling"]), d(sc["rotation"]), 1.0, e,
-        d(cam.world_view_transform), d(cam.full_proj_transform), case["tfx"], case["tfy"], 512, 512, d(sc["features"]), 3,
+        d(cam.world_view_transform), d(cam.full_proj_transform), case["tfx"], case["tfy"], H, W, d(sc["features"]), 3,
         d(cam.camera_center), False, False)
-    st = hip_state(20000, R, 512, 512, geom, binning, img)
+    st = hip_state(P, R, W, H, geom, binning, img)
     assert R == r["num_rendered"]
     assert torch.equal(radii, r["radii"])
     assert np.array_equal(st["keys"], _np(r["keys"]).view(np.uint64))

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """CPU only: the figures behind the bars of tests/pose_helpers.py (the camera gradient), none of them from the kernel.
-    python tools/pose_bars.py [case ...]
+    python tools/pose_bars.py [--camera NAME] [case ...]
+--camera NAME: under the general camera NAME of tests/camera_cases.py (unequal focal lengths, roll, off-centre axis), on the
+rows of camera_cases.POSE_PAIRS for it with their seeds, and the identity on identity_case(camera=NAME).
 Per case of pose_helpers.POSE_CASES, with the float32 oracle (oracle/cpu.py) and float64 autograd (oracle/torch_ref.py):
   * flipped pixels between the float32 oracle's forward and float64, Gaussians on the cone edge (the conditions);
   * dL/dcampos: the oracle-difference reference (dL_dmeans3D with SHs minus the same with colors_precomp = the forward's
@@ -9,6 +11,7 @@ Per case of pose_helpers.POSE_CASES, with the float32 oracle (oracle/cpu.py) and
     float64, relative to the largest entry.
 Then the translation identity on pose_helpers.identity_case(): float64 against itself (the CPU self-check's 1e-12) and the
 float32 oracle's - sum dL/dmu against float64's c.grad, relative to sum |dL/dmu| -> IDENTITY_ORACLE_RATIO."""
+import argparse
 import os
 import sys
 
@@ -44,12 +47,23 @@ def main():
     from oracle import cpu
     from oracle.torch_ref import render_f64
 
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--camera", default=None, help="a name of tests/camera_cases.py CAMERAS")
+    ap.add_argument("cases", nargs="*")
+    args = ap.parse_args()
     cpu.build()
-    names = sys.argv[1:] or PH.POSE_CASES
+    camera = args.camera
+    if camera is None:
+        rows = [(name, None) for name in (args.cases or PH.POSE_CASES)]
+    else:
+        import camera_cases as CC
+
+        rows = [(name, seed) for cam, name, seed in CC.POSE_PAIRS if cam == camera and (not args.cases or name in args.cases)]
+        print(f"camera {camera}: (roll deg, fx / fy, cx, cy) = {CC.CAMERAS[camera]}")
     worst = 0.0
-    print(f"{'case':18s} {'flips':>5s} {'edge':>4s} {'campos ref':>11s} {'proj ref':>9s} {'|sum dm| / sum |dm|':>20s}")
-    for name in names:
-        r = PH.pose_regime(name)
+    print(f"{'case':18s} {'seed':>5s} {'flips':>5s} {'edge':>4s} {'campos ref':>11s} {'proj ref':>9s} {'|sum dm| / sum |dm|':>20s}")
+    for name, seed in rows:
+        r = PH.pose_regime(name, camera=camera, seed=seed)
         f, g = R.oracle_run(cpu, r)
         want_cam, _, stats = PH.f64_pose(f, r)
         flips = flipped_pixels(stats["n_contrib"].numpy(), stats["final_T"].numpy(), f["n_contrib"], f["final_T"]).size
@@ -68,11 +82,11 @@ def main():
             e_cam = float(np.abs(ref - want_cam["campos"]).max() / np.abs(want_cam["campos"]).max())
             cancel = float((np.abs(dm.sum(axis=0)) / np.abs(dm).sum(axis=0)).min())
             worst = max(worst, e_cam)
-        print(f"{name:18s} {flips:5d} {edge:4d} {e_cam:11.2e} {e_proj:9.2e} {cancel:20.3f}", flush=True)
+        print(f"{name:18s} {'own' if seed is None else seed:>5} {flips:5d} {edge:4d} {e_cam:11.2e} {e_proj:9.2e} {cancel:20.3f}", flush=True)
     print(f"CAMPOS_ORACLE_WORST = {worst:.2e}")
 
     # the translation identity
-    case = PH.identity_case()
+    case = PH.identity_case(camera=camera)
     H, W = case["H"], case["W"]
     G = PH.seed_gradient(H, W, 19) * H * W
     f = oracle_forward(cpu, case)
