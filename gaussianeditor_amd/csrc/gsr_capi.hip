@@ -422,6 +422,10 @@ int preprocess_args_ok(int P, int D, int M, const float* means3D, const float* s
 
 // First half of gsr_preprocess: K1 and the two depth-sort passes that never depend on the key range; the
 // first of them publishes the counts into `slot` behind generation `*seq`.
+// The focal length in pixels of an image side (rasterizer_impl.cu:190-191, 308-309): one statement for K1's focal_x / focal_y and
+// for the h_x / h_y of K8+K9 and the camera gradient, which must be the same floats.
+static inline float focal_length(int pixels, float tan_half_fov) { return pixels / (2.0f * tan_half_fov); }
+
 int preprocess_begin_impl(hipStream_t s, int P, int D, int M, const float* means3D, const float* scales, float scale_modifier,
                           const float* rotations, const float* opacities, const float* shs, const float* cov3D_precomp,
                           const float* colors_precomp, const float* viewmatrix, const float* projmatrix, const float* campos,
@@ -433,8 +437,8 @@ int preprocess_begin_impl(hipStream_t s, int P, int D, int M, const float* means
   a.opacities = opacities; a.shs = shs; a.cov3D_precomp = cov3D_precomp; a.colors_precomp = colors_precomp;
   a.viewmatrix = viewmatrix; a.projmatrix = projmatrix; a.campos = campos;
   a.W = W; a.H = H; a.tan_fovx = tan_fovx; a.tan_fovy = tan_fovy;
-  a.focal_y = H / (2.0f * tan_fovy);  // rasterizer_impl.cu:190-191
-  a.focal_x = W / (2.0f * tan_fovx);
+  a.focal_y = focal_length(H, tan_fovy);
+  a.focal_x = focal_length(W, tan_fovx);
   a.gx = (W + TILE - 1) / TILE; a.gy = (H + TILE - 1) / TILE;
   a.skip_color = skip_color;
   a.forward_only = (flags & GSR_FLAG_FORWARD_ONLY) ? 1 : 0;
@@ -717,8 +721,8 @@ int gsr_pose_backward(void* stream, int P, int D, int M, int W, int H, const flo
   pa.scales = cov3D_precomp ? nullptr : scales; pa.rotations = cov3D_precomp ? nullptr : rotations;
   pa.cov3D_precomp = cov3D_precomp;
   pa.viewmatrix = viewmatrix; pa.projmatrix = projmatrix; pa.campos = campos;
-  pa.h_y = H / (2.0f * tan_fovy);  // (as preprocess_backward_impl)
-  pa.h_x = W / (2.0f * tan_fovx);
+  pa.h_y = focal_length(H, tan_fovy);
+  pa.h_x = focal_length(W, tan_fovx);
   pa.tan_fovx = tan_fovx; pa.tan_fovy = tan_fovy;
   pa.acc = acc;
   pa.clamped = g.clamped;
@@ -831,8 +835,8 @@ static int preprocess_backward_impl(void* stream, int P, int D, int M, int W, in
   pa.clamped = g.clamped;
   for (int i = 0; i < 3; ++i) pa.dcol[i] = g.dcol[i];
   pa.viewmatrix = viewmatrix; pa.projmatrix = projmatrix; pa.campos = campos;
-  pa.h_y = H / (2.0f * tan_fovy);  // rasterizer_impl.cu:308-309
-  pa.h_x = W / (2.0f * tan_fovx);
+  pa.h_y = focal_length(H, tan_fovy);
+  pa.h_x = focal_length(W, tan_fovx);
   pa.tan_fovx = tan_fovx; pa.tan_fovy = tan_fovy;
   pa.acc = acc; pa.dL_dmean2D = dL_dmeans2D; pa.dL_dopacity = dL_dopacity; pa.dL_dcolor = dL_dcolors;
   pa.dL_dmeans3D = dL_dmeans3D; pa.dL_dcov3D = dL_dcov3D;

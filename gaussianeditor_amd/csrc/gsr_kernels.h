@@ -328,6 +328,145 @@ __device__ __forceinline__ void cov3d_from_values(float s0, float s1, float s2, 
   c3[0] = Sigma.m[0][0]; c3[1] = Sigma.m[0][1]; c3[2] = Sigma.m[0][2];
   c3[3] = Sigma.m[1][1]; c3[4] = Sigma.m[1][2]; c3[5] = Sigma.m[2][2];
 }
+
+// ---- The projection chain, one definition per piece: K1 evaluates it, K8+K9 and the camera gradient evaluate it again and
+// differentiate it, and all three must arrive at the same bits.  (Which kernel calls what, and the forms that keep every
+// kernel's code what it was: DESIGN.md, profiles/gaussian_chain_shared_isa.md.)
+// transformPoint4x3, auxiliary.h:58-66: the view-space mean
+__device__ __forceinline__ V3 view_point(const float* view, V3 p) {
+  return {view[0] * p.x + view[4] * p.y + view[8] * p.z + view[12], view[1] * p.x + view[5] * p.y + view[9] * p.z + view[13],
+          view[2] * p.x + view[6] * p.y + view[10] * p.z + view[14]};
+}
+// backward.cu:370-377: what the gradient of ndc = p_hom.xy / (p_hom.w + 1e-7) needs of the homogeneous position
+struct HomTerms { float m_w, mul1, mul2; };
+__device__ __forceinline__ HomTerms hom_backward_terms(const float* proj, V3 m) {
+  const float m_hw = proj[3] * m.x + proj[7] * m.y + proj[11] * m.z + proj[15];
+  const float m_w = 1.0f / (m_hw + 0.0000001f);
+  const float mul1 = (proj[0] * m.x + proj[4] * m.y + proj[8] * m.z + proj[12]) * m_w * m_w;
+  const float mul2 = (proj[1] * m.x + proj[5] * m.y + proj[9] * m.z + proj[13]) * m_w * m_w;
+  return {m_w, mul1, mul2};
+}
+// computeCov2D, forward.cu:74-113 / backward.cu:159-190: t = the view-space mean clamped to the 1.3x cone (x_grad_mul,
+// y_grad_mul: 0 where the clamp is active), T = W J, cov = the UNDILATED 2D covariance (entries [0][0], [0][1], [1][1]).
+struct Cov2D { V3 t; float x_grad_mul, y_grad_mul; M3 J, W, Vrk, T, cov; };
+__device__ __forceinline__ Cov2D cov2d_chain(V3 t, const float* view, const float (&c3)[6], float tan_fovx, float tan_fovy,
+                                             float focal_x, float focal_y) {
+  Cov2D c;
+  const float limx = 1.3f * tan_fovx, limy = 1.3f * tan_fovy;
+  const float txtz = t.x / t.z, tytz = t.y / t.z;
+  t.x = fminf(limx, fmaxf(-limx, txtz)) * t.z;
+  t.y = fminf(limy, fmaxf(-limy, tytz)) * t.z;
+  c.t = t;
+  c.x_grad_mul = txtz < -limx || txtz > limx ? 0.f : 1.f;
+  c.y_grad_mul = tytz < -limy || tytz > limy ? 0.f : 1.f;
+  c.J = mk(focal_x / t.z, 0.0f, -(focal_x * t.x) / (t.z * t.z), 0.0f, focal_y / t.z, -(focal_y * t.y) / (t.z * t.z), 0, 0, 0);
+  c.W = mk(view[0], view[4], view[8], view[1], view[5], view[9], view[2], view[6], view[10]);
+  c.Vrk = mk(c3[0], c3[1], c3[2], c3[1], c3[3], c3[4], c3[2], c3[4], c3[5]);
+  c.T = mul(c.W, c.J);
+  c.cov = mul(mul(tr(c.T), tr(c.Vrk)), c.T);
+  return c;
+}
+// Anti-aliasing: r = det(Sigma) / det(Sigma + 0.3 I) from the undilated covariance and the dilated determinant, and the
+// opacity factor h; the floor also covers a det(Sigma) that rounds to <= 0 (on it h is a constant: no r-term in the backward)
+constexpr float AA_R_FLOOR = 2.5e-5f;
+__device__ __forceinline__ float aa_ratio(M3 cov, float det) {
+  return (cov.m[0][0] * cov.m[1][1] - cov.m[0][1] * cov.m[0][1]) * (1.f / det);
+}
+__device__ __forceinline__ float aa_factor(float r) { return sqrtf(fmaxf(AA_R_FLOOR, r)); }
+
+// backward.cu:192-226: the conic's gradient -> dL/d(a, b, c) of the dilated covariance (a b; b c), and through
+// cov = T^T Vrk T to dL/dcov3D (dcov: its six entries, left as they are where the reference's denom2inv is zero).
+// aa: plus the r-term of the opacity factor, g_opacity = dL/d(o h) and aa_ow = o h (K8+K9's header); aa_h = h as K1 computed it.
+struct Cov2DGrad { float da, db, dc, aa_r, aa_h; };
+__device__ __forceinline__ Cov2DGrad cov2d_backward(const M3& cov2D, const M3& T, V3 dL_dcon, bool aa, float g_opacity, float aa_ow,
+                                                    float (&dcov)[6]) {
+  const float ca = cov2D.m[0][0] + 0.3f, cb = cov2D.m[0][1], cc = cov2D.m[1][1] + 0.3f;
+  const float denom = ca * cc - cb * cb;
+  const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
+  Cov2DGrad g = {0, 0, 0};
+  g.aa_r = aa ? aa_ratio(cov2D, denom) : 0.f;
+  g.aa_h = aa ? aa_factor(g.aa_r) : 1.f;
+  if (denom2inv != 0) {
+    g.da = denom2inv * (-cc * cc * dL_dcon.x + 2 * cb * cc * dL_dcon.y + (denom - ca * cc) * dL_dcon.z);
+    g.dc = denom2inv * (-ca * ca * dL_dcon.z + 2 * ca * cb * dL_dcon.y + (denom - ca * cc) * dL_dcon.x);
+    g.db = denom2inv * 2 * (cb * cc * dL_dcon.x - (denom + 2 * cb * cb) * dL_dcon.y + ca * cb * dL_dcon.z);
+    if (aa) {
+      const float aa_r = g.aa_r;
+      if (aa_r > AA_R_FLOOR) {
+        const float x = cov2D.m[0][0], y = cov2D.m[1][1], z = cb, w = 0.3f;
+        const float dL_dr = g_opacity * aa_ow / (2.f * aa_r);
+        const float s = dL_dr * w / (denom * denom);
+        g.da += s * (y * y + w * y + z * z);
+        g.dc += s * (x * x + w * x + z * z);
+        g.db += s * (-2.f * z * (x + y + w));
+      }
+    }
+    const auto& Tm = T.m;
+    dcov[0] = (Tm[0][0] * Tm[0][0] * g.da + Tm[0][0] * Tm[1][0] * g.db + Tm[1][0] * Tm[1][0] * g.dc);
+    dcov[3] = (Tm[0][1] * Tm[0][1] * g.da + Tm[0][1] * Tm[1][1] * g.db + Tm[1][1] * Tm[1][1] * g.dc);
+    dcov[5] = (Tm[0][2] * Tm[0][2] * g.da + Tm[0][2] * Tm[1][2] * g.db + Tm[1][2] * Tm[1][2] * g.dc);
+    dcov[1] = 2 * Tm[0][0] * Tm[0][1] * g.da + (Tm[0][0] * Tm[1][1] + Tm[0][1] * Tm[1][0]) * g.db + 2 * Tm[1][0] * Tm[1][1] * g.dc;
+    dcov[2] = 2 * Tm[0][0] * Tm[0][2] * g.da + (Tm[0][0] * Tm[1][2] + Tm[0][2] * Tm[1][0]) * g.db + 2 * Tm[1][0] * Tm[1][2] * g.dc;
+    dcov[4] = 2 * Tm[0][2] * Tm[0][1] * g.da + (Tm[0][1] * Tm[1][2] + Tm[0][2] * Tm[1][1]) * g.db + 2 * Tm[1][1] * Tm[1][2] * g.dc;
+  }
+  return g;
+}
+// backward.cu:247-270: dL/dT (dT0[r] = dL/dT[0][r], dT1 likewise) through T = W J to dL/dJ, dL/dt (off the cone t.xy are constants)
+__device__ __forceinline__ V3 chain_dt(Cov2D c, const float (&dT0)[3], const float (&dT1)[3], float h_x, float h_y) {
+  const auto& Wx = c.W.m;
+  const float dL_dJ00 = Wx[0][0] * dT0[0] + Wx[0][1] * dT0[1] + Wx[0][2] * dT0[2];
+  const float dL_dJ02 = Wx[2][0] * dT0[0] + Wx[2][1] * dT0[1] + Wx[2][2] * dT0[2];
+  const float dL_dJ11 = Wx[1][0] * dT1[0] + Wx[1][1] * dT1[1] + Wx[1][2] * dT1[2];
+  const float dL_dJ12 = Wx[2][0] * dT1[0] + Wx[2][1] * dT1[1] + Wx[2][2] * dT1[2];
+  const float tz = 1.f / c.t.z, tz2 = tz * tz, tz3 = tz2 * tz;
+  return {c.x_grad_mul * -h_x * tz2 * dL_dJ02, c.y_grad_mul * -h_y * tz2 * dL_dJ12,
+          -h_x * tz2 * dL_dJ00 - h_y * tz2 * dL_dJ11 + (2 * h_x * c.t.x) * tz3 * dL_dJ02 + (2 * h_y * c.t.y) * tz3 * dL_dJ12};
+}
+// backward.cu:228-270: dL/dT (its two non-zero rows) and dL/dt of one Gaussian
+struct ChainGrad { float dT0[3], dT1[3]; V3 dt; };  // dL/dT[0][r], dL/dT[1][r]; dL/dt
+__device__ __forceinline__ ChainGrad chain_backward(Cov2D c, Cov2DGrad g, float h_x, float h_y) {
+  ChainGrad o;
+  const auto& Tm = c.T.m;
+  const auto& V = c.Vrk.m;
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+    o.dT0[r] = 2 * (Tm[0][0] * V[r][0] + Tm[0][1] * V[r][1] + Tm[0][2] * V[r][2]) * g.da +
+               (Tm[1][0] * V[r][0] + Tm[1][1] * V[r][1] + Tm[1][2] * V[r][2]) * g.db;
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+    o.dT1[r] = 2 * (Tm[1][0] * V[r][0] + Tm[1][1] * V[r][1] + Tm[1][2] * V[r][2]) * g.dc +
+               (Tm[0][0] * V[r][0] + Tm[0][1] * V[r][1] + Tm[0][2] * V[r][2]) * g.db;
+  o.dt = chain_dt(c, o.dT0, o.dT1, h_x, h_y);
+  return o;
+}
+// dnormvdv, auxiliary.h:107-117: the gradient dv of v / |v| taken back to v
+__device__ __forceinline__ V3 dnormvdv(V3 v, V3 dv) {
+  const float sum2 = v.x * v.x + v.y * v.y + v.z * v.z;
+  const float invsum32 = 1.0f / sqrtf(sum2 * sum2 * sum2);
+  return {((+sum2 - v.x * v.x) * dv.x - v.y * v.x * dv.y - v.z * v.x * dv.z) * invsum32,
+          (-v.x * v.y * dv.x + (sum2 - v.y * v.y) * dv.y - v.z * v.y * dv.z) * invsum32,
+          (-v.x * v.z * dv.x - v.y * v.z * dv.y + (sum2 - v.z * v.z) * dv.z) * invsum32};
+}
+// dL_dRGB with the channels K1 clamped at zero taken out (Geom::clamped, backward.cu:35-38)
+__device__ __forceinline__ V3 unclamped_rgb_grad(V3 dL_dRGB, uint8_t cl) {
+  dL_dRGB.x *= (cl & 1) ? 0.f : 1.f;
+  dL_dRGB.y *= (cl & 2) ? 0.f : 1.f;
+  dL_dRGB.z *= (cl & 4) ? 0.f : 1.f;
+  return dL_dRGB;
+}
+// v / |v|: the direction the SH basis is evaluated in (forward.cu:28-29)
+__device__ __forceinline__ V3 unit_dir(V3 v) {
+  const float len = sqrtf(v.x * v.x + v.y * v.y + v.z * v.z);
+  return {v.x / len, v.y / len, v.z / len};
+}
+// The real SH basis of computeColorFromSH (forward.cu:20-71, backward.cu:20-139).
+constexpr float SH_C0 = 0.28209479177387814f;
+constexpr float SH_C1 = 0.4886025119029199f;
+__device__ constexpr float SH_C2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f,
+                                       -1.0925484305920792f, 0.5462742152960396f};
+__device__ constexpr float SH_C3[7] = {-0.5900435899266435f, 2.890611442640554f,  -0.4570457994644658f,
+                                       0.3731763325901154f,  -0.4570457994644658f, 1.445305721320277f,
+                                       -0.5900435899266435f};
 #endif  // __HIPCC__
 
 }  // namespace gsr

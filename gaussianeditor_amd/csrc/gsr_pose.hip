@@ -9,9 +9,7 @@
 //   dir = mu - campos        dC        -= dm (the dnormvdv term K9 adds to dL_dmeans3D)
 // Column 3 of the view matrix and column 2 of the projection matrix enter nothing the rasterizer computes: exact zeros.
 // The conventions are those of K8+K9 (the reference's analytic backward): off-cone tx / ty are constants (x_grad_mul,
-// y_grad_mul), the alpha clamp is straight-through, under AA the factor h is differentiated through the covariance.  The
-// cov2D chain is RESTATED here, operation for operation, rather than shared with preprocess_backward_kernel: that kernel's
-// instantiations stay the code they are, and this path costs a second read of the row and the inputs only where it is asked for.
+// y_grad_mul), the alpha clamp is straight-through, under AA the factor h is differentiated through the covariance.
 //
 // 27 sums over the Gaussians (12 + 12 + 3).  No float atomics: a thread adds its Gaussians in ascending index order, a wave
 // reduces with DPP moves, the four waves of a block meet in LDS, every block stores one row of partial sums, and one
@@ -61,22 +59,10 @@ __global__ void __launch_bounds__(GAUSS_BLOCK) pose_backward_kernel(const PoseAr
     const float g2x = acc_m2d.x, g2y = acc_m2d.y;
     const V3 dL_dcon = {acc_con.x, acc_con.y, acc_con.w};
 
-    // ---- the cov2D chain of preprocess_backward_kernel, restated ----
-    V3 t = {view[0] * mean.x + view[4] * mean.y + view[8] * mean.z + view[12],
-            view[1] * mean.x + view[5] * mean.y + view[9] * mean.z + view[13],
-            view[2] * mean.x + view[6] * mean.y + view[10] * mean.z + view[14]};
-    const float limx = 1.3f * a.tan_fovx, limy = 1.3f * a.tan_fovy;
-    const float txtz = t.x / t.z, tytz = t.y / t.z;
-    t.x = fminf(limx, fmaxf(-limx, txtz)) * t.z;
-    t.y = fminf(limy, fmaxf(-limy, tytz)) * t.z;
-    const float x_grad_mul = txtz < -limx || txtz > limx ? 0.f : 1.f;
-    const float y_grad_mul = tytz < -limy || tytz > limy ? 0.f : 1.f;
-    const float h_x = a.h_x, h_y = a.h_y;
-    const M3 J = mk(h_x / t.z, 0.0f, -(h_x * t.x) / (t.z * t.z), 0.0f, h_y / t.z, -(h_y * t.y) / (t.z * t.z), 0, 0, 0);
-    const M3 Wm = mk(view[0], view[4], view[8], view[1], view[5], view[9], view[2], view[6], view[10]);
-    const M3 Vrk = mk(c3[0], c3[1], c3[2], c3[1], c3[3], c3[4], c3[2], c3[4], c3[5]);
-    const M3 T = mul(Wm, J);
-    const M3 cov2D = mul(mul(tr(T), tr(Vrk)), T);
+    const Cov2D ch = cov2d_chain(view_point(view, mean), view, c3, a.tan_fovx, a.tan_fovy, a.h_x, a.h_y);
+    const M3 J = ch.J, cov2D = ch.cov;
+    // (the conic's backward and the dL_dT rows stay written out: cov2d_backward and chain_backward, the statements of K8+K9,
+    //  order r before h and the rows differently, and this kernel's code follows the order -- profiles/gaussian_chain_shared_isa.md)
     const float ca = cov2D.m[0][0] + 0.3f, cb = cov2D.m[0][1], cc = cov2D.m[1][1] + 0.3f;
     const float denom = ca * cc - cb * cb;
     float dL_da = 0, dL_db = 0, dL_dc = 0;
@@ -86,8 +72,8 @@ __global__ void __launch_bounds__(GAUSS_BLOCK) pose_backward_kernel(const PoseAr
       dL_dc = denom2inv * (-ca * ca * dL_dcon.z + 2 * ca * cb * dL_dcon.y + (denom - ca * cc) * dL_dcon.x);
       dL_db = denom2inv * 2 * (cb * cc * dL_dcon.x - (denom + 2 * cb * cb) * dL_dcon.y + ca * cb * dL_dcon.z);
       if (AA) {  // r as K1 and K8+K9 compute it; on the floor h is a constant: no r-term
-        const float aa_r = (cov2D.m[0][0] * cov2D.m[1][1] - cb * cb) * (1.f / denom);
-        if (aa_r > 2.5e-5f) {
+        const float aa_r = aa_ratio(cov2D, denom);
+        if (aa_r > AA_R_FLOOR) {
           const float x = cov2D.m[0][0], y = cov2D.m[1][1], z = cb, w = 0.3f;
           const float dL_dr = acc_m2d.w * aa_ow / (2.f * aa_r);
           const float sc = dL_dr * w / (denom * denom);
@@ -97,8 +83,8 @@ __global__ void __launch_bounds__(GAUSS_BLOCK) pose_backward_kernel(const PoseAr
         }
       }
     }
-    const auto& Tm = T.m;
-    const auto& V = Vrk.m;
+    const auto& Tm = ch.T.m;
+    const auto& V = ch.Vrk.m;
     float dT0[3], dT1[3];  // dL/dT[0][r], dL/dT[1][r]: dL_dT00 .. dL_dT12 of K8
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
@@ -107,16 +93,8 @@ __global__ void __launch_bounds__(GAUSS_BLOCK) pose_backward_kernel(const PoseAr
       dT0[r] = 2 * u0 * dL_da + u1 * dL_db;
       dT1[r] = 2 * u1 * dL_dc + u0 * dL_db;
     }
-    const auto& Wx = Wm.m;
-    const float dL_dJ00 = Wx[0][0] * dT0[0] + Wx[0][1] * dT0[1] + Wx[0][2] * dT0[2];
-    const float dL_dJ02 = Wx[2][0] * dT0[0] + Wx[2][1] * dT0[1] + Wx[2][2] * dT0[2];
-    const float dL_dJ11 = Wx[1][0] * dT1[0] + Wx[1][1] * dT1[1] + Wx[1][2] * dT1[2];
-    const float dL_dJ12 = Wx[2][0] * dT1[0] + Wx[2][1] * dT1[1] + Wx[2][2] * dT1[2];
-    const float tz = 1.f / t.z, tz2 = tz * tz, tz3 = tz2 * tz;
-    float dt[3];
-    dt[0] = x_grad_mul * -h_x * tz2 * dL_dJ02;
-    dt[1] = y_grad_mul * -h_y * tz2 * dL_dJ12;
-    dt[2] = -h_x * tz2 * dL_dJ00 - h_y * tz2 * dL_dJ11 + (2 * h_x * t.x) * tz3 * dL_dJ02 + (2 * h_y * t.y) * tz3 * dL_dJ12;
+    const V3 dL_dt = chain_dt(ch, dT0, dT1, a.h_x, a.h_y);
+    float dt[3] = {dL_dt.x, dL_dt.y, dL_dt.z};
     if (DEPTH) dt[2] += acc_col.w;  // the depth image's share: d = t.z
     const float mu[4] = {mean.x, mean.y, mean.z, 1.f};
     // t = (mu, 1) V
@@ -132,10 +110,8 @@ __global__ void __launch_bounds__(GAUSS_BLOCK) pose_backward_kernel(const PoseAr
       s[r * 3 + 2] += dT0[r] * J.m[0][2] + dT1[r] * J.m[1][2];
     }
     // p_hom = (mu, 1) PV, ndc = p_hom.xy / (p_hom.w + 1e-7)
-    const float m_hw = proj[3] * mean.x + proj[7] * mean.y + proj[11] * mean.z + proj[15];
-    const float m_w = 1.0f / (m_hw + 0.0000001f);
-    const float mul1 = (proj[0] * mean.x + proj[4] * mean.y + proj[8] * mean.z + proj[12]) * m_w * m_w;
-    const float mul2 = (proj[1] * mean.x + proj[5] * mean.y + proj[9] * mean.z + proj[13]) * m_w * m_w;
+    const HomTerms hm = hom_backward_terms(proj, mean);
+    const float m_w = hm.m_w, mul1 = hm.mul1, mul2 = hm.mul2;
     const float dp[3] = {g2x * m_w, g2y * m_w, -(mul1 * g2x + mul2 * g2y)};  // columns 0, 1, 3
 #pragma unroll
     for (int c = 0; c < 4; ++c)
@@ -147,13 +123,10 @@ __global__ void __launch_bounds__(GAUSS_BLOCK) pose_backward_kernel(const PoseAr
       const V3 dRGBdy = *reinterpret_cast<const V3*>(a.dcol[1] + 3 * idx);
       const V3 dRGBdz = *reinterpret_cast<const V3*>(a.dcol[2] + 3 * idx);
       const uint8_t cl = a.clamped[idx];
-      V3 dL_dRGB = {acc_col.x, acc_col.y, acc_col.z};
-      dL_dRGB.x *= (cl & 1) ? 0.f : 1.f;
-      dL_dRGB.y *= (cl & 2) ? 0.f : 1.f;
-      dL_dRGB.z *= (cl & 4) ? 0.f : 1.f;
+      const V3 dL_dRGB = unclamped_rgb_grad(V3{acc_col.x, acc_col.y, acc_col.z}, cl);
       const V3 v = {mean.x - cam.campos[0], mean.y - cam.campos[1], mean.z - cam.campos[2]};
       const V3 dv = {dot3(dRGBdx, dL_dRGB), dot3(dRGBdy, dL_dRGB), dot3(dRGBdz, dL_dRGB)};
-      // dnormvdv, as K9
+      // dnormvdv, written out: each component is subtracted as soon as it is there, and the code follows that order
       const float sum2 = v.x * v.x + v.y * v.y + v.z * v.z;
       const float invsum32 = 1.0f / sqrtf(sum2 * sum2 * sum2);
       s[24] -= ((+sum2 - v.x * v.x) * dv.x - v.y * v.x * dv.y - v.z * v.x * dv.z) * invsum32;

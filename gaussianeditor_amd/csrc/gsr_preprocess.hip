@@ -27,14 +27,6 @@ __device__ __forceinline__ void get_rect(float px, float py, int max_radius, int
   maxy = (uint32_t)min(gy, max(0, f2i_sat((py + r + (float)TILE - 1.0f) / (float)TILE)));
 }
 
-constexpr float SH_C0 = 0.28209479177387814f;
-constexpr float SH_C1 = 0.4886025119029199f;
-__device__ constexpr float SH_C2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f,
-                                       -1.0925484305920792f, 0.5462742152960396f};
-__device__ constexpr float SH_C3[7] = {-0.5900435899266435f, 2.890611442640554f,  -0.4570457994644658f,
-                                       0.3731763325901154f,  -0.4570457994644658f, 1.445305721320277f,
-                                       -0.5900435899266435f};
-
 // Loads the SH coefficients of one Gaussian into registers.  M == 16 (the standard 3DGS ply) is a
 // 192-byte, 16-byte-aligned record read with dwordx4 loads.  All loads of a degree are issued
 // UNCONDITIONALLY back to back (the switch is on the wave-uniform active degree): a per-load guard
@@ -180,9 +172,7 @@ __global__ void __launch_bounds__(GAUSS_BLOCK) __attribute__((amdgpu_waves_per_e
     do {
       p = {a.means3D[3 * idx], a.means3D[3 * idx + 1], a.means3D[3 * idx + 2]};
       // in_frustum, auxiliary.h:139-164: only the near test survives
-      const V3 p_view = {view[0] * p.x + view[4] * p.y + view[8] * p.z + view[12],
-                         view[1] * p.x + view[5] * p.y + view[9] * p.z + view[13],
-                         view[2] * p.x + view[6] * p.y + view[10] * p.z + view[14]};
+      const V3 p_view = view_point(view, p);
       if (p_view.z <= 0.2f) break;
       const float hx = proj[0] * p.x + proj[4] * p.y + proj[8] * p.z + proj[12];
       const float hy = proj[1] * p.x + proj[5] * p.y + proj[9] * p.z + proj[13];
@@ -226,8 +216,7 @@ __global__ void __launch_bounds__(GAUSS_BLOCK) __attribute__((amdgpu_waves_per_e
       if (det == 0.0f) break;
       const float det_inv = 1.f / det;
       if (AA) {  // r = det(Sigma) / det(Sigma + 0.3 I); the floor also covers a det(Sigma) that rounds to <= 0
-        const float r = (cov.m[0][0] * cov.m[1][1] - cy * cy) * det_inv;
-        aa_h = sqrtf(fmaxf(2.5e-5f, r));
+        aa_h = aa_factor(aa_ratio(cov, det));
       }
       conx = cz * det_inv;
       cony = -cy * det_inv;
@@ -303,9 +292,7 @@ __global__ void __launch_bounds__(GAUSS_BLOCK) __attribute__((amdgpu_waves_per_e
           col.y = colors_precomp[3 * (size_t)idx + 1];
           col.z = colors_precomp[3 * (size_t)idx + 2];
         } else {
-          V3 dir = {p.x - cam.campos[0], p.y - cam.campos[1], p.z - cam.campos[2]};
-          const float len = sqrtf(dir.x * dir.x + dir.y * dir.y + dir.z * dir.z);
-          dir = {dir.x / len, dir.y / len, dir.z / len};
+          const V3 dir = unit_dir(V3{p.x - cam.campos[0], p.y - cam.campos[1], p.z - cam.campos[2]});
           if (!sh_loaded) load_sh(a.shs, (size_t)idx, M, D, sh);
           V3 result = SH_C0 * sh[0];
           if (D > 0) {
@@ -476,6 +463,34 @@ __device__ __forceinline__ void sh_tile_store_rows(float* __restrict__ dst_rows,
   __builtin_amdgcn_wave_barrier();
 }
 
+// One view's SH-gradient terms of a Gaussian: t[k] = c_k(dir) * dL_dRGB for the coefficients of degree <= D, zero above.
+__device__ __forceinline__ void sh_grad_terms(int D, V3 dir, V3 dL_dRGB, V3* t) {
+  const float x = dir.x, y = dir.y, z = dir.z;
+  t[0] = SH_C0 * dL_dRGB;
+  if (D > 0) {
+    t[1] = (-SH_C1 * y) * dL_dRGB;
+    t[2] = (SH_C1 * z) * dL_dRGB;
+    t[3] = (-SH_C1 * x) * dL_dRGB;
+    if (D > 1) {
+      const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
+      t[4] = (SH_C2[0] * xy) * dL_dRGB;
+      t[5] = (SH_C2[1] * yz) * dL_dRGB;
+      t[6] = (SH_C2[2] * (2.f * zz - xx - yy)) * dL_dRGB;
+      t[7] = (SH_C2[3] * xz) * dL_dRGB;
+      t[8] = (SH_C2[4] * (xx - yy)) * dL_dRGB;
+      if (D > 2) {
+        t[9] = (SH_C3[0] * y * (3.f * xx - yy)) * dL_dRGB;
+        t[10] = (SH_C3[1] * xy * z) * dL_dRGB;
+        t[11] = (SH_C3[2] * y * (4.f * zz - xx - yy)) * dL_dRGB;
+        t[12] = (SH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy)) * dL_dRGB;
+        t[13] = (SH_C3[4] * x * (4.f * zz - xx - yy)) * dL_dRGB;
+        t[14] = (SH_C3[5] * z * (xx - yy)) * dL_dRGB;
+        t[15] = (SH_C3[6] * x * (xx - 3.f * yy)) * dL_dRGB;
+      }
+    }
+  }
+}
+
 // (Three waves per SIMD: the 52 KB of store tiles per workgroup allow three workgroups per CU, ~140 VGPRs.)
 // ROWS (PreBwdArgs::row_state, gsr_preprocess_backward_rows): the gradient arrays belong to the caller ACROSS calls.  Nine
 // Gaussians of ten get all-zero gradients from a view (culled, or no pixel blended them); their rows are rewritten only if
@@ -580,87 +595,19 @@ preprocess_backward_kernel(const PreBwdArgs a) {
                  (DEPTH && acc_col.w != 0.f);
 
     // ---- computeCov2DCUDA, backward.cu:159-273 ----
-    V3 t = {view[0] * mean.x + view[4] * mean.y + view[8] * mean.z + view[12],
-            view[1] * mean.x + view[5] * mean.y + view[9] * mean.z + view[13],
-            view[2] * mean.x + view[6] * mean.y + view[10] * mean.z + view[14]};
-    const float limx = 1.3f * a.tan_fovx, limy = 1.3f * a.tan_fovy;
-    const float txtz = t.x / t.z, tytz = t.y / t.z;
-    t.x = fminf(limx, fmaxf(-limx, txtz)) * t.z;
-    t.y = fminf(limy, fmaxf(-limy, tytz)) * t.z;
-    const float x_grad_mul = txtz < -limx || txtz > limx ? 0.f : 1.f;
-    const float y_grad_mul = tytz < -limy || tytz > limy ? 0.f : 1.f;
-    const float h_x = a.h_x, h_y = a.h_y;
-    const M3 J = mk(h_x / t.z, 0.0f, -(h_x * t.x) / (t.z * t.z), 0.0f, h_y / t.z, -(h_y * t.y) / (t.z * t.z), 0, 0, 0);
-    const M3 Wm = mk(view[0], view[4], view[8], view[1], view[5], view[9], view[2], view[6], view[10]);
-    const M3 Vrk = mk(c3[0], c3[1], c3[2], c3[1], c3[3], c3[4], c3[2], c3[4], c3[5]);
-    const M3 T = mul(Wm, J);
-    const M3 cov2D = mul(mul(tr(T), tr(Vrk)), T);
-    const float ca = cov2D.m[0][0] + 0.3f, cb = cov2D.m[0][1], cc = cov2D.m[1][1] + 0.3f;
-    const float denom = ca * cc - cb * cb;
-    float dL_da = 0, dL_db = 0, dL_dc = 0;
-    const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
-    const auto& Tm = T.m;
-    float aa_r = 0.f;
-    if (AA) {  // r and h exactly as K1 computed them (same operations on the same covariance)
-      aa_r = (cov2D.m[0][0] * cov2D.m[1][1] - cb * cb) * (1.f / denom);
-      aa_h = sqrtf(fmaxf(2.5e-5f, aa_r));
-    }
-    if (denom2inv != 0) {
-      dL_da = denom2inv * (-cc * cc * dL_dcon.x + 2 * cb * cc * dL_dcon.y + (denom - ca * cc) * dL_dcon.z);
-      dL_dc = denom2inv * (-ca * ca * dL_dcon.z + 2 * ca * cb * dL_dcon.y + (denom - ca * cc) * dL_dcon.x);
-      dL_db = denom2inv * 2 * (cb * cc * dL_dcon.x - (denom + 2 * cb * cb) * dL_dcon.y + ca * cb * dL_dcon.z);
-      if (AA && aa_r > 2.5e-5f) {  // (on the floor h is a constant: no r-term)
-        const float x = cov2D.m[0][0], y = cov2D.m[1][1], z = cb, w = 0.3f;
-        const float dL_dr = acc_m2d.w * aa_ow / (2.f * aa_r);
-        const float s = dL_dr * w / (denom * denom);
-        dL_da += s * (y * y + w * y + z * z);
-        dL_dc += s * (x * x + w * x + z * z);
-        dL_db += s * (-2.f * z * (x + y + w));
-      }
-      dcov[0] = (Tm[0][0] * Tm[0][0] * dL_da + Tm[0][0] * Tm[1][0] * dL_db + Tm[1][0] * Tm[1][0] * dL_dc);
-      dcov[3] = (Tm[0][1] * Tm[0][1] * dL_da + Tm[0][1] * Tm[1][1] * dL_db + Tm[1][1] * Tm[1][1] * dL_dc);
-      dcov[5] = (Tm[0][2] * Tm[0][2] * dL_da + Tm[0][2] * Tm[1][2] * dL_db + Tm[1][2] * Tm[1][2] * dL_dc);
-      dcov[1] = 2 * Tm[0][0] * Tm[0][1] * dL_da + (Tm[0][0] * Tm[1][1] + Tm[0][1] * Tm[1][0]) * dL_db +
-                2 * Tm[1][0] * Tm[1][1] * dL_dc;
-      dcov[2] = 2 * Tm[0][0] * Tm[0][2] * dL_da + (Tm[0][0] * Tm[1][2] + Tm[0][2] * Tm[1][0]) * dL_db +
-                2 * Tm[1][0] * Tm[1][2] * dL_dc;
-      dcov[4] = 2 * Tm[0][2] * Tm[0][1] * dL_da + (Tm[0][1] * Tm[1][2] + Tm[0][2] * Tm[1][1]) * dL_db +
-                2 * Tm[1][1] * Tm[1][2] * dL_dc;
-    }
-    const auto& V = Vrk.m;
-    const float dL_dT00 = 2 * (Tm[0][0] * V[0][0] + Tm[0][1] * V[0][1] + Tm[0][2] * V[0][2]) * dL_da +
-                          (Tm[1][0] * V[0][0] + Tm[1][1] * V[0][1] + Tm[1][2] * V[0][2]) * dL_db;
-    const float dL_dT01 = 2 * (Tm[0][0] * V[1][0] + Tm[0][1] * V[1][1] + Tm[0][2] * V[1][2]) * dL_da +
-                          (Tm[1][0] * V[1][0] + Tm[1][1] * V[1][1] + Tm[1][2] * V[1][2]) * dL_db;
-    const float dL_dT02 = 2 * (Tm[0][0] * V[2][0] + Tm[0][1] * V[2][1] + Tm[0][2] * V[2][2]) * dL_da +
-                          (Tm[1][0] * V[2][0] + Tm[1][1] * V[2][1] + Tm[1][2] * V[2][2]) * dL_db;
-    const float dL_dT10 = 2 * (Tm[1][0] * V[0][0] + Tm[1][1] * V[0][1] + Tm[1][2] * V[0][2]) * dL_dc +
-                          (Tm[0][0] * V[0][0] + Tm[0][1] * V[0][1] + Tm[0][2] * V[0][2]) * dL_db;
-    const float dL_dT11 = 2 * (Tm[1][0] * V[1][0] + Tm[1][1] * V[1][1] + Tm[1][2] * V[1][2]) * dL_dc +
-                          (Tm[0][0] * V[1][0] + Tm[0][1] * V[1][1] + Tm[0][2] * V[1][2]) * dL_db;
-    const float dL_dT12 = 2 * (Tm[1][0] * V[2][0] + Tm[1][1] * V[2][1] + Tm[1][2] * V[2][2]) * dL_dc +
-                          (Tm[0][0] * V[2][0] + Tm[0][1] * V[2][1] + Tm[0][2] * V[2][2]) * dL_db;
-    const auto& Wx = Wm.m;
-    const float dL_dJ00 = Wx[0][0] * dL_dT00 + Wx[0][1] * dL_dT01 + Wx[0][2] * dL_dT02;
-    const float dL_dJ02 = Wx[2][0] * dL_dT00 + Wx[2][1] * dL_dT01 + Wx[2][2] * dL_dT02;
-    const float dL_dJ11 = Wx[1][0] * dL_dT10 + Wx[1][1] * dL_dT11 + Wx[1][2] * dL_dT12;
-    const float dL_dJ12 = Wx[2][0] * dL_dT10 + Wx[2][1] * dL_dT11 + Wx[2][2] * dL_dT12;
-    const float tz = 1.f / t.z, tz2 = tz * tz, tz3 = tz2 * tz;
-    const float dL_dtx = x_grad_mul * -h_x * tz2 * dL_dJ02;
-    const float dL_dty = y_grad_mul * -h_y * tz2 * dL_dJ12;
-    const float dL_dtz = -h_x * tz2 * dL_dJ00 - h_y * tz2 * dL_dJ11 + (2 * h_x * t.x) * tz3 * dL_dJ02 +
-                         (2 * h_y * t.y) * tz3 * dL_dJ12;
+    const Cov2D c = cov2d_chain(view_point(view, mean), view, c3, a.tan_fovx, a.tan_fovy, a.h_x, a.h_y);
+    const Cov2DGrad g = cov2d_backward(c.cov, c.T, dL_dcon, AA, acc_m2d.w, aa_ow, dcov);
+    if (AA) aa_h = g.aa_h;
+    const V3 dL_dt = chain_backward(c, g, a.h_x, a.h_y).dt;
     // transformVec4x3Transpose, auxiliary.h:89-97 (assignment, backward.cu:273)
-    dmean = {view[0] * dL_dtx + view[1] * dL_dty + view[2] * dL_dtz,
-             view[4] * dL_dtx + view[5] * dL_dty + view[6] * dL_dtz,
-             view[8] * dL_dtx + view[9] * dL_dty + view[10] * dL_dtz};
+    dmean = {view[0] * dL_dt.x + view[1] * dL_dt.y + view[2] * dL_dt.z,
+             view[4] * dL_dt.x + view[5] * dL_dt.y + view[6] * dL_dt.z,
+             view[8] * dL_dt.x + view[9] * dL_dt.y + view[10] * dL_dt.z};
 
     // ---- preprocessCUDA (backward), backward.cu:370-395 ----
     const V3 m = mean;
-    const float m_hw = proj[3] * m.x + proj[7] * m.y + proj[11] * m.z + proj[15];
-    const float m_w = 1.0f / (m_hw + 0.0000001f);
-    const float mul1 = (proj[0] * m.x + proj[4] * m.y + proj[8] * m.z + proj[12]) * m_w * m_w;
-    const float mul2 = (proj[1] * m.x + proj[5] * m.y + proj[9] * m.z + proj[13]) * m_w * m_w;
+    const HomTerms hm = hom_backward_terms(proj, m);
+    const float m_w = hm.m_w, mul1 = hm.mul1, mul2 = hm.mul2;
     nonzero_in = nonzero_in || g2x != 0.f || g2y != 0.f;
     V3 dL_dmean;
     dL_dmean.x = (proj[0] * m_w - proj[3] * mul1) * g2x + (proj[1] * m_w - proj[3] * mul2) * g2y;
@@ -675,47 +622,13 @@ preprocess_backward_kernel(const PreBwdArgs a) {
     if (a.shs != nullptr) {
       // computeColorFromSH (backward), backward.cu:20-139
       const V3 dir_orig = {m.x - cam.campos[0], m.y - cam.campos[1], m.z - cam.campos[2]};
-      const float len = sqrtf(dir_orig.x * dir_orig.x + dir_orig.y * dir_orig.y + dir_orig.z * dir_orig.z);
-      const V3 dir = {dir_orig.x / len, dir_orig.y / len, dir_orig.z / len};
+      const V3 dir = unit_dir(dir_orig);
       nonzero_in = nonzero_in || dL_dRGB.x != 0.f || dL_dRGB.y != 0.f || dL_dRGB.z != 0.f;
-      dL_dRGB.x *= (cl & 1) ? 0.f : 1.f;
-      dL_dRGB.y *= (cl & 2) ? 0.f : 1.f;
-      dL_dRGB.z *= (cl & 4) ? 0.f : 1.f;
+      dL_dRGB = unclamped_rgb_grad(dL_dRGB, cl);
       drgb = dL_dRGB;
-      const float x = dir.x, y = dir.y, z = dir.z;
-      dsh[0] = SH_C0 * dL_dRGB;
-      if (a.D > 0) {
-        dsh[1] = (-SH_C1 * y) * dL_dRGB;
-        dsh[2] = (SH_C1 * z) * dL_dRGB;
-        dsh[3] = (-SH_C1 * x) * dL_dRGB;
-        if (a.D > 1) {
-          const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-          dsh[4] = (SH_C2[0] * xy) * dL_dRGB;
-          dsh[5] = (SH_C2[1] * yz) * dL_dRGB;
-          dsh[6] = (SH_C2[2] * (2.f * zz - xx - yy)) * dL_dRGB;
-          dsh[7] = (SH_C2[3] * xz) * dL_dRGB;
-          dsh[8] = (SH_C2[4] * (xx - yy)) * dL_dRGB;
-          if (a.D > 2) {
-            dsh[9] = (SH_C3[0] * y * (3.f * xx - yy)) * dL_dRGB;
-            dsh[10] = (SH_C3[1] * xy * z) * dL_dRGB;
-            dsh[11] = (SH_C3[2] * y * (4.f * zz - xx - yy)) * dL_dRGB;
-            dsh[12] = (SH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy)) * dL_dRGB;
-            dsh[13] = (SH_C3[4] * x * (4.f * zz - xx - yy)) * dL_dRGB;
-            dsh[14] = (SH_C3[5] * z * (xx - yy)) * dL_dRGB;
-            dsh[15] = (SH_C3[6] * x * (xx - 3.f * yy)) * dL_dRGB;
-          }
-        }
-      }
+      sh_grad_terms(a.D, dir, dL_dRGB, dsh);
       const V3 dL_ddir = {dot3(dRGBdx, dL_dRGB), dot3(dRGBdy, dL_dRGB), dot3(dRGBdz, dL_dRGB)};
-      // dnormvdv, auxiliary.h:107-117
-      const V3 v = dir_orig, dv = dL_ddir;
-      const float sum2 = v.x * v.x + v.y * v.y + v.z * v.z;
-      const float invsum32 = 1.0f / sqrtf(sum2 * sum2 * sum2);
-      V3 dm;
-      dm.x = ((+sum2 - v.x * v.x) * dv.x - v.y * v.x * dv.y - v.z * v.x * dv.z) * invsum32;
-      dm.y = (-v.x * v.y * dv.x + (sum2 - v.y * v.y) * dv.y - v.z * v.y * dv.z) * invsum32;
-      dm.z = (-v.x * v.z * dv.x - v.y * v.z * dv.y + (sum2 - v.z * v.z) * dv.z) * invsum32;
-      dmean = dmean + dm;
+      dmean = dmean + dnormvdv(dir_orig, dL_ddir);
     }
 
     if (a.scales != nullptr) {
@@ -820,39 +733,13 @@ preprocess_backward_kernel(const PreBwdArgs a) {
 // Gaussian and view (all-gather) instead of summing 3M (all-reduce of 192 B per Gaussian at M = 16), and every rank
 // rebuilds sum_v c_k(dir_v) * dL_dRGB_v itself, views in ascending order: the operations and the order of a single
 // process that accumulates the views' gradients one after the other, so all replicas hold bit-identical sums.
-// The c_k are spelled exactly as in preprocess_backward_kernel.
 // ----------------------------------------------------------------------------------
-// One view's SH-gradient terms of a Gaussian: t[k] = c_k(dir) * dL_dRGB for the coefficients of degree <= D, zero above.
-__device__ __forceinline__ void sh_grad_terms(int D, V3 m, const float* __restrict__ cam, V3 dL_dRGB, V3* t) {
-  const V3 dir_orig = {m.x - cam[0], m.y - cam[1], m.z - cam[2]};
-  const float len = sqrtf(dir_orig.x * dir_orig.x + dir_orig.y * dir_orig.y + dir_orig.z * dir_orig.z);
-  const V3 dir = {dir_orig.x / len, dir_orig.y / len, dir_orig.z / len};
-  const float x = dir.x, y = dir.y, z = dir.z;
+// One view's SH-gradient terms of a Gaussian at m, every t[k] written
+__device__ __forceinline__ void sh_grad_terms_of_view(int D, V3 m, const float* __restrict__ cam, V3 dL_dRGB, V3* t) {
+  const V3 dir = unit_dir(V3{m.x - cam[0], m.y - cam[1], m.z - cam[2]});
 #pragma unroll
   for (int k = 0; k < 16; ++k) t[k] = {0.f, 0.f, 0.f};
-  t[0] = SH_C0 * dL_dRGB;
-  if (D > 0) {
-    t[1] = (-SH_C1 * y) * dL_dRGB;
-    t[2] = (SH_C1 * z) * dL_dRGB;
-    t[3] = (-SH_C1 * x) * dL_dRGB;
-    if (D > 1) {
-      const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-      t[4] = (SH_C2[0] * xy) * dL_dRGB;
-      t[5] = (SH_C2[1] * yz) * dL_dRGB;
-      t[6] = (SH_C2[2] * (2.f * zz - xx - yy)) * dL_dRGB;
-      t[7] = (SH_C2[3] * xz) * dL_dRGB;
-      t[8] = (SH_C2[4] * (xx - yy)) * dL_dRGB;
-      if (D > 2) {
-        t[9] = (SH_C3[0] * y * (3.f * xx - yy)) * dL_dRGB;
-        t[10] = (SH_C3[1] * xy * z) * dL_dRGB;
-        t[11] = (SH_C3[2] * y * (4.f * zz - xx - yy)) * dL_dRGB;
-        t[12] = (SH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy)) * dL_dRGB;
-        t[13] = (SH_C3[4] * x * (4.f * zz - xx - yy)) * dL_dRGB;
-        t[14] = (SH_C3[5] * z * (xx - yy)) * dL_dRGB;
-        t[15] = (SH_C3[6] * x * (xx - 3.f * yy)) * dL_dRGB;
-      }
-    }
-  }
+  sh_grad_terms(D, dir, dL_dRGB, t);
 }
 
 __global__ void __launch_bounds__(GAUSS_BLOCK) sh_grad_compose_kernel(int P, int D, int M, int N,
@@ -875,7 +762,7 @@ __global__ void __launch_bounds__(GAUSS_BLOCK) sh_grad_compose_kernel(int P, int
     // a view that does not see the Gaussian (or whose colour was clamped in all channels) contributes exact zeros
     if (dL_dRGB.x == 0.f && dL_dRGB.y == 0.f && dL_dRGB.z == 0.f) continue;
     V3 t[16];
-    sh_grad_terms(D, m, campos + 3 * v, dL_dRGB, t);
+    sh_grad_terms_of_view(D, m, campos + 3 * v, dL_dRGB, t);
 #pragma unroll
     for (int k = 0; k < 16; ++k) dsh[k] = dsh[k] + t[k];
   }
@@ -1083,7 +970,7 @@ __global__ void __launch_bounds__(GAUSS_BLOCK) view_messages_accumulate_kernel(i
         if (dL_dRGB.x == 0.f && dL_dRGB.y == 0.f && dL_dRGB.z == 0.f) continue;  // (as sh_grad_compose_kernel)
         const ViewMsg v = carve_view_message(messages + (size_t)(vb + u) * stride_words, P, cap);
         V3 t[16];
-        sh_grad_terms(D, m, v.cam, dL_dRGB, t);
+        sh_grad_terms_of_view(D, m, v.cam, dL_dRGB, t);
 #pragma unroll
         for (int kk = 0; kk < 16; ++kk) dsh[kk] = dsh[kk] + t[kk];
       }
