@@ -1,5 +1,5 @@
 """Guard bands and poison around every buffer the Python glue hands to the native library (a helper module, imported by
-test_cpu_guarded_alloc.py and test_gpu_guard_bands.py only).
+test_cpu_guarded_alloc.py, test_gpu_guard_bands.py and test_gpu_stream_order.py only).
 
 The library never allocates: outputs, the three state buffers and every workspace are `torch.empty` / `torch.zeros` /
 `torch.ones` / `torch.full` / `torch.empty_like` / `torch.zeros_like` calls of `gaussianeditor_amd/**`, looked up as

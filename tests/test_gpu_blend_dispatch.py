@@ -9,17 +9,29 @@ two channel counts mixed up, the forward's exact kernel where the fast one was a
 see: a kernel of another cut -- every cut computes the same image and the same weights, so all of them are held to the
 oracle here, but not told apart --, and in the trace an exact kernel in place of the fast one (0 / 1 masks, no flipped
 pixel on this scene).  (The checkpointed forward is chosen by process-wide environment knobs; every SEG case of
-test_gpu_k7_matrix.py exercises it.)"""
+test_gpu_k7_matrix.py exercises it.)
+
+The grid of the persistent kernels is compute units x 4 x GSR_BLEND_WAVES_PER_SIMD (4 by default), and the cut's
+thresholds move with it: `_grid` reads the knob as the library does, and test_on_other_grid_shapes runs the file, the
+feature kernels and the feature cells of the guard-band matrix in a fresh process for 1, 2, 3, 5 and 8 (6.1, 6.5, 7.4, 8.0
+and 8.8 s on the MI355X; this process: 5 s without them).  test_back_to_back_launches_of_one_queue_kind is where a launch
+that fails to put its queue's cursors back shows, at each of those grids."""
 import functools
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
 import torch
 
-from helpers import flipped_pixels, gaussians_under, hip_state, make_case, oracle_forward, settings
+from helpers import (assert_grads_close, flipped_pixels, gaussians_under, hip_state, make_case, oracle_backward, oracle_forward,
+                     rel_err, seed_gradient, settings)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+KNOB = "GSR_BLEND_WAVES_PER_SIMD"
 P = 5000
 
 
@@ -37,9 +49,23 @@ def forward_split(grid, quads, for_backward):
 
 
 @functools.lru_cache(None)
+def _waves_per_simd():
+    """gsr_blend.hip, waves_per_simd(): GSR_BLEND_WAVES_PER_SIMD clamped to 0 .. 8, 0 and unset: 4."""
+    e = os.environ.get(KNOB)
+    if e is None:
+        return 4
+    try:
+        v = int(e)
+    except ValueError:
+        v = 0  # (atoi)
+    return min(max(v, 0), 8) or 4
+
+
+@functools.lru_cache(None)
 def _grid():
-    # (blend_grid_size(): CUs x 4 SIMDs x 4 persistent waves)
-    return torch.cuda.get_device_properties(DEV).multi_processor_count * 4 * 4
+    # (blend_grid_size(): CUs x 4 SIMDs x the persistent waves per SIMD, 4 unless the environment says otherwise: the
+    #  image sizes below stay next to the thresholds of the grid that is really launched)
+    return torch.cuda.get_device_properties(DEV).multi_processor_count * 4 * _waves_per_simd()
 
 
 def _size(cut, for_backward):
@@ -247,3 +273,93 @@ def test_nothing_to_blend(fast):
             sc["xyz"].to(DEV), None, sc["opacity"].to(DEV), None, w, sc["scaling"].to(DEV), sc["rotation"].to(DEV), None, cnt,
             torch.ones(1, H, W, device=DEV))
     assert not w.any() and not cnt.any()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# back-to-back launches of one queue kind; the other launch grids
+# ----------------------------------------------------------------------------------------------------------------------
+def test_back_to_back_launches_of_one_queue_kind():
+    """The cursors of a queue kind (forward, backward, trace) live in the view's image state, zeroed by the binning and then
+    by the workgroup of every launch that retires last (retire_queue): a launch that leaves them standing makes the NEXT
+    launch of its kind on that state skip items.  Two renders of one view, two auxiliary forwards and two backwards on the
+    second one's state, then a smaller view that reuses nothing: every forward bit-identical to its twin and to the oracle,
+    the backwards within the run-to-run bar of test_gpu_parity.py::test_backward_run_to_run_spread (2e-6) of each other and
+    within the parity bar of the oracle."""
+    from oracle import cpu as O
+
+    c = _c()
+    W, H = _size(1, True)  # more quadrant items than persistent waves: the queues are popped
+    case, f = _case(W, H)
+    sc, cam = case["sc"], case["cam"]
+    e = torch.empty(0, device=DEV)
+    dev = lambda t: t.to(DEV).contiguous()  # noqa: E731
+    bg, xyz, op, scl, rot, sh = (dev(t) for t in (case["bg"], sc["xyz"], sc["opacity"], sc["scaling"], sc["rotation"], sc["features"]))
+    view, proj, campos = dev(cam.world_view_transform), dev(cam.full_proj_transform), dev(cam.camera_center)
+
+    def render():
+        return c.rasterize_gaussians(bg, xyz, e, op, scl, rot, 1.0, e, view, proj, case["tfx"], case["tfy"], H, W, sh, case["D"],
+                                     campos, False, False, flags=0)
+
+    first, second = render(), render()
+    R, color, depth, radii, geom, binning, img = second
+    assert R == first[0] == f["num_rendered"] > 0
+    assert torch.equal(first[1], color) and torch.equal(first[2], depth) and torch.equal(first[3], radii)
+    _assert_image(f"second render {W}x{H}", False, color, depth, hip_state(P, R, W, H, geom, binning, img), f, W, H)
+    aux, f_aux = dev(_aux_colors()), _aux_case(W, H)
+    sems = [c.rasterize_gaussians_aux(bg, aux, R, geom, binning, img, H, W, flags=0) for _ in range(2)]
+    assert torch.equal(sems[0], sems[1]) and np.array_equal(sems[1].cpu().numpy(), f_aux["color"])
+    G = seed_gradient(H, W, 5) * (H * W)
+    Gd = dev(G)
+
+    def backward():
+        m2, _, dop, m3, _, dsh, dscl, drot = c.rasterize_gaussians_backward(
+            bg, xyz, radii, e, scl, rot, 1.0, e, view, proj, case["tfx"], case["tfy"], Gd, sh, case["D"], campos, geom, R, binning,
+            img, False, flags=0)
+        torch.cuda.synchronize()
+        return {k: v.cpu().numpy() for k, v in dict(dL_dmeans2D=m2, dL_dopacity=dop, dL_dmeans3D=m3, dL_dsh=dsh, dL_dscales=dscl,
+                                                    dL_drotations=drot).items()}
+
+    a, b = backward(), backward()
+    want = oracle_backward(O, case, f, G)
+    for k in a:
+        spread = rel_err(a[k], b[k])
+        print(f"  back to back: {k} run-to-run {spread:.2e}")
+        assert spread <= 2e-6, (k, spread)
+    for i, g in enumerate((a, b)):
+        assert_grads_close(g, want, tag=f"backward {i}", keys=list(g))
+    # ... and after the backwards, once more the forward kind on that state
+    assert torch.equal(c.rasterize_gaussians_aux(bg, aux, R, geom, binning, img, H, W, flags=0), sems[0])
+    W2, H2 = min(_size(4, False), _size(4, True))
+    assert W2 * H2 < W * H
+    case2, f2 = _case(W2, H2)
+    R2, color2, depth2, _, geom2, binning2, img2 = _render(case2, 0)
+    assert R2 == f2["num_rendered"] > 0
+    _assert_image(f"smaller view {W2}x{H2}", False, color2, depth2, hip_state(P, R2, W2, H2, geom2, binning2, img2), f2, W2, H2)
+
+
+#: what a child of test_on_other_grid_shapes runs: this file (without that test), the feature forward at every channel count
+#: and the feature backward -- grid min(blend grid / 4, 3 x compute units): 1, 2 and 3 slots --, and the feature cells of the
+#: guard-band matrix, which also meet the run on a side stream there
+CHILD_FILES = ("test_gpu_blend_dispatch.py", "test_gpu_features.py", "test_gpu_guard_bands.py")
+CHILD_SELECT = ("(test_gpu_blend_dispatch and not test_on_other_grid_shapes) or channel_counts or backward_with_the_colour_loss "
+                "or test_feature_image_and_its_backward")
+
+
+@pytest.mark.parametrize("waves", ["1", "2", "3", "5", "8"])
+def test_on_other_grid_shapes(waves):
+    """DESIGN 3.3, "no launch-shape knob changes a result": everything above -- the main forward with and without
+    GSR_FLAG_FORWARD_ONLY, the auxiliary forward and the trace in both exp modes at the sizes next to the cut's thresholds
+    of THAT grid, the back-to-back launches -- and the feature kernels, in a fresh process per value of
+    GSR_BLEND_WAVES_PER_SIMD (read once per process), one at a time, each under its own time limit.  At 8 the single-wave
+    kernels launch 8 192 workgroups: 128 retire groups, the last grid retire_queue serves.  Measured on the MI355X: 50 tests
+    per child, the children for 1, 2, 3, 5 and 8 take 6.1, 6.5, 7.4, 8.0 and 8.8 s (4.5 to 7.2 s of them in the tests); every
+    stream run in them conclusive.  Not reached on a 256-CU device and left untested: the memset fallback of prepare_queue
+    (more than 128 retire groups) and units == 0 (a CU count the fold does not divide)."""
+    env = {k: v for k, v in os.environ.items() if k != KNOB}
+    env[KNOB] = waves
+    files = [os.path.join(ROOT, "tests", f) for f in CHILD_FILES]
+    r = subprocess.run([sys.executable, "-m", "pytest", *files, "-m", "gpu", "-x", "-q", "-s", "-k", CHILD_SELECT],
+                       env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    print("\n".join(ln for ln in r.stdout.splitlines() if "side stream" in ln or " passed" in ln or " failed" in ln))
+    assert r.returncode == 0, r.stdout[-6000:] + r.stderr[-2000:]
+    assert " passed" in r.stdout and "failed" not in r.stdout and "skipped" not in r.stdout, r.stdout[-3000:]

@@ -3,7 +3,7 @@
 The native library never allocates: every output, the three state buffers and every workspace is a torch allocation of
 the Python glue, sized by gsr_scratch_sizes and the gsr_*_workspace_size functions, and the kernels get raw pointers.
 The rest of the suite checks what the kernels leave INSIDE those buffers.  Here every matrix cell is driven through the
-product's own Python entry points three times -- under guarded_alloc.GuardedAllocator with pattern 0xFF (NaN as float32,
+product's own Python entry points -- under guarded_alloc.GuardedAllocator with pattern 0xFF (NaN as float32,
 0xFFFFFFFF as an index or count, 255 as a mask byte), with pattern 0x5A (a large finite float, a large index) and
 unpatched -- with the test's own inputs inside guarded interiors too (`place`):
 
@@ -19,9 +19,29 @@ unpatched -- with the test's own inputs inside guarded interiors too (`place`):
 
 Outputs the API documents as unspecified are cut to their specified part before (b): `dead_idx` beyond n_dead.
 
-Measured on the MI355X: the whole file, 60 tests in one process plus the two child processes of the environment regimes,
-runs in 14.7 s; the slowest tests are the two children (3.7 s each, mostly interpreter start) and the 4112 x 4096 image
-(1.6 s).  Guarded allocations whose guards were checked, both patterns together (`test_zz_allocation_counts` prints the
+A fourth run of every cell, in front of the unpatched one, is off the default stream (stream_order.SideStream): on a
+fresh stream, its inputs holding decoys until a sleep on that stream has passed, while the default stream sleeps; its
+outputs are copied to the host on that stream and only that stream is waited for.  (b) holds for it unchanged -- every
+deterministic output bit-identical to the unpatched run --, (c) through the callers' loops over the runs, and the run must
+be conclusive: the outputs on the host while the default stream still sleeps.  A mismatch: the product launched something
+on another stream before the side stream's inputs existed, or something had not run when the outputs were read.  Not
+conclusive: the product waited for the default stream or the whole device.  The run and its warm-up are under
+GuardedAllocator (0x5A, guards unchecked, not in the table below): the buffers are poisoned anew on the side stream, so
+that the warm-up's right results, still in the blocks the caching allocator hands back, cannot stand in for a kernel
+that never ran.  The drivers' own waits are for the current stream, not the device.
+
+Measured on the MI355X, the stream run: all 56 cells (and the two children's) conclusive and bit-identical.  The first run of
+a cell takes 0.3 to 16 ms, except where it loads a code object (rasterizer P1_17x19 165 ms, fused loss tex_5x7 738 ms,
+fused Adam aligned n257 569 ms, densify 296 ms, the children's cell 179 ms), so the sleep is the floor of 200 ms in 52
+cells and 0.66, 2.95, 2.27, 1.18 and 0.71 s in those.  With `place` sleeping 1 ms per input the outputs are on the host
+1.1 ms (simple_knn, 1 input) to 41.5 ms (densify, 37 inputs) after entry, 11.8 ms in the rasterizer cells (11 inputs),
+34.2 ms at 4112 x 4096: the sleep is 5.3 times the window where the margin is smallest (the message round trip, 36
+inputs: 37.6 ms of 200 ms), 5.8 times at 4112 x 4096 and fused Adam two_launches, 7.7 times or more elsewhere.  The whole
+file then runs in 33.5 s (before the stream run: 14.7 s): 52 sleeps of 0.2 s and four longer ones are 17.5 s of that.
+
+Measured on the MI355X before the stream run was added: the whole file, 60 tests in one process plus the two child
+processes of the environment regimes, runs in 14.7 s; the slowest tests are the two children (3.7 s each, mostly
+interpreter start; 4.5 s with the stream run) and the 4112 x 4096 image (1.6 s; 1.95 s).  Guarded allocations whose guards were checked, both patterns together (`test_zz_allocation_counts` prints the
 table); "product": made by an allocation call inside gaussianeditor_amd/, the rest are the tests' own inputs (`place`):
 
     group                  checked  product
@@ -50,6 +70,7 @@ import collections
 import os
 import subprocess
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -60,9 +81,11 @@ import densify_helpers as dh
 import features_helpers as FH
 import loss_helpers as LH
 import mcmc_helpers as mh
+import stream_order as SO
 from depth_helpers import depth_expectation
 from guarded_alloc import GuardedAllocator
 from helpers import assert_grads_close, make_case, oracle_backward, oracle_forward, rel_err, seed_gradient
+from stream_order import host as _host, same_bits as _same_bits
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -89,37 +112,30 @@ def _reset_product_state():
     _reuse.forget()
 
 
-def _host(d):
-    out = {}
-    for k, v in (d or {}).items():
-        if isinstance(v, torch.Tensor):
-            v = v.detach().cpu().contiguous()
-            out[k] = v.view(torch.uint8).numpy() if v.dtype == torch.bool else v.numpy()
-        else:
-            out[k] = v
-    return out
-
-
-def _same_bits(a, b):
-    if isinstance(a, np.ndarray) or isinstance(b, np.ndarray):
-        return (isinstance(a, np.ndarray) and isinstance(b, np.ndarray) and a.shape == b.shape and a.dtype == b.dtype
-                and a.tobytes() == b.tobytes())
-    return type(a) is type(b) and a == b
-
-
 def three_runs(group, fn, tag=""):
     """fn(put) -> (deterministic outputs {name: tensor | number}, gradients {name: tensor} | None), run under 0xFF, under
-    0x5A and unpatched; (a) and (b) asserted here -> [(outputs, gradients)] as numpy, the unpatched run last."""
+    0x5A, on a side stream with late inputs while the default stream sleeps (stream_order.SideStream) and unpatched; (a) and
+    (b) asserted here -> [(outputs, gradients)] as numpy, in that order: the unpatched run last."""
     runs = []
+    cell_seconds = None
     for pattern in PATTERNS + (None,):
         _reset_product_state()
         if pattern is None:
+            # the stream run: after the patterned runs (code objects loaded, the allocator warm), in front of the unpatched one
+            stream_run, side = SO.run_cell(fn, SO.sleep_ms_for(cell_seconds), reset=_reset_product_state,
+                                           allocator=lambda: GuardedAllocator(PATTERNS[1]))
+            print(f"  {group} {tag}: first run {cell_seconds * 1e3:.0f} ms; {SO.report(side)}")
+            runs.append(stream_run)
+            _reset_product_state()
             det, grads = fn(_plain_put)
             torch.cuda.synchronize()
         else:
+            t0 = time.perf_counter()
             with GuardedAllocator(pattern) as ga:
                 det, grads = fn(ga.place)
                 torch.cuda.synchronize()
+            if cell_seconds is None:
+                cell_seconds = time.perf_counter() - t0
             ga.assert_clean()  # (a)
             made = sum(r["site"].startswith("gaussianeditor_amd") for r in ga.records)  # (the rest: the test's own `place`)
             print(f"  {group} {tag}: pattern {pattern:#04x}: {len(ga)} guarded allocations, {made} of them the product's, all clean")
@@ -134,6 +150,10 @@ def three_runs(group, fn, tag=""):
         assert det.keys() == plain.keys(), (group, tag)
         for name in plain:
             assert _same_bits(det[name], plain[name]), f"{group} {tag}: `{name}` depends on the pattern ({pattern:#04x})"
+    # (b) of the stream run: a mismatch -- something ran on another stream before the side stream's inputs existed, or had not
+    # run when the outputs were read; not conclusive -- the product waited for the default stream or for the whole device
+    v = SO.verdict(stream_run[0], plain, side)
+    assert v == "clean", f"{group} {tag}: the run on a side stream: {v}; {SO.report(side)}"
     return runs
 
 
@@ -209,7 +229,7 @@ def _raster(put, case, G, cols=None, cov=None, flags=0, GA=None, GD=None, pose=F
     if GD is not None:
         loss = loss + (depth * put(GD)).sum()
     loss.backward()
-    torch.cuda.synchronize()
+    torch.cuda.current_stream().synchronize()  # (the product has joined its own streams back; a side stream run stays on its stream)
     grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v.detach())) for k, v in leaves.items()}
     if flags & O.FLAG_ABS_GRAD:
         grads["absgrad"] = m2d.absgrad
