@@ -28,8 +28,13 @@
 // A radix pass is three kernels (histogram -> per-bin scan -> scatter); there is no decoupled
 // look-back, so no inter-workgroup hand-off inside a launch (per-XCD L2s are not coherent; a kernel
 // boundary is the cheapest correct fence).  Stability comes from ranking with wave64 ballots in key
-// order, never from atomics.
+// order, never from atomics.  The three scatter kernels (sort_, depth_, group_scatter_kernel) are one
+// algorithm with different payloads: its pieces -- the ballot ranking, the per-digit prefix over the
+// waves, the slot in LDS, the position of the write-out -- are defined once, in "The stable radix
+// scatter" below; on the host, with_sort_width picks the block width of every sort.
 #include <stdlib.h>
+
+#include <type_traits>
 
 #include "gsr_kernels.h"
 
@@ -40,6 +45,54 @@ __device__ __forceinline__ int f2i_sat(float v) {
   if (v >= 2147483648.0f) return 2147483647;
   if (v <= -2147483648.0f) return (-2147483647 - 1);
   return (int)v;
+}
+
+// ----------------------------------------------------------------------------------
+// The stable radix scatter: the pieces sort_scatter_kernel, depth_scatter_kernel and group_scatter_kernel share.
+// Every __shared__ array is declared by the kernel (its LDS size and layout are the kernel's business) and handed in by
+// reference; C is the type of the per-wave counters, L that of the digits' block-local offsets (uint32_t or uint16_t).
+// ----------------------------------------------------------------------------------
+// Rank of a key among the keys of its wave with the same digit `d` (< 2^BITS): (count of that digit in earlier calls, kept
+// in the wave's counter row) + (lower lanes with the same digit in this call, from BITS ballots).  Called by all 64 lanes.
+template <int BITS, class C>
+__device__ __forceinline__ uint32_t wave_digit_rank(uint32_t d, bool valid, C (&cnt_row)[1 << BITS], uint64_t lt_mask) {
+  uint64_t m = __ballot(valid);
+#pragma unroll
+  for (int b = 0; b < BITS; ++b) {
+    const uint64_t bb = __ballot((d >> b) & 1u);
+    m &= ((d >> b) & 1u) ? bb : ~bb;
+  }
+  const uint32_t before = (uint32_t)__popcll(m & lt_mask);
+  uint32_t old = 0;
+  if (valid) old = cnt_row[d];
+  // all reads of this call precede the leader's write (one wave, program order)
+  if (valid && before == 0) cnt_row[d] = (C)(old + (uint32_t)__popcll(m));
+  return old + before;
+}
+// Digit d's counts over the waves -> their exclusive prefix (the waves' local bases); returns the block's total of d.
+// Called by the one thread that owns d.
+template <int NW, int NB, class C>
+__device__ __forceinline__ uint32_t digit_wave_prefix(C (&cnt)[NW][NB], uint32_t d) {
+  uint32_t run = 0;
+#pragma unroll
+  for (int i = 0; i < NW; ++i) {
+    const uint32_t c = cnt[i][d];
+    cnt[i][d] = (C)run;
+    run += c;
+  }
+  return run;
+}
+// The permutation into LDS: the slot of a key in the block-sorted order = (first slot of its digit) + (keys of that digit
+// in earlier waves) + (its rank inside its wave).
+template <int NB, class C, class L>
+__device__ __forceinline__ uint32_t scatter_slot(const L (&lexcl)[NB], const C (&cnt_row)[NB], uint32_t d, uint32_t rank) {
+  return (uint32_t)lexcl[d] + (uint32_t)cnt_row[d] + rank;
+}
+// The write-out: slot j of the block-sorted order, of digit d, goes to the block's first global position of d + its
+// distance from the digit's first slot (a digit that occurs: lexcl[d] <= j).
+template <int NB, class L>
+__device__ __forceinline__ uint32_t write_out_pos(const uint32_t (&gbase)[NB], const L (&lexcl)[NB], uint32_t d, int j) {
+  return gbase[d] + ((uint32_t)j - (uint32_t)lexcl[d]);
 }
 
 // ----------------------------------------------------------------------------------
@@ -235,31 +288,13 @@ __global__ void __launch_bounds__(TH) sort_scatter_kernel(const K* __restrict__ 
     const int64_t k = wbase + (int64_t)i * 64 + l;
     const bool valid = k < n;
     const uint32_t d = (key[i] >> shift) & mask;
-    uint64_t m = __ballot(valid);
-#pragma unroll
-    for (int b = 0; b < RBITS; ++b) {
-      const uint64_t bb = __ballot((d >> b) & 1u);
-      m &= ((d >> b) & 1u) ? bb : ~bb;
-    }
-    const uint32_t before = (uint32_t)__popcll(m & lt_mask);
-    uint32_t old = 0;
-    if (valid) old = cnt[w][d];
-    // all reads of this iteration precede the leader's write (one wave, program order)
-    if (valid && before == 0) cnt[w][d] = old + (uint32_t)__popcll(m);
-    rank[i] = (uint16_t)(old + before);
+    rank[i] = (uint16_t)wave_digit_rank<RBITS>(d, valid, cnt[w], lt_mask);
   }
   __syncthreads();
   {
     // per digit: block total, exclusive prefix over the waves, and the digit's offset in block-sorted order
     uint32_t run = 0;
-    if (owns_bin) {
-#pragma unroll
-      for (int i = 0; i < NW; ++i) {
-        const uint32_t c = cnt[i][threadIdx.x];
-        cnt[i][threadIdx.x] = run;
-        run += c;
-      }
-    }
+    if (owns_bin) run = digit_wave_prefix(cnt, threadIdx.x);
     uint32_t tot;
     const uint32_t ex = block_excl_scan_u32<TH>(run, &tot, smem);
     if (owns_bin) lexcl[threadIdx.x] = ex;
@@ -270,7 +305,7 @@ __global__ void __launch_bounds__(TH) sort_scatter_kernel(const K* __restrict__ 
     const int64_t k = wbase + (int64_t)i * 64 + l;
     if (k < n) {
       const uint32_t d = (key[i] >> shift) & mask;
-      const uint32_t lp = lexcl[d] + cnt[w][d] + rank[i];
+      const uint32_t lp = scatter_slot(lexcl, cnt[w], d, rank[i]);
       skey[lp] = key[i];
       sval[lp] = val[i];
     }
@@ -283,7 +318,7 @@ __global__ void __launch_bounds__(TH) sort_scatter_kernel(const K* __restrict__ 
     if (j < nvalid) {
       const uint32_t kk = skey[j];
       const uint32_t d = (kk >> shift) & mask;
-      const uint32_t pos = gbase[d] + ((uint32_t)j - lexcl[d]);
+      const uint32_t pos = write_out_pos(gbase, lexcl, d, j);
       keys_out[pos] = (K)kk;
       vals_out[pos] = sval[j];
     }
@@ -294,6 +329,19 @@ __global__ void __launch_bounds__(TH) sort_scatter_kernel(const K* __restrict__ 
 // with 1024 threads a block's 4096 keys are ranked by 16 waves in 4 rounds instead of by 4 waves in 16.  Many-block sorts
 // keep 256 threads (more blocks resident per CU).
 constexpr uint32_t SORT_WIDE_MAX_BLOCKS = 1024;
+static bool sort_is_wide(uint32_t nblocks) { return nblocks <= SORT_WIDE_MAX_BLOCKS; }
+// f(TH) with the block width of a sort of `nblocks` blocks as a compile-time constant: decltype(th)::value
+template <class F>
+static void with_sort_width(uint32_t nblocks, F&& f) {
+  if (sort_is_wide(nblocks)) f(std::integral_constant<int, 1024>{});
+  else f(std::integral_constant<int, SORT_THREADS>{});
+}
+// f(flag) with a run-time choice between two instantiations as a compile-time constant
+template <class F>
+static void with_flag(bool flag, F&& f) {
+  if (flag) f(std::true_type{});
+  else f(std::false_type{});
+}
 template <class K, int TH>
 static void radix_sort_pairs_th(hipStream_t s, K* const keys[2], uint32_t* const vals[2], int64_t n, int npass,
                                 const int* digit_bits, uint32_t* hist, uint32_t* bin_total, bool iota_first, int p0,
@@ -310,12 +358,10 @@ static void radix_sort_pairs_th(hipStream_t s, K* const keys[2], uint32_t* const
                        hist, nblocks, pub ? publish_src : nullptr, publish_count, pub ? publish_dst : nullptr, publish_seq,
                        (const uint32_t*)nullptr);
     hipLaunchKernelGGL(sort_scan_kernel, dim3(RBINS), dim3(SORT_THREADS), 0, s, hist, bin_total, nblocks);
-    if (p == 0 && iota_first)
-      hipLaunchKernelGGL((sort_scatter_kernel<true, K, TH>), dim3(nblocks), dim3(TH), 0, s, (const K*)keys[cur],
+    with_flag(p == 0 && iota_first, [&](auto iota) {
+      hipLaunchKernelGGL((sort_scatter_kernel<decltype(iota)::value, K, TH>), dim3(nblocks), dim3(TH), 0, s, (const K*)keys[cur],
                          (const uint32_t*)vals[cur], keys[cur ^ 1], vals[cur ^ 1], n, shift, mask, hist, bin_total, nblocks);
-    else
-      hipLaunchKernelGGL((sort_scatter_kernel<false, K, TH>), dim3(nblocks), dim3(TH), 0, s, (const K*)keys[cur],
-                         (const uint32_t*)vals[cur], keys[cur ^ 1], vals[cur ^ 1], n, shift, mask, hist, bin_total, nblocks);
+    });
     shift += digit_bits[p];
     cur ^= 1;
   }
@@ -328,12 +374,10 @@ static void radix_sort_pairs(hipStream_t s, K* const keys[2], uint32_t* const va
                              const int* digit_bits, uint32_t* hist, uint32_t* bin_total, bool iota_first, int p0 = 0,
                              const uint4* publish_src = nullptr, uint32_t publish_count = 0, uint32_t* publish_dst = nullptr,
                              uint32_t publish_seq = 0) {
-  if ((uint32_t)((n + SORT_KPB - 1) / SORT_KPB) <= SORT_WIDE_MAX_BLOCKS)
-    radix_sort_pairs_th<K, 1024>(s, keys, vals, n, npass, digit_bits, hist, bin_total, iota_first, p0, publish_src, publish_count,
-                                 publish_dst, publish_seq);
-  else
-    radix_sort_pairs_th<K, SORT_THREADS>(s, keys, vals, n, npass, digit_bits, hist, bin_total, iota_first, p0, publish_src,
-                                         publish_count, publish_dst, publish_seq);
+  with_sort_width((uint32_t)((n + SORT_KPB - 1) / SORT_KPB), [&](auto th) {
+    radix_sort_pairs_th<K, decltype(th)::value>(s, keys, vals, n, npass, digit_bits, hist, bin_total, iota_first, p0, publish_src,
+                                                publish_count, publish_dst, publish_seq);
+  });
 }
 
 // ----------------------------------------------------------------------------------
@@ -419,18 +463,7 @@ __global__ void __launch_bounds__(TH) depth_scatter_kernel(const uint32_t* __res
     const int64_t k = wbase + (int64_t)i * 64 + l;
     const bool valid = k < n;
     const uint32_t d = (key[i] >> shift) & mask;
-    uint64_t m = __ballot(valid);
-#pragma unroll
-    for (int b = 0; b < RBITS; ++b) {
-      const uint64_t bb = __ballot((d >> b) & 1u);
-      m &= ((d >> b) & 1u) ? bb : ~bb;
-    }
-    const uint32_t before = (uint32_t)__popcll(m & lt_mask);
-    uint32_t old = 0;
-    if (valid) old = cnt[w][d];
-    // all reads of this iteration precede the leader's write (one wave, program order)
-    if (valid && before == 0) cnt[w][d] = old + (uint32_t)__popcll(m);
-    rank[i] = (uint16_t)(old + before);
+    rank[i] = (uint16_t)wave_digit_rank<RBITS>(d, valid, cnt[w], lt_mask);
   }
   __syncthreads();
   {
@@ -514,42 +547,33 @@ static void depth_sort_grouped_th(hipStream_t s, int P, const Geom& g, int p0, i
     // (the histogram kernel always runs 1024 threads wide: it holds 1 KB of LDS, and its extra publishing block walks
     //  ceil(P / 256) partials -- 23 438 at 6 M Gaussians, 40 us with 256 threads and one load in flight per thread)
     const dim3 gh(nblocks + (pub ? 1u : 0u)), gs(nblocks), bt(TH), bh(1024);
-    if (fin)
-      hipLaunchKernelGGL((sort_hist_kernel<uint32_t, 1024, true>), gh, bh, 0, s, (const uint32_t*)g.dkey[cur], n, shift, 255u, g.ghist,
+    with_flag(fin, [&](auto lastp) {
+      constexpr bool LASTP = decltype(lastp)::value;
+      hipLaunchKernelGGL((sort_hist_kernel<uint32_t, 1024, LASTP>), gh, bh, 0, s, (const uint32_t*)g.dkey[cur], n, shift, 255u, g.ghist,
                          nblocks, pub ? g.k1_partials : nullptr, npart, pub ? publish_dst : nullptr, publish_seq,
-                         (const uint32_t*)g.drect[cur]);
-    else
-      hipLaunchKernelGGL((sort_hist_kernel<uint32_t, 1024, false>), gh, bh, 0, s, (const uint32_t*)g.dkey[cur], n, shift, 255u, g.ghist,
-                         nblocks, pub ? g.k1_partials : nullptr, npart, pub ? publish_dst : nullptr, publish_seq,
-                         (const uint32_t*)nullptr);
-    hipLaunchKernelGGL(sort_scan_kernel, dim3(fin ? 2 * RBINS : RBINS), dim3(SORT_THREADS), 0, s, g.ghist, g.gbin_total, nblocks);
-#define GSR_DEPTH_SCATTER(LASTP, IOTAP)                                                                                          \
-  hipLaunchKernelGGL((depth_scatter_kernel<LASTP, IOTAP, TH>), gs, bt, 0, s, (const uint32_t*)g.dkey[cur],                       \
-                     (const uint32_t*)g.dval[cur], (const uint32_t*)g.drect[cur], (const uint2*)g.rect, g.dkey[cur ^ 1],         \
-                     g.dval[cur ^ 1], g.drect[cur ^ 1], n, shift, 255u, (const uint32_t*)g.ghist, (const uint32_t*)g.gbin_total, \
-                     nblocks, hdr, (uint32_t)(cur ^ 1))
-    if (fin && p == 0) GSR_DEPTH_SCATTER(true, true);
-    else if (fin) GSR_DEPTH_SCATTER(true, false);
-    else if (p == 0) GSR_DEPTH_SCATTER(false, true);
-    else GSR_DEPTH_SCATTER(false, false);
-#undef GSR_DEPTH_SCATTER
+                         LASTP ? (const uint32_t*)g.drect[cur] : (const uint32_t*)nullptr);
+      hipLaunchKernelGGL(sort_scan_kernel, dim3(LASTP ? 2 * RBINS : RBINS), dim3(SORT_THREADS), 0, s, g.ghist, g.gbin_total, nblocks);
+      with_flag(p == 0, [&](auto iotap) {
+        hipLaunchKernelGGL((depth_scatter_kernel<LASTP, decltype(iotap)::value, TH>), gs, bt, 0, s, (const uint32_t*)g.dkey[cur],
+                           (const uint32_t*)g.dval[cur], (const uint32_t*)g.drect[cur], (const uint2*)g.rect, g.dkey[cur ^ 1],
+                           g.dval[cur ^ 1], g.drect[cur ^ 1], n, shift, 255u, (const uint32_t*)g.ghist,
+                           (const uint32_t*)g.gbin_total, nblocks, hdr, (uint32_t)(cur ^ 1));
+      });
+    });
   }
 }
 hipError_t launch_depth_passes_grouped(hipStream_t s, int P, const Geom& g, int p0, int p1, bool last, uint32_t* publish_dst,
                                        uint32_t publish_seq) {
-  if ((uint32_t)(((int64_t)P + SORT_KPB - 1) / SORT_KPB) <= SORT_WIDE_MAX_BLOCKS)
-    depth_sort_grouped_th<1024>(s, P, g, p0, p1, last, publish_dst, publish_seq);
-  else
-    depth_sort_grouped_th<SORT_THREADS>(s, P, g, p0, p1, last, publish_dst, publish_seq);
+  with_sort_width((uint32_t)(((int64_t)P + SORT_KPB - 1) / SORT_KPB),
+                  [&](auto th) { depth_sort_grouped_th<decltype(th)::value>(s, P, g, p0, p1, last, publish_dst, publish_seq); });
   return hipGetLastError();
 }
 
 // ----------------------------------------------------------------------------------
 // Depth order of the Gaussians + prefix of tiles_touched in that order.
 // ----------------------------------------------------------------------------------
-// `sgx` != 0 (grouped path): block sums of the number of 8x8-tile GROUPS a rectangle reaches; sgx == 0 (legacy pair sort):
-// of its tiles.
-__global__ void __launch_bounds__(GAUSS_BLOCK) sorted_block_sums_kernel(int P, int gx, int sgx, const uint32_t* __restrict__ order,
+// Legacy pair sort only: block sums of the number of tiles a rectangle reaches.
+__global__ void __launch_bounds__(GAUSS_BLOCK) sorted_block_sums_kernel(int P, int gx, const uint32_t* __restrict__ order,
                                                                        const uint2* __restrict__ rect,
                                                                        uint32_t* __restrict__ wh_sorted,
                                                                        uint32_t* __restrict__ org_sorted,
@@ -562,14 +586,10 @@ __global__ void __launch_bounds__(GAUSS_BLOCK) sorted_block_sums_kernel(int P, i
   // What the emit kernel needs of it is left in depth order, so that it reads everything coalesced.
   const uint2 rc = i < P ? rect[order[i]] : make_uint2(0u, 0u);
   const uint32_t w = rc.y & 0xffffu, h = rc.y >> 16, x0 = rc.x & 0xffffu, y0 = rc.x >> 16;
-  uint32_t n = w * h, org = y0 * (uint32_t)gx + x0;
-  if (sgx != 0 && n != 0) {  // grouped path: the emit kernel gets the tile rectangle as it is and counts GROUPS
-    n = (((x0 + w - 1u) >> GROUP_SHIFT) - (x0 >> GROUP_SHIFT) + 1u) * (((y0 + h - 1u) >> GROUP_SHIFT) - (y0 >> GROUP_SHIFT) + 1u);
-    org = rc.x;
-  }
+  const uint32_t n = w * h, org = y0 * (uint32_t)gx + x0;
   if (i < P) {
     wh_sorted[i] = rc.y;  // width | height << 16 of the tile rectangle
-    org_sorted[i] = org;  // legacy path: id of its first tile; grouped path: x | y << 16 of its first tile
+    org_sorted[i] = org;  // id of its first tile
   }
   uint32_t total;
   (void)block_excl_scan_u32<GAUSS_BLOCK>(n, &total, smem);
@@ -606,11 +626,11 @@ hipError_t launch_depth_passes(hipStream_t s, int P, const Geom& g, int p0, int 
   return hipGetLastError();
 }
 // After `passes` passes: tile counts gathered into depth order (+ their per-block sums and the prefix of those).
-hipError_t launch_depth_finish(hipStream_t s, int P, const Geom& g, int passes, int gx, int sgx) {
+hipError_t launch_depth_finish(hipStream_t s, int P, const Geom& g, int passes, int gx) {
   const int fin = passes & 1;
   const int nb = (P + GAUSS_BLOCK - 1) / GAUSS_BLOCK;
   // dkey[fin ^ 1] / dval[fin ^ 1] (the input of the last pass) are dead: reuse them for the depth-ordered rectangles
-  hipLaunchKernelGGL(sorted_block_sums_kernel, dim3(nb), dim3(GAUSS_BLOCK), 0, s, P, gx, sgx, g.dval[fin], g.rect,
+  hipLaunchKernelGGL(sorted_block_sums_kernel, dim3(nb), dim3(GAUSS_BLOCK), 0, s, P, gx, g.dval[fin], g.rect,
                      g.dkey[fin ^ 1], g.dval[fin ^ 1], g.block_sums, reinterpret_cast<uint32_t*>(g.total), (uint32_t)fin);
   hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(1024), 0, s, g.block_sums, g.block_offs, nb);
   return hipGetLastError();
@@ -625,6 +645,24 @@ hipError_t launch_depth_finish(hipStream_t s, int P, const Geom& g, int passes, 
 // inside its rectangle gives the tile, rows first as the reference's loops do.
 // Only the tile id is written as key (the depth is implied by the position).
 // ----------------------------------------------------------------------------------
+// The owner of slot s of a block's run: the last j with s_off[j] <= s (s < s_off[GAUSS_BLOCK], so s_off[j + 1] > s and
+// Gaussian j owns at least one slot).
+__device__ __forceinline__ uint32_t slot_owner(const uint32_t (&s_off)[GAUSS_BLOCK + 1], uint32_t s) {
+  uint32_t lo = 0, hi = GAUSS_BLOCK;
+#pragma unroll
+  for (int step = 0; step < 8; ++step) {  // GAUSS_BLOCK == 256
+    const uint32_t mid = (lo + hi) >> 1;
+    if (s_off[mid] <= s) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+// k / w without an integer division: k, w < 2^24 (at most gx * gy tiles), one correction step each way.
+__device__ __forceinline__ uint32_t div_small(uint32_t k, uint32_t w) {
+  uint32_t q = (uint32_t)((float)k * __builtin_amdgcn_rcpf((float)w));
+  if (q * w > k) q--;
+  if ((q + 1u) * w <= k) q++;
+  return q;
+}
 template <class K>
 __global__ void __launch_bounds__(GAUSS_BLOCK) emit_keys_kernel(int P, int gx, int nclear, const Geom g, K* __restrict__ tkeys,
                                                                uint32_t* __restrict__ vals, uint2* __restrict__ ranges) {
@@ -651,18 +689,9 @@ __global__ void __launch_bounds__(GAUSS_BLOCK) emit_keys_kernel(int P, int gx, i
   if (threadIdx.x == 0) s_off[GAUSS_BLOCK] = total;
   __syncthreads();
   for (uint32_t s = threadIdx.x; s < total; s += GAUSS_BLOCK) {
-    // the last j with s_off[j] <= s: s_off[j + 1] > s, so Gaussian j owns at least one slot
-    uint32_t lo = 0, hi = GAUSS_BLOCK;
-#pragma unroll
-    for (int step = 0; step < 8; ++step) {  // GAUSS_BLOCK == 256
-      const uint32_t mid = (lo + hi) >> 1;
-      if (s_off[mid] <= s) lo = mid; else hi = mid;
-    }
+    const uint32_t lo = slot_owner(s_off, s);
     const uint32_t k = s - s_off[lo], wj = s_w[lo];
-    // row = k / wj without an integer division: k, wj < 2^24 (at most gx * gy tiles), one correction step each way
-    uint32_t row = (uint32_t)((float)k * __builtin_amdgcn_rcpf((float)wj));
-    if (row * wj > k) row--;
-    if ((row + 1u) * wj <= k) row++;
+    const uint32_t row = div_small(k, wj);
     const uint32_t col = k - row * wj;
     tkeys[boff + s] = (K)(s_org[lo] + row * (uint32_t)gx + col);
     vals[boff + s] = s_idx[lo];
@@ -719,20 +748,11 @@ __global__ void __launch_bounds__(GAUSS_BLOCK) emit_groups_kernel(int P, int sgx
   if (threadIdx.x == 0) s_off[GAUSS_BLOCK] = total;
   __syncthreads();
   for (uint32_t s = threadIdx.x; s < total; s += GAUSS_BLOCK) {
-    // the last j with s_off[j] <= s: s_off[j + 1] > s, so Gaussian j owns at least one slot
-    uint32_t lo = 0, hi = GAUSS_BLOCK;
-#pragma unroll
-    for (int step = 0; step < 8; ++step) {  // GAUSS_BLOCK == 256
-      const uint32_t mid = (lo + hi) >> 1;
-      if (s_off[mid] <= s) lo = mid; else hi = mid;
-    }
+    const uint32_t lo = slot_owner(s_off, s);
     const uint32_t k = s - s_off[lo], jr = s_rect[lo];
     const uint32_t jx = jr & 0xffu, jy = (jr >> 8) & 0xffu, jw = ((jr >> 16) & 0xffu) + 1u, jh = (jr >> 24) + 1u;
     const uint32_t g0x = jx >> GROUP_SHIFT, nsx = ((jx + jw - 1u) >> GROUP_SHIFT) - g0x + 1u;
-    // row = k / nsx without an integer division (k, nsx < 2^24), one correction step each way
-    uint32_t row = (uint32_t)((float)k * __builtin_amdgcn_rcpf((float)nsx));
-    if (row * nsx > k) row--;
-    if ((row + 1u) * nsx <= k) row++;
+    const uint32_t row = div_small(k, nsx);
     const uint32_t gxi = g0x + (k - row * nsx), gyi = (jy >> GROUP_SHIFT) + row;
     gkeys[boff + s] = (gyi * (uint32_t)sgx + gxi) | (group_local_rect(jx, jy, jw, jh, gxi, gyi) << 16);
     vals[boff + s] = s_idx[lo];
@@ -924,18 +944,13 @@ __global__ void __launch_bounds__(1024) tile_worklist_kernel(int T, uint2* __res
 // Grouped path, step 2: ONE stable radix pass over the group instances (key = group id, < 2^BITS), whose output leaves
 // each group's segment padded to whole chunks: segment s starts at chunk * (number of chunks of the groups before it).
 // ----------------------------------------------------------------------------------
-// histogram of the pass + the padding value into every KEY slot of the output side (the scatter overwrites the real ones:
-// what remains are the padding slots between the segments and behind the last one; a real key never equals GROUP_PAD,
-// its local rectangle has 12 bits)
+// histogram of the pass (the padding slots of the output side are filled by extra blocks of emit_groups_kernel)
 template <int BITS, int TH>
 __global__ void __launch_bounds__(TH) group_hist_kernel(const uint32_t* __restrict__ keys, int64_t n,
-                                                                 uint32_t* __restrict__ hist, uint32_t nblocks,
-                                                                 uint32_t* __restrict__ fill_dst, int64_t fill_n) {
+                                                                 uint32_t* __restrict__ hist, uint32_t nblocks) {
   constexpr int NB = 1 << BITS;
   __shared__ uint32_t h[NB];
   for (int i = threadIdx.x; i < NB; i += TH) h[i] = 0;
-  (void)fill_dst;  // (the padding of the sorted side is written by extra blocks of emit_groups_kernel since round 3)
-  (void)fill_n;
   __syncthreads();
   const int64_t base = (int64_t)blockIdx.x * SORT_KPB;
   uint32_t kv[(SORT_KPB / TH)];
@@ -1017,18 +1032,7 @@ __global__ void __launch_bounds__(TH) group_scatter_kernel(const uint32_t* __res
     const int64_t k = wbase + (int64_t)i * 64 + l;
     const bool valid = k < n;
     const uint32_t d = key[i] & (NB - 1);
-    uint64_t m = __ballot(valid);
-#pragma unroll
-    for (int b = 0; b < BITS; ++b) {
-      const uint64_t bb = __ballot((d >> b) & 1u);
-      m &= ((d >> b) & 1u) ? bb : ~bb;
-    }
-    const uint32_t before = (uint32_t)__popcll(m & lt_mask);
-    uint32_t old = 0;
-    if (valid) old = cnt[w][d];
-    // all reads of this iteration precede the leader's write (one wave, program order)
-    if (valid && before == 0) cnt[w][d] = (uint16_t)(old + (uint32_t)__popcll(m));
-    rank[i] = (uint16_t)(old + before);
+    rank[i] = (uint16_t)wave_digit_rank<BITS>(d, valid, cnt[w], lt_mask);
   }
   __syncthreads();
   {
@@ -1038,14 +1042,7 @@ __global__ void __launch_bounds__(TH) group_scatter_kernel(const uint32_t* __res
     for (int j = 0; j < BPT; ++j) {
       const uint32_t d = owns ? threadIdx.x * BPT + j : 0u;
       uint32_t run = 0;
-      if (owns) {
-#pragma unroll
-        for (int i = 0; i < NW; ++i) {
-          const uint32_t c = cnt[i][d];
-          cnt[i][d] = (uint16_t)run;
-          run += c;
-        }
-      }
+      if (owns) run = digit_wave_prefix(cnt, d);
       tot_d[j] = run;
       sum += run;
     }
@@ -1065,7 +1062,7 @@ __global__ void __launch_bounds__(TH) group_scatter_kernel(const uint32_t* __res
     const int64_t k = wbase + (int64_t)i * 64 + l;
     if (k < n) {
       const uint32_t d = key[i] & (NB - 1);
-      const uint32_t lp = (uint32_t)lexcl[d] + (uint32_t)cnt[w][d] + rank[i];
+      const uint32_t lp = scatter_slot(lexcl, cnt[w], d, rank[i]);
       skey[lp] = key[i];
       sval[lp] = val[i];
     }
@@ -1077,7 +1074,7 @@ __global__ void __launch_bounds__(TH) group_scatter_kernel(const uint32_t* __res
     const int j = i * TH + (int)threadIdx.x;
     if (j < nvalid) {
       const uint32_t kk = skey[j], d = kk & (NB - 1);
-      const uint32_t pos = gbase[d] + ((uint32_t)j - (uint32_t)lexcl[d]);
+      const uint32_t pos = write_out_pos(gbase, lexcl, d, j);
       keys_out[pos] = kk;
       vals_out[pos] = sval[j];
     }
@@ -1360,6 +1357,13 @@ static void launch_chunks(hipStream_t s, const Binning& b, const GroupArgs& a) {
 }
 
 static int64_t checkpoint_state_words(const Image& im);
+// The work list of the blend kernels.  `grouped` != null: K5 too, from the grouped path's tile totals, as two blocks side by
+// side; null: one block over the ranges that exist already (see tile_worklist_kernel).
+static void launch_worklist(hipStream_t s, int gx, int gy, const Image& im, const Binning* grouped) {
+  hipLaunchKernelGGL(tile_worklist_kernel, dim3(grouped ? 2 : 1), dim3(1024), 0, s, gx * gy, im.ranges, im.work_order, im.work_meta,
+                     im.queue_heads, im.work_est, grouped ? (const uint32_t*)grouped->tile_total : (const uint32_t*)nullptr,
+                     grouped ? grouped->tile_start : (uint32_t*)nullptr, im.ck_table, (uint32_t)ck_tiles((size_t)gx * gy));
+}
 template <int BITS>
 static void launch_grouped(hipStream_t s, int P, int64_t R, int gx, int gy, const Geom& g, const Binning& b, const Image& im) {
   const int nbg = (P + GAUSS_BLOCK - 1) / GAUSS_BLOCK;
@@ -1367,22 +1371,15 @@ static void launch_grouped(hipStream_t s, int P, int64_t R, int gx, int gy, cons
   const int fill_blocks = 512;  // (two per CU: 5 MB of padding at 1 M Gaussians)
   hipLaunchKernelGGL(emit_groups_kernel, dim3(nbg + fill_blocks), dim3(GAUSS_BLOCK), 0, s, P, b.sgx, g, b.gkey[0], b.gval[0], nbg,
                      b.gkey[1], padded, reinterpret_cast<uint4*>(im.ck_work), checkpoint_state_words(im) / 4);
-  const bool wide = b.sort_blocks <= SORT_WIDE_MAX_BLOCKS;  // few blocks: 1024 threads per block (see radix_sort_pairs)
-  if (wide)
-    hipLaunchKernelGGL((group_hist_kernel<BITS, 1024>), dim3(b.sort_blocks), dim3(1024), 0, s, (const uint32_t*)b.gkey[0], b.G,
-                       b.ghist, b.sort_blocks, b.gkey[1], padded);
-  else
-    hipLaunchKernelGGL((group_hist_kernel<BITS, SORT_THREADS>), dim3(b.sort_blocks), dim3(SORT_THREADS), 0, s,
-                       (const uint32_t*)b.gkey[0], b.G, b.ghist, b.sort_blocks, b.gkey[1], padded);
-  hipLaunchKernelGGL(sort_scan_kernel, dim3(1 << BITS), dim3(SORT_THREADS), 0, s, b.ghist, b.gbin_total, b.sort_blocks);
-  if (wide)
-    hipLaunchKernelGGL((group_scatter_kernel<BITS, 1024>), dim3(b.sort_blocks), dim3(1024), 0, s, (const uint32_t*)b.gkey[0],
-                       (const uint32_t*)b.gval[0], b.gkey[1], b.gval[1], b.G, (const uint32_t*)b.ghist,
-                       (const uint32_t*)b.gbin_total, b.sort_blocks, (uint32_t)b.chunk, b.group_first);
-  else
-    hipLaunchKernelGGL((group_scatter_kernel<BITS, SORT_THREADS>), dim3(b.sort_blocks), dim3(SORT_THREADS), 0, s,
-                       (const uint32_t*)b.gkey[0], (const uint32_t*)b.gval[0], b.gkey[1], b.gval[1], b.G, (const uint32_t*)b.ghist,
-                       (const uint32_t*)b.gbin_total, b.sort_blocks, (uint32_t)b.chunk, b.group_first);
+  with_sort_width(b.sort_blocks, [&](auto th) {
+    constexpr int TH = decltype(th)::value;
+    const dim3 grid(b.sort_blocks), block(TH);
+    hipLaunchKernelGGL((group_hist_kernel<BITS, TH>), grid, block, 0, s, (const uint32_t*)b.gkey[0], b.G, b.ghist, b.sort_blocks);
+    hipLaunchKernelGGL(sort_scan_kernel, dim3(1 << BITS), dim3(SORT_THREADS), 0, s, b.ghist, b.gbin_total, b.sort_blocks);
+    hipLaunchKernelGGL((group_scatter_kernel<BITS, TH>), grid, block, 0, s, (const uint32_t*)b.gkey[0], (const uint32_t*)b.gval[0],
+                       b.gkey[1], b.gval[1], b.G, (const uint32_t*)b.ghist, (const uint32_t*)b.gbin_total, b.sort_blocks,
+                       (uint32_t)b.chunk, b.group_first);
+  });
   GroupArgs a;
   a.gx = gx; a.gy = gy; a.sgx = b.sgx; a.chunks = (size_t)b.chunks;
   // stage of the scatter pass: a whole chunk's entries when they fit 1024 (8 KB of LDS: 20 waves per CU), else 2048
@@ -1392,15 +1389,24 @@ static void launch_grouped(hipStream_t s, int P, int64_t R, int gx, int gy, cons
   launch_chunks<false>(s, b, a);
   hipLaunchKernelGGL(group_colscan_kernel, dim3(b.groups), dim3(COLSCAN_WAVES * 64), 0, s, gx, gy, b.sgx,
                      (const uint32_t*)b.group_first, (const uint16_t*)b.chunk_cnt, b.chunk_pre, b.tile_total);
-  hipLaunchKernelGGL(tile_worklist_kernel, dim3(2), dim3(1024), 0, s, gx * gy, im.ranges, im.work_order, im.work_meta,
-                     im.queue_heads, im.work_est, (const uint32_t*)b.tile_total, b.tile_start, im.ck_table,
-                     (uint32_t)ck_tiles((size_t)gx * gy));
+  launch_worklist(s, gx, gy, im, &b);
   launch_chunks<true>(s, b, a);
 }
 
 // The words between Image::ck_work and the end of Image::tile_maxc (work split, walk depths: contiguous sections).
 static int64_t checkpoint_state_words(const Image& im) {
   return (int64_t)((reinterpret_cast<const char*>(im.ck_pool) - reinterpret_cast<const char*>(im.ck_work)) / 4);
+}
+
+// Legacy path: (tile id, Gaussian) pairs with keys of type K, emitted in depth order, sorted by tile id; K5 on the sorted keys.
+template <class K>
+static void launch_pair_sort(hipStream_t s, int P, int64_t R, int gx, int gy, const Geom& g, const Binning& b, const Image& im) {
+  const int nbg = (P + GAUSS_BLOCK - 1) / GAUSS_BLOCK;
+  const dim3 ge(max(nbg, (gx * gy + GAUSS_BLOCK - 1) / GAUSS_BLOCK)), gr((unsigned)((R + 256 * RANGE_PER - 1) / (256 * RANGE_PER)));
+  K* const tk[2] = {(K*)b.tkey[0], (K*)b.tkey[1]};
+  hipLaunchKernelGGL(emit_keys_kernel<K>, ge, dim3(GAUSS_BLOCK), 0, s, P, gx, gx * gy, g, tk[0], b.vals[0], im.ranges);
+  radix_sort_pairs<K>(s, tk, b.vals, R, b.passes, b.digit_bits, b.hist, b.bin_total, false);
+  hipLaunchKernelGGL(tile_ranges_kernel<K>, gr, dim3(256), 0, s, R, (const K*)tk[b.final_buf], im.ranges);
 }
 
 hipError_t launch_binning(hipStream_t s, int P, int64_t R, int W, int H, const Geom& g, const Binning& b, const Image& im) {
@@ -1412,9 +1418,7 @@ hipError_t launch_binning(hipStream_t s, int P, int64_t R, int W, int H, const G
   if (R <= 0) {
     hipError_t e = hipMemsetAsync(im.ranges, 0, sizeof(uint2) * (size_t)gx * gy, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(tile_worklist_kernel, dim3(1), dim3(1024), 0, s, gx * gy, im.ranges, im.work_order, im.work_meta,
-                       im.queue_heads, im.work_est, (const uint32_t*)nullptr, (uint32_t*)nullptr, im.ck_table,
-                       (uint32_t)ck_tiles((size_t)gx * gy));
+    launch_worklist(s, gx, gy, im, nullptr);
     return hipGetLastError();
   }
   if (!b.legacy) {
@@ -1422,22 +1426,9 @@ hipError_t launch_binning(hipStream_t s, int P, int64_t R, int W, int H, const G
     else launch_grouped<11>(s, P, R, gx, gy, g, b, im);
     return hipGetLastError();
   }
-  const int nbg = (P + GAUSS_BLOCK - 1) / GAUSS_BLOCK;
-  const dim3 ge(max(nbg, (gx * gy + GAUSS_BLOCK - 1) / GAUSS_BLOCK)), gr((unsigned)((R + 256 * RANGE_PER - 1) / (256 * RANGE_PER)));
-  if (b.key_bytes == 2) {  // tile ids fit 16 bits: 6 instead of 8 bytes per sorted pair
-    uint16_t* const tk[2] = {(uint16_t*)b.tkey[0], (uint16_t*)b.tkey[1]};
-    hipLaunchKernelGGL(emit_keys_kernel<uint16_t>, ge, dim3(GAUSS_BLOCK), 0, s, P, gx, gx * gy, g, tk[0], b.vals[0], im.ranges);
-    radix_sort_pairs<uint16_t>(s, tk, b.vals, R, b.passes, b.digit_bits, b.hist, b.bin_total, false);
-    hipLaunchKernelGGL(tile_ranges_kernel<uint16_t>, gr, dim3(256), 0, s, R, (const uint16_t*)tk[b.final_buf], im.ranges);
-  } else {
-    uint32_t* const tk[2] = {(uint32_t*)b.tkey[0], (uint32_t*)b.tkey[1]};
-    hipLaunchKernelGGL(emit_keys_kernel<uint32_t>, ge, dim3(GAUSS_BLOCK), 0, s, P, gx, gx * gy, g, tk[0], b.vals[0], im.ranges);
-    radix_sort_pairs<uint32_t>(s, tk, b.vals, R, b.passes, b.digit_bits, b.hist, b.bin_total, false);
-    hipLaunchKernelGGL(tile_ranges_kernel<uint32_t>, gr, dim3(256), 0, s, R, (const uint32_t*)tk[b.final_buf], im.ranges);
-  }
-  hipLaunchKernelGGL(tile_worklist_kernel, dim3(1), dim3(1024), 0, s, gx * gy, im.ranges, im.work_order, im.work_meta,
-                     im.queue_heads, im.work_est, (const uint32_t*)nullptr, (uint32_t*)nullptr, im.ck_table,
-                     (uint32_t)ck_tiles((size_t)gx * gy));
+  if (b.key_bytes == 2) launch_pair_sort<uint16_t>(s, P, R, gx, gy, g, b, im);  // tile ids fit 16 bits: 6 instead of 8 bytes per sorted pair
+  else launch_pair_sort<uint32_t>(s, P, R, gx, gy, g, b, im);
+  launch_worklist(s, gx, gy, im, nullptr);
   return hipGetLastError();
 }
 
@@ -1463,6 +1454,10 @@ __global__ void __launch_bounds__(256) export_keys_grouped_kernel(int64_t R, uin
   }
   keys[i] = ((uint64_t)lo << 32) | (uint64_t)__float_as_uint(rec1[vals[i]].z);
 }
+template <class K>
+static void launch_export_pairs(hipStream_t s, dim3 grid, int64_t R, const Binning& b, const Geom& g, uint64_t* keys) {
+  hipLaunchKernelGGL(export_keys_kernel<K>, grid, dim3(256), 0, s, R, (const K*)b.tkey[b.final_buf], b.vals[b.final_buf], g.rec1, keys);
+}
 hipError_t launch_export_keys(hipStream_t s, int64_t R, int W, int H, const Binning& b, const Geom& g, uint64_t* keys) {
   const dim3 grid((unsigned)((R + 255) / 256));
   if (!b.legacy) {
@@ -1470,11 +1465,9 @@ hipError_t launch_export_keys(hipStream_t s, int64_t R, int W, int H, const Binn
     hipLaunchKernelGGL(export_keys_grouped_kernel, grid, dim3(256), 0, s, R, T, (const uint32_t*)b.tile_start,
                        (const uint32_t*)b.point_list, g.rec1, keys);
   } else if (b.key_bytes == 2) {
-    hipLaunchKernelGGL(export_keys_kernel<uint16_t>, grid, dim3(256), 0, s, R, (const uint16_t*)b.tkey[b.final_buf],
-                       b.vals[b.final_buf], g.rec1, keys);
+    launch_export_pairs<uint16_t>(s, grid, R, b, g, keys);
   } else {
-    hipLaunchKernelGGL(export_keys_kernel<uint32_t>, grid, dim3(256), 0, s, R, (const uint32_t*)b.tkey[b.final_buf],
-                       b.vals[b.final_buf], g.rec1, keys);
+    launch_export_pairs<uint32_t>(s, grid, R, b, g, keys);
   }
   return hipGetLastError();
 }

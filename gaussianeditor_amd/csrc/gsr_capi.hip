@@ -479,7 +479,7 @@ int preprocess_end_impl(hipStream_t s, int P, int W, int H, void* geom, HostSlot
   if (legacy) {
     const int passes = nbits <= 16 ? 2 : (nbits + 7) / 8;
     if (passes > 2) GSR_HIP(launch_depth_passes(s, P, g, 2, passes));
-    GSR_HIP(launch_depth_finish(s, P, g, passes, gx, 0));
+    GSR_HIP(launch_depth_finish(s, P, g, passes, gx));
   } else {
     // The LAST pass also leaves what the emission of gsr_bin needs (depth_scatter_kernel<true>), and which pass that is
     // is only known now: at least one pass follows the two that ran under the wait (a key range of <= 16 bits: its

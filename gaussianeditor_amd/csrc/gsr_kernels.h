@@ -151,15 +151,17 @@ hipError_t launch_export_geom(hipStream_t s, int P, const Geom& g, float* means2
                               float* conic_opacity, uint32_t* tiles_touched, uint8_t* clamped);
 hipError_t launch_depth_passes(hipStream_t s, int P, const Geom& g, int p0, int p1, uint32_t* publish_dst = nullptr,
                                uint32_t publish_seq = 0);
-// sgx: groups per row when the grouped binning path follows (the depth-ordered rectangles are then group rectangles), 0 for
-// the legacy pair sort
-hipError_t launch_depth_finish(hipStream_t s, int P, const Geom& g, int passes, int gx, int sgx);
+// Legacy pair sort only: the tile rectangles gathered into depth order + the prefix of their tile counts.
+hipError_t launch_depth_finish(hipStream_t s, int P, const Geom& g, int passes, int gx);
 // Grouped path: the same passes carrying the packed tile rectangle; `last`: pass p1 - 1 is the final one and leaves the
 // depth order, the rectangles in that order and every Gaussian's first slot of the emission (no launch_depth_finish).
 hipError_t launch_depth_passes_grouped(hipStream_t s, int P, const Geom& g, int p0, int p1, bool last,
                                        uint32_t* publish_dst = nullptr, uint32_t publish_seq = 0);
 hipError_t launch_export_keys(hipStream_t s, int64_t R, int W, int H, const Binning& b, const Geom& g, uint64_t* keys);
 hipError_t launch_binning(hipStream_t s, int P, int64_t R, int W, int H, const Geom& g, const Binning& b, const Image& im);
+// The binning's stable LSD radix sort of (key, value) pairs, for the other translation units (gsr_knn.hip).
+void radix_sort_pairs_u32(hipStream_t s, uint32_t* const keys[2], uint32_t* const vals[2], int64_t n, int npass,
+                          const int* digit_bits, uint32_t* hist, uint32_t* bin_total, bool iota_first);
 size_t knn_workspace_bytes(int P);
 hipError_t launch_knn(hipStream_t s, int P, const float* points, void* workspace, float* out);
 hipError_t launch_near_points(hipStream_t s, int n_ref, const float* ref, int n_query, const float* query, float thresh,

@@ -218,9 +218,6 @@ __global__ void __launch_bounds__(256) knn_search_kernel(int P, const float4* __
   dists[order[idx]] = (best[0] + best[1] + best[2]) / 3.0f;
 }
 
-void radix_sort_pairs_u32(hipStream_t s, uint32_t* const keys[2], uint32_t* const vals[2], int64_t n, int npass,
-                          const int* digit_bits, uint32_t* hist, uint32_t* bin_total, bool iota_first);  // gsr_binning.hip
-
 size_t knn_workspace_bytes(int P) { return carve_knn(nullptr, P).bytes; }
 
 // bounds -> Morton codes -> sort -> gather -> boxes over `points`; leaves w.sorted / w.val[0] / w.boxes

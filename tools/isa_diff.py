@@ -11,11 +11,42 @@ basic-block label numbers (.LBB<n>_) are normalised, and the --rename pairs are 
 (a template parameter that went away changes the mangled name and nothing else).  Prints identical / different /
 only-in-old / only-in-new per unit; the exit status is non-zero on any "different" or "only-in-new".  Needs hipcc and no
 GPU; about 25 s per unit.
+
+--commutative adds a class between identical and different: kernels that differ ONLY in the order of the two source
+operands of the integer opcodes in COMMUTATIVE (a helper that takes a pointer where the text indexed an array makes the
+compiler state `v_and_b32 v1, v79, v78` as `v1, v78, v79`; in the SDWA encoding a source moves together with its
+src<n>_sel).  Everything else still has to match line for line: the
+number of lines, every opcode, every destination register, every other instruction and the .amdhsa_ descriptor.  Such
+kernels are printed as "commutative" and do not count towards the exit status.  No floating-point opcode is in the set.
 """
 import argparse, concurrent.futures, os, re, shlex, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = "gaussianeditor_amd/csrc"
+
+
+# two-source integer opcodes whose result does not depend on the order of the sources
+COMMUTATIVE = ("v_and_b32", "v_or_b32", "v_xor_b32", "v_add_u32", "s_and_b32", "s_and_b64", "s_or_b32", "s_or_b64", "s_xor_b32",
+               "s_xor_b64", "s_add_u32")
+_COMMUTATIVE_RE = re.compile(r"^((?:%s)(?:_e32|_e64)?)\s+([^,\s]+),\s*([^,\s]+),\s*([^,\s]+)$" % "|".join(COMMUTATIVE))
+# the same opcodes in their SDWA encoding: every source carries its sub-dword selector with it
+_COMMUTATIVE_SDWA_RE = re.compile(r"^((?:%s)_sdwa)\s+([^,\s]+),\s*([^,\s]+),\s*([^,\s]+)((?:\s+dst_\w+:\w+)*)"
+                                  r"\s+src0_sel:(\w+)\s+src1_sel:(\w+)$" % "|".join(COMMUTATIVE))
+
+
+def sort_commutative(body):
+    """The lines of one function with the two sources of every plain COMMUTATIVE instruction in sorted order."""
+    out = []
+    for text in body:
+        m = _COMMUTATIVE_RE.match(text)  # (an instruction with a source modifier, a third operand or another suffix stays as it is)
+        if m:
+            text = "%s %s, %s, %s" % ((m.group(1), m.group(2)) + tuple(sorted(m.group(3, 4))))
+        m = _COMMUTATIVE_SDWA_RE.match(text)
+        if m:
+            (a, sa), (b, sb) = sorted([(m.group(3), m.group(6)), (m.group(4), m.group(7))])
+            text = "%s %s, %s, %s%s src0_sel:%s src1_sel:%s" % (m.group(1), m.group(2), a, b, m.group(5), sa, sb)
+        out.append(text)
+    return out
 
 
 def unit_commands(tree):
@@ -63,6 +94,7 @@ def main():
     ap.add_argument("--old-rev", default="HEAD~1", help="git revision of the old tree (default HEAD~1)")
     ap.add_argument("--new", default=ROOT, help="new source tree (default: the working tree)")
     ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW", help="mangled-name fragment that changed")
+    ap.add_argument("--commutative", action="store_true", help="report kernels that differ only in the source order of COMMUTATIVE opcodes apart")
     ap.add_argument("--jobs", type=int, default=min(8, os.cpu_count() or 1))
     args = ap.parse_args()
     renames = [tuple(r.split("=", 1)) for r in args.rename]
@@ -86,10 +118,13 @@ def main():
                 a = jobs[0, u].result() if (0, u) in jobs else {}
                 b = jobs[1, u].result() if (1, u) in jobs else {}
                 different = sorted(k for k in a if k in b and a[k] != b[k])
+                swapped = [k for k in different if args.commutative and sort_commutative(a[k]) == sort_commutative(b[k])]
+                different = [k for k in different if k not in swapped]
                 gone, new = sorted(set(a) - set(b)), sorted(set(b) - set(a))
-                same = len(set(a) & set(b)) - len(different)
-                print(f"{u}.hip: {same} identical, {len(different)} different, {len(gone)} only-in-old, {len(new)} only-in-new")
-                for tag, names in (("different", different), ("only-in-old", gone), ("only-in-new", new)):
+                same = len(set(a) & set(b)) - len(different) - len(swapped)
+                print(f"{u}.hip: {same} identical, " + (f"{len(swapped)} commutative, " if args.commutative else "")
+                      + f"{len(different)} different, {len(gone)} only-in-old, {len(new)} only-in-new")
+                for tag, names in (("commutative", swapped), ("different", different), ("only-in-old", gone), ("only-in-new", new)):
                     for k in names:
                         print(f"  {tag}: {k}")
                 bad += len(different) + len(new)
