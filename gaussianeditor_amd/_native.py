@@ -168,6 +168,8 @@ SIGNATURES = {
     # ALPHA << 4; (stream, W, H, image, counts[2] = {items, list-segment items} of the latest backward's work list)
     "gsr_debug_blend_backward_launches": (c_int, [POINTER(ctypes.c_uint64)]),
     "gsr_debug_blend_backward_items": (c_int, [_P, c_int, c_int, _P, POINTER(c_int64)]),
+    # which radix scatter ran (host-side bookkeeping): (counts[24]), index layout at the declaration in include/gsr.h
+    "gsr_debug_sort_launches": (c_int, [POINTER(ctypes.c_uint64)]),
     # the fused L1 + SSIM loss (gaussianeditor_amd/losses.py): (planes, H, W, bytes);
     # (stream, planes, H, W, img, gt, w_l1, w_ssim, c, maps | NULL, workspace, out3);
     # (stream, planes, H, W, img, gt, maps, w_l1, w_ssim, dL_dloss, dL_dimg)

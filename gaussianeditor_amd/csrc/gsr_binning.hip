@@ -32,8 +32,10 @@
 // algorithm with different payloads: its pieces -- the ballot ranking, the per-digit prefix over the
 // waves, the slot in LDS, the position of the write-out -- are defined once, in "The stable radix
 // scatter" below; on the host, with_sort_width picks the block width of every sort.
+#include <limits.h>
 #include <stdlib.h>
 
+#include <atomic>
 #include <type_traits>
 
 #include "gsr_kernels.h"
@@ -329,12 +331,40 @@ __global__ void __launch_bounds__(TH) sort_scatter_kernel(const K* __restrict__ 
 // with 1024 threads a block's 4096 keys are ranked by 16 waves in 4 rounds instead of by 4 waves in 16.  Many-block sorts
 // keep 256 threads (more blocks resident per CU).
 constexpr uint32_t SORT_WIDE_MAX_BLOCKS = 1024;
-static bool sort_is_wide(uint32_t nblocks) { return nblocks <= SORT_WIDE_MAX_BLOCKS; }
+// GSR_SORT_THREADS=256|1024 (tests) gives every sort of the process that width, whatever its block count: both widths are
+// correct for any size, and the narrow one is otherwise reached only by sorts of more than 4 194 304 keys.  0: not set
+// (any other value counts as not set).
+static int sort_width_knob() {
+  static const int forced = [] {
+    const int v = env_knob("GSR_SORT_THREADS", 0, 0, INT_MAX);
+    return (v == SORT_THREADS || v == 1024) ? v : 0;
+  }();
+  return forced;
+}
+static bool sort_is_wide(uint32_t nblocks) {
+  const int forced = sort_width_knob();
+  return forced != 0 ? forced == 1024 : nblocks <= SORT_WIDE_MAX_BLOCKS;
+}
 // f(TH) with the block width of a sort of `nblocks` blocks as a compile-time constant: decltype(th)::value
 template <class F>
 static void with_sort_width(uint32_t nblocks, F&& f) {
   if (sort_is_wide(nblocks)) f(std::integral_constant<int, 1024>{});
   else f(std::integral_constant<int, SORT_THREADS>{});
+}
+// Host-side launch counts of the scatter kernels per instantiation and of the scan's carry round (gsr_debug_sort_launches;
+// the index layout is stated at its declaration in include/gsr.h); relaxed: renders run from several host threads and
+// nothing is ordered by the counts.
+constexpr int SORT_COUNT_SCATTER = 0, SORT_COUNT_DEPTH = 8, SORT_COUNT_GROUP = 16, SORT_COUNT_SCAN_CARRY = 20, SORT_COUNTS = 24;
+static std::atomic<uint64_t> g_sort_launches[SORT_COUNTS];
+static void count_sort_launch(int index) { g_sort_launches[index].fetch_add(1, std::memory_order_relaxed); }
+void sort_launch_counts(uint64_t counts[24]) {
+  for (int i = 0; i < SORT_COUNTS; ++i) counts[i] = g_sort_launches[i].load(std::memory_order_relaxed);
+}
+// The per-bin scan of a radix pass: `bins` rows of `nblocks` counts.  Rows longer than one round of the block
+// (SORT_THREADS * SCAN_PER counts) take further rounds, each behind the carry of the rounds before it.
+static void launch_sort_scan(hipStream_t s, uint32_t bins, uint32_t* hist, uint32_t* bin_total, uint32_t nblocks) {
+  hipLaunchKernelGGL(sort_scan_kernel, dim3(bins), dim3(SORT_THREADS), 0, s, hist, bin_total, nblocks);
+  if (nblocks > (uint32_t)(SORT_THREADS * SCAN_PER)) count_sort_launch(SORT_COUNT_SCAN_CARRY);
 }
 // f(flag) with a run-time choice between two instantiations as a compile-time constant
 template <class F>
@@ -357,10 +387,12 @@ static void radix_sort_pairs_th(hipStream_t s, K* const keys[2], uint32_t* const
     hipLaunchKernelGGL((sort_hist_kernel<K, TH>), dim3(nblocks + (pub ? 1u : 0u)), dim3(TH), 0, s, (const K*)keys[cur], n, shift, mask,
                        hist, nblocks, pub ? publish_src : nullptr, publish_count, pub ? publish_dst : nullptr, publish_seq,
                        (const uint32_t*)nullptr);
-    hipLaunchKernelGGL(sort_scan_kernel, dim3(RBINS), dim3(SORT_THREADS), 0, s, hist, bin_total, nblocks);
+    launch_sort_scan(s, RBINS, hist, bin_total, nblocks);
     with_flag(p == 0 && iota_first, [&](auto iota) {
-      hipLaunchKernelGGL((sort_scatter_kernel<decltype(iota)::value, K, TH>), dim3(nblocks), dim3(TH), 0, s, (const K*)keys[cur],
+      constexpr bool IOTA = decltype(iota)::value;
+      hipLaunchKernelGGL((sort_scatter_kernel<IOTA, K, TH>), dim3(nblocks), dim3(TH), 0, s, (const K*)keys[cur],
                          (const uint32_t*)vals[cur], keys[cur ^ 1], vals[cur ^ 1], n, shift, mask, hist, bin_total, nblocks);
+      count_sort_launch(SORT_COUNT_SCATTER + (IOTA ? 1 : 0) + (std::is_same<K, uint32_t>::value ? 2 : 0) + (TH == 1024 ? 4 : 0));
     });
     shift += digit_bits[p];
     cur ^= 1;
@@ -552,12 +584,14 @@ static void depth_sort_grouped_th(hipStream_t s, int P, const Geom& g, int p0, i
       hipLaunchKernelGGL((sort_hist_kernel<uint32_t, 1024, LASTP>), gh, bh, 0, s, (const uint32_t*)g.dkey[cur], n, shift, 255u, g.ghist,
                          nblocks, pub ? g.k1_partials : nullptr, npart, pub ? publish_dst : nullptr, publish_seq,
                          LASTP ? (const uint32_t*)g.drect[cur] : (const uint32_t*)nullptr);
-      hipLaunchKernelGGL(sort_scan_kernel, dim3(LASTP ? 2 * RBINS : RBINS), dim3(SORT_THREADS), 0, s, g.ghist, g.gbin_total, nblocks);
+      launch_sort_scan(s, LASTP ? 2 * RBINS : RBINS, g.ghist, g.gbin_total, nblocks);
       with_flag(p == 0, [&](auto iotap) {
-        hipLaunchKernelGGL((depth_scatter_kernel<LASTP, decltype(iotap)::value, TH>), gs, bt, 0, s, (const uint32_t*)g.dkey[cur],
+        constexpr bool IOTA = decltype(iotap)::value;
+        hipLaunchKernelGGL((depth_scatter_kernel<LASTP, IOTA, TH>), gs, bt, 0, s, (const uint32_t*)g.dkey[cur],
                            (const uint32_t*)g.dval[cur], (const uint32_t*)g.drect[cur], (const uint2*)g.rect, g.dkey[cur ^ 1],
                            g.dval[cur ^ 1], g.drect[cur ^ 1], n, shift, 255u, (const uint32_t*)g.ghist,
                            (const uint32_t*)g.gbin_total, nblocks, hdr, (uint32_t)(cur ^ 1));
+        count_sort_launch(SORT_COUNT_DEPTH + (LASTP ? 1 : 0) + (IOTA ? 2 : 0) + (TH == 1024 ? 4 : 0));
       });
     });
   }
@@ -1375,10 +1409,11 @@ static void launch_grouped(hipStream_t s, int P, int64_t R, int gx, int gy, cons
     constexpr int TH = decltype(th)::value;
     const dim3 grid(b.sort_blocks), block(TH);
     hipLaunchKernelGGL((group_hist_kernel<BITS, TH>), grid, block, 0, s, (const uint32_t*)b.gkey[0], b.G, b.ghist, b.sort_blocks);
-    hipLaunchKernelGGL(sort_scan_kernel, dim3(1 << BITS), dim3(SORT_THREADS), 0, s, b.ghist, b.gbin_total, b.sort_blocks);
+    launch_sort_scan(s, 1u << BITS, b.ghist, b.gbin_total, b.sort_blocks);
     hipLaunchKernelGGL((group_scatter_kernel<BITS, TH>), grid, block, 0, s, (const uint32_t*)b.gkey[0], (const uint32_t*)b.gval[0],
                        b.gkey[1], b.gval[1], b.G, (const uint32_t*)b.ghist, (const uint32_t*)b.gbin_total, b.sort_blocks,
                        (uint32_t)b.chunk, b.group_first);
+    count_sort_launch(SORT_COUNT_GROUP + (BITS == 11 ? 1 : 0) + (TH == 1024 ? 2 : 0));
   });
   GroupArgs a;
   a.gx = gx; a.gy = gy; a.sgx = b.sgx; a.chunks = (size_t)b.chunks;

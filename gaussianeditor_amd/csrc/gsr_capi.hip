@@ -1361,6 +1361,12 @@ int gsr_debug_blend_backward_launches(uint64_t* counts) {
   return GSR_OK;
 }
 
+int gsr_debug_sort_launches(uint64_t* counts) {
+  if (!counts) return GSR_ERR_BAD_ARGUMENT;
+  sort_launch_counts(counts);
+  return GSR_OK;
+}
+
 int gsr_debug_blend_backward_items(void* stream, int W, int H, const void* image, int64_t* counts) {
   if (!image || !counts || W <= 0 || H <= 0) return GSR_ERR_BAD_ARGUMENT;
   const size_t T = (size_t)((W + TILE - 1) / TILE) * ((H + TILE - 1) / TILE);

@@ -469,6 +469,8 @@ __device__ __forceinline__ uint32_t block_excl_scan_u32(uint32_t v, uint32_t* bl
 // The library's environment knobs, all of them (tests and bench.py set them; none is needed in normal use).  Each is read
 // once per process, at its first use:
 //   GSR_BIN_LEGACY=1            the two-pass pair sort for every image size (gsr_capi.hip: bin_legacy)
+//   GSR_SORT_THREADS=256|1024   that block width for every radix sort, whatever its size (gsr_binning.hip: with_sort_width);
+//                               any other value counts as unset: 1024 for sorts of up to 1024 blocks, 256 beyond
 //   GSR_CK_CHUNKS=n             checkpoint stride in 64-entry chunks, uniform table; 0 = no checkpoints; unset: by list length
 //   GSR_CK_DEBUG=1              lets GSR_CK_CHUNKS go below 4 (gsr_capi.hip: checkpoint_chunks)
 //   GSR_CK_SLOTS=n              checkpoint slots in use per tile, 2 .. CK_MAX (default CK_MAX)

@@ -162,6 +162,9 @@ hipError_t launch_binning(hipStream_t s, int P, int64_t R, int W, int H, const G
 // The binning's stable LSD radix sort of (key, value) pairs, for the other translation units (gsr_knn.hip).
 void radix_sort_pairs_u32(hipStream_t s, uint32_t* const keys[2], uint32_t* const vals[2], int64_t n, int npass,
                           const int* digit_bits, uint32_t* hist, uint32_t* bin_total, bool iota_first);
+// debug (host only): launches of the radix scatter kernels per instantiation in this process (include/gsr.h:
+// gsr_debug_sort_launches states the index layout)
+void sort_launch_counts(uint64_t counts[24]);
 size_t knn_workspace_bytes(int P);
 hipError_t launch_knn(hipStream_t s, int P, const float* points, void* workspace, float* out);
 hipError_t launch_near_points(hipStream_t s, int n_ref, const float* ref, int n_query, const float* query, float thresh,

@@ -28,8 +28,9 @@
  *     call as `flags`); the only thing it owns is a small pool of 8 KiB pinned host buffers, one checked out per host
  *     thread and device, through which gsr_preprocess receives its counts (the device writes them, the host polls).
  *   - tuning / experiment knobs are environment variables read ONCE per process, none of which changes any result
- *     (launch geometry of the persistent blend kernels, work-list ordering, and GSR_BIN_LEGACY=1,
- *     which sends every image down the tile-pair sort that otherwise only images beyond 131 072 tiles take); they are
+ *     (launch geometry of the persistent blend kernels, work-list ordering, GSR_BIN_LEGACY=1,
+ *     which sends every image down the tile-pair sort that otherwise only images beyond 131 072 tiles take, and
+ *     GSR_SORT_THREADS=256|1024, which gives every radix sort the block width that otherwise its size decides); they are
  *     listed in DESIGN.md section 3.3 and are not part of this ABI.
  *   - an absent optional input is a NULL pointer (the reference uses empty
  *     tensors for the same purpose, diff_gaussian_rasterization/__init__.py:285-295).
@@ -875,6 +876,24 @@ int gsr_debug_blend_forward_profile(void* stream, int P, int64_t R, int W, int H
  * (no blend backward has run on it). */
 int gsr_debug_blend_backward_launches(uint64_t* counts);
 int gsr_debug_blend_backward_items(void* stream, int W, int H, const void* image, int64_t* counts);
+
+/* Which radix scatter did the binning run?  Host-side bookkeeping for the tests: nothing is launched.
+ * gsr_debug_sort_launches: counts[24] (HOST) receives how often this process has launched the stable scatter kernels of
+ * gsr_binning.hip so far, per instantiation.  TH is the block width of the sort: 1024 for sorts of up to 1024 blocks of
+ * 4096 keys, 256 beyond, or what GSR_SORT_THREADS says for every sort of the process (depth order, group instances, tile
+ * pairs, gsr_knn's and gsr_near's Morton codes).
+ *    0 ..  7  sort_scatter_kernel<IOTA, K, TH>      IOTA | (K is uint32_t) << 1 | (TH == 1024) << 2
+ *             (the tile-pair sort, 16- or 32-bit tile ids, IOTA never; the depth order of the pair-sort path and the
+ *              Morton sort: K = uint32_t, IOTA in their first pass.  IOTA with 16-bit keys is never launched: 1 and 5 stay 0)
+ *    8 .. 15  depth_scatter_kernel<LAST, IOTA, TH>  LAST | IOTA << 1 | (TH == 1024) << 2
+ *             (the grouped path's depth order: three or four passes, so LAST & IOTA is never launched: 11 and 15 stay 0)
+ *   16 .. 19  group_scatter_kernel<BITS, TH>        (BITS == 11) | (TH == 1024) << 1
+ *   20        launches of sort_scan_kernel whose rows exceed one round of its block (more than 2048 blocks, i.e. more than
+ *             8 388 608 keys): the rounds behind the first start from a carry
+ *   21 .. 23  zero
+ * Counted where the instantiation is chosen, with relaxed atomics (renders may run from several host threads).
+ * GSR_ERR_BAD_ARGUMENT for NULL. */
+int gsr_debug_sort_launches(uint64_t* counts);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

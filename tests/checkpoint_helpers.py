@@ -32,7 +32,7 @@ FINE_POS = tuple(64 * c for c in (0, 4, 8, 12, 16, 20, 24, 32, 40, 48, 64, 80, 9
 CK_MAX = len(FINE_POS)
 CK_TILES_CAP = 2048
 REGS_TILES = 8192  # above it backward_worklist_kernel re-reads the tiles' counts (in_regs is false)
-KNOBS = ("GSR_CK_CHUNKS", "GSR_CK_SLOTS", "GSR_CK_DEBUG", "GSR_BWD_SEG", "GSR_BIN_LEGACY")
+KNOBS = ("GSR_CK_CHUNKS", "GSR_CK_SLOTS", "GSR_CK_DEBUG", "GSR_BWD_SEG", "GSR_BIN_LEGACY", "GSR_SORT_THREADS")
 BG = (0.2, 0.5, 0.7)
 EDGES = (256, 257, 1536, 1537, 2048, 2049, 16384, 16385)
 ONE_TILE = ("reach", "ragged", "just_on", "just_off") + tuple(f"edge{n}" for n in EDGES) + ("saturating",)

@@ -924,7 +924,7 @@ def test_environment_regimes(regime):
     """One forward and backward cell (P = 257, 130 x 66, num_rendered 6082) with the same three assertions in a fresh
     process per regime, one at a time, each under its own time limit.  With GSR_CK_CHUNKS=1 the lists are cut into
     segments and the checkpoint pool is the last section of the image scratch."""
-    env = {k: v for k, v in os.environ.items() if k not in ("GSR_BIN_LEGACY", "GSR_CK_CHUNKS", "GSR_CK_DEBUG", "GSR_BWD_SEG")}
+    env = {k: v for k, v in os.environ.items() if k not in ("GSR_BIN_LEGACY", "GSR_CK_CHUNKS", "GSR_CK_DEBUG", "GSR_BWD_SEG", "GSR_SORT_THREADS")}
     env.update(REGIMES[regime])
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-x", "-q", "-s", "-k",
                         "test_rasterizer_num_rendered_between_one_and_two_sort_blocks"],

@@ -107,7 +107,7 @@ def _fresh(cmd, env, timeout=600):
 
 def test_seg_rows_in_a_fresh_process(tmp_path):
     base = str(tmp_path / "base_F.npz")
-    env = {k: v for k, v in os.environ.items() if k not in ("GSR_CK_CHUNKS", "GSR_BWD_SEG", "GSR_CK_DEBUG", "GSR_CK_SLOTS")}
+    env = {k: v for k, v in os.environ.items() if k not in ("GSR_CK_CHUNKS", "GSR_BWD_SEG", "GSR_CK_DEBUG", "GSR_CK_SLOTS", "GSR_SORT_THREADS")}
     t0 = time.time()
     p = _fresh([sys.executable, "-c", f"import sys; sys.path[:0] = [{ROOT!r}, {TESTS!r}]; import k7_matrix_helpers as K; "
                 f"K.write_base({base!r})"], dict(env, GSR_CK_CHUNKS="4", GSR_BWD_SEG="0"))

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 from helpers import hip_state, make_case, seed_gradient, settings
+from sort_matrix_helpers import assert_sorted_list_invariants
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -42,24 +43,11 @@ def _forward(case, bg=None):
 def test_full_size_sorted_list_invariants(full_case):
     R, color, depth, radii, geom, binning, img = _forward(full_case)
     st = hip_state(P, R, W, H, geom, binning, img)
-    keys, pl, ranges, tt = st["keys"], st["point_list"].astype(np.int64), st["ranges"].astype(np.int64), st["tiles_touched"]
-    rad = radii.cpu().numpy()
+    tt = st["tiles_touched"]
     assert R == int(tt.astype(np.int64).sum()) and R > 4_000_000
-    assert np.array_equal(tt > 0, rad > 0)                       # tiles only for visible Gaussians, and for every one
-    assert (keys[1:] >= keys[:-1]).all()                           # sorted by (tile, depth bits)
-    ties = keys[1:] == keys[:-1]
-    assert (pl[1:][ties] > pl[:-1][ties]).all()  # equal keys: ascending Gaussian index (stable)
-    assert (rad[pl] > 0).all()
-    # the depth bits of an instance are its Gaussian's depth
-    assert np.array_equal((keys & np.uint64(0xffffffff)).astype(np.uint32), st["depths"][pl].view(np.uint32))
-    # ranges: tile t owns exactly the run of keys with tile id t; empty tiles hold (0, 0); together a partition of [0, R)
-    tile_of = (keys >> np.uint64(32)).astype(np.int64)
-    T = ranges.shape[0]
-    counts = np.bincount(tile_of, minlength=T)
-    starts = np.concatenate(([0], np.cumsum(counts)[:-1]))
-    nonempty = counts > 0
-    assert np.array_equal(ranges[nonempty, 0], starts[nonempty]) and np.array_equal(ranges[nonempty, 1], (starts + counts)[nonempty])
-    assert (ranges[~nonempty] == 0).all() and int(counts.sum()) == R
+    # (sorted by (tile, depth bits), ties in ascending Gaussian index, the ranges the runs of the tile ids and a partition of
+    #  [0, R), the depth bits the Gaussian's depth: shared with tests/test_gpu_sort_matrix.py)
+    counts = assert_sorted_list_invariants(st, R, radii.cpu().numpy())
     # per pixel: the walk never goes past its tile's list; transmittance is a product of factors in (0.01, 1]
     ncon = st["n_contrib"].reshape(H, W).astype(np.int64)
     fT = st["final_T"].reshape(H, W)
