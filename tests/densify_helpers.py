@@ -365,3 +365,135 @@ def densify_and_prune_torch(par, moments, extra, noise_fn, *, max_grad, max_dens
     new_extra = dict(xyz_gradient_accum=torch.zeros((final, 1), device=dev), denom=torch.zeros((final, 1), device=dev),
                      max_radii2D=torch.zeros((final,), device=dev), mask=mask, generation=gen, xyz_bound=side.get("bound"), xyz64=side.get("xyz64"))
     return par, moments, new_extra, (before, n_clone, n_split, n_pruned)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the second size regimes of the row-surgery and policy kernels (tests/test_cpu_size_regimes.py checks that every size
+# below lies where it claims, tests/test_gpu_size_regimes.py runs the kernels there)
+# ----------------------------------------------------------------------------------------------------------------------
+SCAN_EDGE = 1024 * 1024             # rows one trip of compact_scan_kernel covers: 1024 blocks of 1024 rows
+PC = SCAN_EDGE + 1024 + 1           # 1026 row blocks: the scan's second trip holds two, the last with one row
+PD = 1024 * 256 + 257               # 1026 blocks of 256 rows: the densify kernels' grid stride, ragged
+P_APPEND, N_APPEND = 400001, 12345  # (P + n) * 180 bytes > 4096 blocks * 256 threads * 64 bytes
+P_COUNTS = 1025                     # the tensor-count cases: two row blocks, the second with one row
+TENSOR_COUNTS = (33, 65)            # two and three Python chunks of 32 tensors
+ROW_WIDTHS = (1, 3, 4, 12, 16, 20, 180, 2, 8)  # bytes per row, cycled over the tensors of a count case
+
+
+def kernel_constants():
+    """The thresholds the size-regime tests rely on, parsed out of the sources' text: every `constexpr int NAME = value`
+    of the .hip / .h files (names resolved through one another), the step of compact_scan_kernel's carry loop, the grid
+    caps of append_rows_kernel and mcmc_scatter_kernel with append's bytes per block, and the Python chunk of densify.py."""
+    import os
+    import re
+
+    pkg = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gaussianeditor_amd")
+
+    def text(*parts):
+        with open(os.path.join(pkg, *parts)) as f:
+            return f.read()
+
+    src = {n: text("csrc", *n.split("/")) for n in ("gsr_kernels.h", "gsr_common.h", "gsr_compact.hip", "gsr_densify.hip",
+                                                    "gsr_mcmc.hip", "loss/gsr_loss.hip")}
+    raw = {}
+    for body in src.values():
+        for line in re.findall(r"^\s*constexpr\s+int\s+([^;]*);", body, flags=re.M):
+            for part in line.split(","):
+                m = re.fullmatch(r"\s*(\w+)\s*=\s*(\w+)\s*", part)
+                if m:
+                    raw[m.group(1)] = m.group(2)
+
+    def value(name):
+        v = raw[name]
+        return int(v) if v.isdigit() else value(v)
+
+    out = {k: value(k) for k in ("VIEW_MSG_ROWS", "CMP_ROWS", "CMP_MAX_TENSORS", "CMP_TENSORS_PER_BLOCK", "SPLIT_ROWS", "DNS_BLOCK",
+                                 "DNS_MAX_BLOCKS", "MC_BLOCK", "MC_MAX_TENSORS", "LT_W", "LT_H", "LTHREADS")}
+
+    def one(pattern, body, what):
+        found = set(re.findall(pattern, body))
+        assert len(found) == 1, (what, found)
+        return found.pop()
+
+    out["SCAN_CHUNK"] = int(one(r"base < nb; base \+= (\d+)\)", src["gsr_compact.hip"], "compact_scan_kernel's step"))
+    a, b = one(r"\(most \+ (\d+)ull \* (\d+)ull - 1\)", src["gsr_compact.hip"], "append_rows_kernel's bytes per block")
+    out["APPEND_BLOCK_BYTES"] = int(a) * int(b)
+    a, b = one(r"want > (\d+) \? (\d+) : want", src["gsr_compact.hip"], "append_rows_kernel's grid cap")
+    assert a == b
+    out["APPEND_MAX_BLOCKS"] = int(a)
+    a, b = one(r"want > (\d+) \? (\d+) : want", src["gsr_mcmc.hip"], "mcmc_scatter_kernel's grid cap")
+    assert a == b
+    out["MC_SCATTER_MAX_BLOCKS"] = int(a)
+    out["PY_CHUNK"] = int(one(r"range\(0, len\(srcs\), (\d+)\)", text("densify.py"), "densify.py's chunk of tensors"))
+    return out
+
+
+def compact_tensors(P, seed=0):
+    """The tensors of test_compact_rows_equals_boolean_indexing (its copy of the mask replaced by a random bool tensor) and
+    three further narrow ones -- 2-, 4- and 20-byte rows -- so that compact_apply_kernel runs two blockIdx.y groups of 8."""
+    g = torch.Generator().manual_seed(7000 + seed)
+    return [torch.randn(P, 3, generator=g), torch.randn(P, 15, 3, generator=g), torch.randn(P, 1, generator=g),
+            torch.randn(P, 4, generator=g), torch.arange(P, dtype=torch.int64), torch.rand(P, generator=g) < 0.5,
+            torch.randn(P, generator=g), torch.randint(0, 255, (P, 3), generator=g, dtype=torch.uint8),
+            torch.randint(-30000, 30000, (P,), generator=g, dtype=torch.int16), torch.randint(0, 2 ** 31 - 1, (P,), generator=g, dtype=torch.int32),
+            torch.randn(P, 5, generator=g)]
+
+
+def compact_masks(P, seed=0):
+    """name -> (P,) bool keep mask: a random half (with the rows on both sides of SCAN_EDGE and the last one); only the rows
+    from SCAN_EDGE on (carry 0: the output comes from the scan's second trip alone); every row below SCAN_EDGE and a random
+    half of the tail with the last row (carry SCAN_EDGE); the very last row alone.  P > SCAN_EDGE."""
+    assert P > SCAN_EDGE
+    g = torch.Generator().manual_seed(7100 + seed)
+    rows = torch.arange(P)
+    half = torch.rand(P, generator=g) < 0.5
+    head = (rows < SCAN_EDGE) | half
+    head[P - 1] = True
+    last = torch.zeros(P, dtype=torch.bool)
+    last[P - 1] = True
+    rnd = torch.rand(P, generator=g) < 0.5
+    rnd[[SCAN_EDGE - 1, SCAN_EDGE, P - 1]] = True  # (cut to SCAN_EDGE + 1 rows its last block of one row has its survivor)
+    return {"random": rnd, "tail_only": rows >= SCAN_EDGE, "head_kept": head, "last_row": last}
+
+
+def split_case_large(P, n_random=300, N=2, seed=0):
+    """test_split_positions' inputs at P rows: (xyz, scaling, rotation, sel, noise) numpy; the selection holds rows 0,
+    SCAN_EDGE - 1, SCAN_EDGE and P - 1 and n_random random ones."""
+    rng = np.random.default_rng(7200 + seed)
+    xyz = (rng.standard_normal((P, 3)) * 3).astype(F)
+    scaling = np.exp(rng.uniform(-6, -1, (P, 3))).astype(F)
+    rot = rng.standard_normal((P, 4))
+    rot = (rot / np.linalg.norm(rot, axis=1, keepdims=True) * np.exp(rng.uniform(np.log(0.1), np.log(10), (P, 1)))).astype(F)
+    sel = np.zeros(P, bool)
+    sel[rng.choice(P, n_random, replace=False)] = True
+    sel[[0, SCAN_EDGE - 1, SCAN_EDGE, P - 1]] = True
+    noise = rng.standard_normal((N * int(sel.sum()), 3)).astype(F)
+    return xyz, scaling, rot, sel, noise
+
+
+def message_case_large(P, seed=0):
+    """Synthetic dense gradients of one view for the view-message plan: ([means3D (P,3), scales (P,3), rotations (P,4),
+    means2D (P,3), opacities (P,1)], rgb (P,3), touched (P,) bool) as torch tensors.  About 1 % of the rows are touched, the
+    last row of every one of the last three blocks among them; a touched row is non-zero in tensor (row % 6) and in a random
+    half of the others, so that no single tensor gives the mask away."""
+    g = torch.Generator().manual_seed(7300 + seed)
+    touched = torch.rand(P, generator=g) < 0.01
+    touched[[0, SCAN_EDGE - 1, SCAN_EDGE, SCAN_EDGE + 1023, P - 1]] = True
+    rows = torch.arange(P)
+    out = []
+    for i, k in enumerate((3, 3, 4, 3, 1, 3)):
+        on = touched & ((rows % 6 == i) | (torch.rand(P, generator=g) < 0.5))
+        v = torch.randn(P, k, generator=g)
+        v[v == 0] = 1.0
+        out.append(torch.where(on[:, None], v, torch.zeros(())))  # (+0 elsewhere: v * False would leave -0)
+    return out[:5], out[5], touched
+
+
+def count_case(count, P=P_COUNTS, seed=0):
+    """`count` uint8 tensors of P rows whose widths cycle through ROW_WIDTHS, with their n-row extensions (every third
+    None: zero rows) -> (tensors, extensions, n)."""
+    g = torch.Generator().manual_seed(7400 + count + seed)
+    n = 77
+    ts = [torch.randint(0, 256, (P, ROW_WIDTHS[i % len(ROW_WIDTHS)]), generator=g, dtype=torch.uint8) for i in range(count)]
+    ex = [None if i % 3 == 2 else torch.randint(0, 256, (n, t.shape[1]), generator=g, dtype=torch.uint8) for i, t in enumerate(ts)]
+    return ts, ex, n

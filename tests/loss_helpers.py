@@ -160,3 +160,62 @@ def fixture_bar(case):
     r, e = reference_error(case), expectation(case)
     return dict(loss=max(2 * r["loss"], 1e-6), l1=max(2 * r["l1"], 1e-6), ssim=max(2 * r["ssim"], 1e-6),
                 grad=max(2 * r["grad"], 1e-6 * float(np.abs(e["grad"]).max())))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# a shape beyond the fixture (tests/test_cpu_size_regimes.py, tests/test_gpu_size_regimes.py): 3 x 10 x 10 = 300 tiles of
+# 16 x 64, ragged in both directions (1 row, 1 column), so that loss_finish_kernel's threads add more than one slot each.
+# Its float32 arrays would be 3 MB per case, so the fixture does not hold it; the bar's "reference's own float32 error" is
+# taken from the same formula evaluated in float32 torch on the CPU, which tests/test_cpu_size_regimes.py pins to the
+# fixture's arrays on every fixture case.
+# ----------------------------------------------------------------------------------------------------------------------
+LARGE_SHAPE = (3, 145, 577)
+LARGE_SEED = 1100
+
+
+def loss_and_grad32(x, y, w_l1, w_ssim, c):
+    """loss_and_grad64's formula in float32 throughout (window, conv2d, autograd): (loss, l1, ssim, dloss/dx) float32."""
+    x = torch.as_tensor(np.asarray(x, np.float32)).clone().requires_grad_(True)
+    y = torch.as_tensor(np.asarray(y, np.float32))
+    n = int(np.prod(x.shape[:-2]))
+    g = window64().float()
+    w = (g[:, None] * g[None, :]).expand(n, 1, 11, 11).contiguous()
+    blur = lambda t: F.conv2d(t, w, padding=5, groups=n)  # noqa: E731
+    xp, yp = _planes(x), _planes(y)
+    mu1, mu2 = blur(xp), blur(yp)
+    s1, s2, s12 = blur(xp * xp) - mu1 * mu1, blur(yp * yp) - mu2 * mu2, blur(xp * yp) - mu1 * mu2
+    ssim = (((2 * mu1 * mu2 + C1) * (2 * s12 + C2)) / ((mu1 * mu1 + mu2 * mu2 + C1) * (s1 + s2 + C2))).mean()
+    l1 = (x - y).abs().mean()
+    loss = w_l1 * l1 + w_ssim * ssim + c
+    loss.backward()
+    return (np.float32(loss.detach().numpy()), np.float32(l1.detach().numpy()), np.float32(ssim.detach().numpy()),
+            x.grad.numpy().copy())
+
+
+def float32_error(x, y, e):
+    """reference_error with loss_and_grad32 in the place of the fixture's arrays; e: dict(loss, l1, ssim, grad) in float64."""
+    r32 = loss_and_grad32(x, y, *weights())
+    return dict(loss=abs(float(r32[0]) - e["loss"]), l1=abs(float(r32[1]) - e["l1"]), ssim=abs(float(r32[2]) - e["ssim"]),
+                grad=float(np.abs(r32[3].astype(np.float64) - e["grad"]).max()))
+
+
+def bar_of_error(r, e):
+    """fixture_bar's formula on an error dict r and the float64 yardstick e."""
+    return dict(loss=max(2 * r["loss"], 1e-6), l1=max(2 * r["l1"], 1e-6), ssim=max(2 * r["ssim"], 1e-6),
+                grad=max(2 * r["grad"], 1e-6 * float(np.abs(e["grad"]).max())))
+
+
+_large = {}
+
+
+def large_case(variant):
+    """variant 'tex' | 'flat' at LARGE_SHAPE, computed once: dict(x, y, loss, l1, ssim, grad [float64 yardstick], ref_error,
+    bar) where bar is fixture_bar's formula with the float32 evaluation above in the place of the fixture's arrays."""
+    if variant not in _large:
+        x, y = image_pair(LARGE_SHAPE, LARGE_SEED, variant == "flat")
+        loss, l1, ssim, grad = loss_and_grad64(x, y, *weights())
+        c = dict(x=x, y=y, loss=loss, l1=l1, ssim=ssim, grad=grad)
+        c["ref_error"] = float32_error(x, y, c)
+        c["bar"] = bar_of_error(c["ref_error"], c)
+        _large[variant] = c
+    return _large[variant]

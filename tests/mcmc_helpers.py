@@ -273,3 +273,49 @@ def mcmc_refine_torch(par, moments, extra, *, cap_max, min_opacity=0.005, grow=1
                     extra[key] = torch.cat((t, torch.zeros((n_new,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev)))
             touched.update(src_grow=src)
     return par, moments, extra, (P, n_dead, n_rel, n_add), touched
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the second size regimes (tests/test_cpu_size_regimes.py, tests/test_gpu_size_regimes.py)
+# ----------------------------------------------------------------------------------------------------------------------
+N_LARGE_DRAWS = 30000
+P_REFINE, DEAD_EVERY, MASK_FRACTION = 300000, 7, 0.6   # the end-to-end refine: every 7th row dead, 60 % of the rows masked in
+GROW_REFINE = 1.1                                      # 30 000 appended rows: the growth's copies stride too
+F_REST_WORDS = 45                                      # a (P, 15, 3) float32 row
+P_VALUE, N_VALUE = 400000, 350001                      # a relocation whose 3-word VALUE rows (scaling) stride: 3 n > 1 048 576
+
+
+def relocate_case_large(P=P_VALUE, n=N_VALUE, seed=0):
+    """A relocation of n dead rows out of P on three narrow groups: ({xyz (P,3), opacity (P,1), scaling (P,3)}, dead (n,) int64
+    ascending, src (n,) int64 among the other rows, new_opacity (n,1), new_scaling (n,3)); the new values are a function of
+    the source row, as relocation_values makes them, so the draws of one source agree."""
+    g = torch.Generator().manual_seed(8200 + seed)
+    par = dict(xyz=torch.randn(P, 3, generator=g), opacity=torch.randn(P, 1, generator=g), scaling=torch.randn(P, 3, generator=g))
+    perm = torch.randperm(P, generator=g)
+    dead, alive = perm[:n].sort().values, perm[n:]
+    src = alive[torch.randint(0, int(alive.numel()), (n,), generator=g)]
+    table_o, table_s = torch.randn(P, 1, generator=g), torch.randn(P, 3, generator=g)
+    return par, dead, src, table_o[src], table_s[src]
+
+
+def large_sample_case(P, seed=0, min_opacity=0.005):
+    """(opacity (P,) f32, mask (P,) bool, u (N_LARGE_DRAWS,) f32): about 5 % of the rows dead, spread over every block, the
+    last row and the rows on both sides of 1024 * 1024 among them; u holds both of its ends."""
+    rng = np.random.default_rng(8000 + seed)
+    opacity = rng.random(P).astype(F)
+    opacity[opacity <= F(min_opacity)] = F(0.5)
+    opacity[rng.random(P) < 0.05] = F(0.001)
+    mask = rng.random(P) < 0.9
+    edge = 1024 * 1024
+    for r in (3, edge - 1, edge, P - 1):
+        opacity[r], mask[r] = F(0.001), True
+    opacity[4], mask[4] = np.nextafter(F(min_opacity), F(1)), True
+    opacity[P - 2], mask[P - 2] = F(1.0), True  # the last alive row: the largest u must find it
+    u = np.minimum(rng.random(N_LARGE_DRAWS).astype(F), F(1 - 2.0 ** -24))
+    u[0], u[1] = F(0), F(1 - 2.0 ** -24)
+    return opacity, mask, u
+
+
+def refine_mask_large(P=P_REFINE):
+    """The edit mask of the end-to-end refine at scale (CPU generator: the CPU test counts the dead rows inside it)."""
+    return torch.rand(P, generator=torch.Generator().manual_seed(8100)) < MASK_FRACTION
