@@ -170,6 +170,9 @@ SIGNATURES = {
     "gsr_debug_blend_backward_items": (c_int, [_P, c_int, c_int, _P, POINTER(c_int64)]),
     # which radix scatter ran (host-side bookkeeping): (counts[24]), index layout at the declaration in include/gsr.h
     "gsr_debug_sort_launches": (c_int, [POINTER(ctypes.c_uint64)]),
+    # which chunk kernel of the grouped binning ran (host-side bookkeeping): (counts[16]), index log2(NB) | SCATTER << 2 |
+    # (stage of 2048 entries) << 3
+    "gsr_debug_group_launches": (c_int, [POINTER(ctypes.c_uint64)]),
     # the fused L1 + SSIM loss (gaussianeditor_amd/losses.py): (planes, H, W, bytes);
     # (stream, planes, H, W, img, gt, w_l1, w_ssim, c, maps | NULL, workspace, out3);
     # (stream, planes, H, W, img, gt, maps, w_l1, w_ssim, dL_dloss, dL_dimg)

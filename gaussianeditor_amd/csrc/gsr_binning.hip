@@ -1378,10 +1378,18 @@ __global__ void __launch_bounds__(COLSCAN_WAVES * 64) group_colscan_kernel(int g
   }
 }
 
+// Host-side launch counts of group_chunk_kernel (gsr_debug_group_launches; the index layout is stated at its declaration
+// in include/gsr.h): log2(NB) | SCATTER << 2 | (stage_cap == 2048) << 3.  The count pass has no stage: cap bit 0.
+static std::atomic<uint64_t> g_group_launches[16];
+void group_launch_counts(uint64_t counts[16]) {
+  for (int i = 0; i < 16; ++i) counts[i] = g_group_launches[i].load(std::memory_order_relaxed);
+}
 template <bool SCATTER>
 static void launch_chunks(hipStream_t s, const Binning& b, const GroupArgs& a) {
   const dim3 grid((unsigned)((b.chunks + 7) / 8 * 8)), block(64);  // a multiple of 8: see the chunk -> XCD dealing in the kernel
   const size_t lds = SCATTER ? sizeof(uint2) * ((size_t)a.stage_cap + 1) : 0;
+  const int nb = b.chunk / 64, log2_nb = nb >= 8 ? 3 : (nb == 4 ? 2 : (nb == 2 ? 1 : 0));
+  g_group_launches[log2_nb | (SCATTER ? 4 : 0) | (SCATTER && a.stage_cap == 2048u ? 8 : 0)].fetch_add(1, std::memory_order_relaxed);
   switch (b.chunk / 64) {
     case 1: hipLaunchKernelGGL((group_chunk_kernel<SCATTER, 1>), grid, block, lds, s, a); break;
     case 2: hipLaunchKernelGGL((group_chunk_kernel<SCATTER, 2>), grid, block, lds, s, a); break;

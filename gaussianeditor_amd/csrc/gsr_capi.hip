@@ -215,6 +215,17 @@ inline int bin_legacy(int W, int H) {
   const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
   return (forced || group_count(W, H) > GROUP_MAX || gx > RECT32_EDGE || gy > RECT32_EDGE) ? 1 : 0;
 }
+// GSR_GROUP_CHUNK=64|128|256|512 (tests) gives every view of the process that chunk length of the grouped path, whatever
+// its G: every length is correct for any G, and the longer ones are otherwise reached only above a million group
+// instances.  0: not set (any other value counts as not set).  Every carve of a view goes through here, so that
+// gsr_scratch_sizes, gsr_bin and the blend / export entry points agree.
+inline int group_chunk_forced() {
+  static const int forced = [] {
+    const int v = env_knob("GSR_GROUP_CHUNK", 0, 0, INT_MAX);
+    return (v == 64 || v == 128 || v == 256 || v == 512) ? v : 0;
+  }();
+  return forced;
+}
 // Whether a view's forward leaves checkpoints, and where the first one sits (in 64-entry chunks): where lists are LONG
 // (deep-tile scenes, 6 M Gaussians: the backward walks up to 7 000 positions of a tile's list; blend backward 438 -> 339 us
 // and 528 -> 314 us when introduced at a uniform 512 positions), none where they are short.  On the benchmark view (mean list 593 entries per tile) the heaviest backward
@@ -276,7 +287,7 @@ inline CkTable checkpoint_table(int64_t R, int W, int H) {
 // What the blend / export entry points need of the binning scratch sits in front of everything sized by the number of
 // group instances, so they carve with G = 0.
 inline Binning carve_binning_view(const void* binning, int64_t R, int W, int H) {
-  return carve_binning(const_cast<void*>(binning), R, 0, W, H, bin_legacy(W, H));
+  return carve_binning(const_cast<void*>(binning), R, 0, W, H, bin_legacy(W, H), group_chunk_forced());
 }
 // Scratch buffers are accessed with 16-byte vector loads at 256-byte aligned section offsets.
 inline bool misaligned(const void* p) { return ((uintptr_t)p & 255u) != 0; }
@@ -365,7 +376,7 @@ int gsr_sort_key_bits(int W, int H) { return sort_key_bits(W, H); }
 int gsr_scratch_sizes(int P, int64_t R, int64_t G, int W, int H, size_t sizes[3]) {
   if (P < 0 || R < 0 || G < 0 || W <= 0 || H <= 0 || sizes == nullptr) return GSR_ERR_BAD_ARGUMENT;
   sizes[0] = carve_geom(nullptr, P).bytes;
-  sizes[1] = carve_binning(nullptr, R, G, W, H, bin_legacy(W, H)).bytes;
+  sizes[1] = carve_binning(nullptr, R, G, W, H, bin_legacy(W, H), group_chunk_forced()).bytes;
   // (the checkpoint pool -- up to 64 MB, the LAST section of the image scratch -- only for views whose forward writes
   //  checkpoints: the same predicate of (R, W, H) the blend entry points use.  R = 0, "not known yet": the size WITH the
   //  pool, so that a buffer sized before gsr_preprocess is never too small)
@@ -599,7 +610,7 @@ int gsr_bin(void* stream, int P, int64_t R, int64_t G, int W, int H, const void*
   const int legacy = bin_legacy(W, H);
   if (R > 0 && !legacy && (G <= 0 || G > R)) return GSR_ERR_BAD_ARGUMENT;  // every group instance holds >= 1 tile instance
   const Geom g = carve_geom(const_cast<void*>(geom), P);
-  const Binning b = carve_binning(binning, R, G, W, H, legacy);
+  const Binning b = carve_binning(binning, R, G, W, H, legacy, group_chunk_forced());
   const Image im = carve_image(image, W, H);
   GSR_HIP(launch_binning((hipStream_t)stream, P, R, W, H, g, b, im));
   return GSR_OK;
@@ -1364,6 +1375,12 @@ int gsr_debug_blend_backward_launches(uint64_t* counts) {
 int gsr_debug_sort_launches(uint64_t* counts) {
   if (!counts) return GSR_ERR_BAD_ARGUMENT;
   sort_launch_counts(counts);
+  return GSR_OK;
+}
+
+int gsr_debug_group_launches(uint64_t* counts) {
+  if (!counts) return GSR_ERR_BAD_ARGUMENT;
+  group_launch_counts(counts);
   return GSR_OK;
 }
 

@@ -275,7 +275,8 @@ __host__ __device__ inline int group_chunk_items(int64_t G) {
   return 64 * per;
 }
 // `legacy`: the caller's choice of path (capi: image size, GSR_BIN_LEGACY); G is ignored on the legacy path.
-__host__ __device__ inline Binning carve_binning(void* base, int64_t R, int64_t G, int W, int H, int legacy) {
+// `forced_chunk`: 0, or the chunk length GSR_GROUP_CHUNK gives every view of the process (capi: group_chunk_forced).
+__host__ __device__ inline Binning carve_binning(void* base, int64_t R, int64_t G, int W, int H, int legacy, int forced_chunk) {
   char* p = (char*)base;
   Binning b;
   const int64_t gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE, T = gx * gy;
@@ -299,7 +300,7 @@ __host__ __device__ inline Binning carve_binning(void* base, int64_t R, int64_t 
   b.groups = b.sgx * b.sgy;
   b.group_bits = b.groups <= 256 ? 8 : 11;
   b.G = legacy ? 0 : G;
-  b.chunk = group_chunk_items(b.G);
+  b.chunk = forced_chunk != 0 ? forced_chunk : group_chunk_items(b.G);
   b.chunks = b.G / b.chunk + b.groups;
   b.sort_blocks = (uint32_t)((b.G + SORT_KPB - 1) / SORT_KPB);
   if (legacy) {
@@ -471,6 +472,8 @@ __device__ __forceinline__ uint32_t block_excl_scan_u32(uint32_t v, uint32_t* bl
 //   GSR_BIN_LEGACY=1            the two-pass pair sort for every image size (gsr_capi.hip: bin_legacy)
 //   GSR_SORT_THREADS=256|1024   that block width for every radix sort, whatever its size (gsr_binning.hip: with_sort_width);
 //                               any other value counts as unset: 1024 for sorts of up to 1024 blocks, 256 beyond
+//   GSR_GROUP_CHUNK=64|128|256|512  that many group instances per chunk of the grouped binning, whatever G (gsr_capi.hip:
+//                               group_chunk_forced); any other value counts as unset: group_chunk_items(G)
 //   GSR_CK_CHUNKS=n             checkpoint stride in 64-entry chunks, uniform table; 0 = no checkpoints; unset: by list length
 //   GSR_CK_DEBUG=1              lets GSR_CK_CHUNKS go below 4 (gsr_capi.hip: checkpoint_chunks)
 //   GSR_CK_SLOTS=n              checkpoint slots in use per tile, 2 .. CK_MAX (default CK_MAX)

@@ -165,6 +165,8 @@ void radix_sort_pairs_u32(hipStream_t s, uint32_t* const keys[2], uint32_t* cons
 // debug (host only): launches of the radix scatter kernels per instantiation in this process (include/gsr.h:
 // gsr_debug_sort_launches states the index layout)
 void sort_launch_counts(uint64_t counts[24]);
+// debug (host only): launches of group_chunk_kernel per instantiation and stage size (gsr_debug_group_launches)
+void group_launch_counts(uint64_t counts[16]);
 size_t knn_workspace_bytes(int P);
 hipError_t launch_knn(hipStream_t s, int P, const float* points, void* workspace, float* out);
 hipError_t launch_near_points(hipStream_t s, int n_ref, const float* ref, int n_query, const float* query, float thresh,

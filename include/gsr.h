@@ -30,7 +30,8 @@
  *   - tuning / experiment knobs are environment variables read ONCE per process, none of which changes any result
  *     (launch geometry of the persistent blend kernels, work-list ordering, GSR_BIN_LEGACY=1,
  *     which sends every image down the tile-pair sort that otherwise only images beyond 131 072 tiles take, and
- *     GSR_SORT_THREADS=256|1024, which gives every radix sort the block width that otherwise its size decides); they are
+ *     GSR_SORT_THREADS=256|1024, which gives every radix sort the block width that otherwise its size decides, and
+ *     GSR_GROUP_CHUNK=64|128|256|512, the same for the chunk length of the grouped binning); they are
  *     listed in DESIGN.md section 3.3 and are not part of this ABI.
  *   - an absent optional input is a NULL pointer (the reference uses empty
  *     tensors for the same purpose, diff_gaussian_rasterization/__init__.py:285-295).
@@ -894,6 +895,19 @@ int gsr_debug_blend_backward_items(void* stream, int W, int H, const void* image
  * Counted where the instantiation is chosen, with relaxed atomics (renders may run from several host threads).
  * GSR_ERR_BAD_ARGUMENT for NULL. */
 int gsr_debug_sort_launches(uint64_t* counts);
+
+/* Which chunk kernel did the grouped binning run?  Host-side bookkeeping for the tests: nothing is launched.
+ * gsr_debug_group_launches: counts[16] (HOST) receives how often this process has launched group_chunk_kernel<SCATTER, NB>
+ * of gsr_binning.hip so far.  NB = chunk length / 64: 1, 2, 4 or 8 by the number of group instances G of the view, or what
+ * GSR_GROUP_CHUNK=64|128|256|512 says for every view of the process.  Index:
+ *    log2(NB) | SCATTER << 2 | (LDS stage of 2048 entries) << 3
+ *    0 ..  3  the count pass (no stage: the stage bit is 0, so 8 .. 11 stay 0)
+ *    4 ..  7  the append pass with a stage of 1024 entries: (R / G + 1) * chunk length <= 820.  R >= G, so a chunk of 512
+ *             never has it: 7 stays 0
+ *   12 .. 15  the append pass with a stage of 2048 entries
+ * Counted where the instantiation is chosen, with relaxed atomics (renders may run from several host threads).
+ * GSR_ERR_BAD_ARGUMENT for NULL. */
+int gsr_debug_group_launches(uint64_t* counts);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

@@ -105,6 +105,10 @@ def test_argument_validation_needs_no_gpu():
     assert L.gsr_debug_sort_launches(None) == -1  # (no array for the 24 counts)
     c24 = (ctypes.c_uint64 * 24)(*([7] * 24))
     assert L.gsr_debug_sort_launches(c24) == 0 and not any(c24[21:])  # (host-side counts, no device needed; 21 .. 23: zero)
+    assert L.gsr_debug_group_launches(None) == -1  # (no array for the 16 counts)
+    c16 = (ctypes.c_uint64 * 16)(*([7] * 16))
+    # (host-side counts, no device needed; the count pass has no stage and a chunk of 512 never a stage of 1024 entries)
+    assert L.gsr_debug_group_launches(c16) == 0 and not any(c16[8:12]) and c16[7] == 0
     assert L.gsr_debug_blend_backward_items(None, 64, 64, None, r) == -1 and L.gsr_debug_blend_backward_items(None, 0, 64, ctypes.c_void_p(256), r) == -1
     assert L.gsr_sh_grad_compose(None, 10, 4, 16, 1, None, None, None, None) == -1  # degree > 3
     assert L.gsr_view_message_plan(None, 10, None, None, None, None, None) == -1

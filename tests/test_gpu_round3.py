@@ -54,8 +54,10 @@ def _lists_match(case):
 
 
 @pytest.mark.parametrize("P,W,H,s0", [
-    (3000, 640, 360, 0.6),     # every splat covers the image: each group instance covers 64 tiles (quarter batches)
-    (20000, 1024, 1024, 0.15), # ~25 tiles per group instance: half batches, several flushes per chunk
+    # (the mean tiles per group instance of these two put the LDS stage at 2048 entries, where half a batch -- 32 items x 64
+    #  tiles -- always fits: quarter batches need a stage of 1024, i.e. heavy batches in a light view: test_gpu_chunk_matrix.py)
+    (3000, 640, 360, 0.6),     # every splat covers the image: each group instance covers up to 64 tiles (half batches)
+    (20000, 1024, 1024, 0.15), # ~25 tiles per group instance: ~1600 entries per batch, mostly whole batches, a flush per batch
     (5000, 128, 128, 0.05),    # ONE group: nothing to sort
     (5000, 2048, 16, 0.05),    # one tile row, 16 groups
     (200000, 1920, 1080, 0.02),
