@@ -179,6 +179,16 @@ SIGNATURES = {
     "gsr_loss_workspace_size": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
     "gsr_photometric_loss_forward": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_float, c_float, c_float, _P, _P, _P]),
     "gsr_photometric_loss_backward": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_float, c_float, _P, _P]),
+    # the bilateral-grid slice and its TV regulariser (gaussianeditor_amd/bilagrid.py): (B, H, W, GX, GY, GZ, bytes);
+    # (stream, B, H, W, N, GX, GY, GZ, grids, idx, img, out);
+    # (stream, B, H, W, N, GX, GY, GZ, grids, idx, img, dL_dout, workspace, dL_dimg | NULL, dL_dgrids | NULL);
+    # (N, GX, GY, GZ, bytes); (stream, N, GX, GY, GZ, grids, workspace, out1); (stream, N, GX, GY, GZ, grids, dL_dtv, dL_dgrids)
+    "gsr_bilagrid_workspace_size": (c_int, [c_int] * 6 + [POINTER(c_size_t)]),
+    "gsr_bilagrid_slice_forward": (c_int, [_P] + [c_int] * 7 + [_P] * 4),
+    "gsr_bilagrid_slice_backward": (c_int, [_P] + [c_int] * 7 + [_P] * 7),
+    "gsr_bilagrid_tv_workspace_size": (c_int, [c_int] * 4 + [POINTER(c_size_t)]),
+    "gsr_bilagrid_tv_forward": (c_int, [_P] + [c_int] * 4 + [_P] * 3),
+    "gsr_bilagrid_tv_backward": (c_int, [_P] + [c_int] * 4 + [_P] * 3),
 }
 
 _lib = None

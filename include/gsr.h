@@ -74,7 +74,8 @@ extern "C" {
  * (the camera gradient; no new flag bit, nothing existing changed).  Then, likewise additive:
  * GSR_MAX_FEATURE_CHANNELS, gsr_blend_forward_features and gsr_blend_backward_features (the feature image; no new flag bit).
  * Then, likewise additive: gsr_mcmc_noise, gsr_mcmc_workspace_size, gsr_mcmc_sample, gsr_mcmc_relocation_values and
- * gsr_mcmc_scatter (the 3DGS-MCMC strategy; no new flag bit, nothing existing changed). */
+ * gsr_mcmc_scatter (the 3DGS-MCMC strategy; no new flag bit, nothing existing changed).  Then, likewise additive: the six
+ * gsr_bilagrid_* entry points (the bilateral-grid slice and its TV regulariser; nothing existing changed). */
 #define GSR_ABI_VERSION 6
 /* The blend backward's accumulator table: GSR_ACC_ROW floats (one 64-byte line) per Gaussian, 64-byte aligned.  Columns:
  *   [GSR_ACC_MEAN2D] .x [+1] .y of dL_dmean2D      (backward.cu:545-546)
@@ -832,6 +833,41 @@ int gsr_photometric_loss_forward(void* stream, int planes, int H, int W, const f
                                  float w_ssim, float c, float* maps, void* workspace, float* out3);
 int gsr_photometric_loss_backward(void* stream, int planes, int H, int W, const float* img, const float* gt,
                                   const float* maps, float w_l1, float w_ssim, const float* dL_dloss, float* dL_dimg);
+
+/* ---- per-image appearance compensation: the bilateral-grid slice and its TV regulariser ----
+ * What 3DGS trainers put between the render and the loss for real captures (gsplat: use_bilateral_grid, "slice" and
+ * total_variation_loss): a small learnable grid of 3 x 4 affine colour transforms per training image.
+ *   grids (N,12,GZ,GY,GX) f32, grids[n][k][z][y][x], k = 4 c + m: row c, column m of a row-major 3 x 4 matrix (gsplat's layout);
+ *   img, out, dL_dout, dL_dimg (B,3,H,W) f32, planar;  idx (B) int64 ON THE DEVICE: image b uses grids[idx[b]].  The kernels
+ *       read it (the host neither waits nor reads anything back) and CLAMP it to [0, N - 1]: an index out of range selects
+ *       the nearest valid grid and nothing outside `grids` is read or written.
+ * Slice, for the pixel in row i, column j with colour (r, g, b):
+ *   u = (j + 0.5) / W, v = (i + 0.5) / H, gray = 0.299 r + 0.587 g + 0.114 b,
+ *   gx = u (GX - 1), gy = v (GY - 1), gz = clamp(gray, 0, 1) (GZ - 1);  x0 = min(floor(gx), GX - 2), fx = gx - x0, same for y, z;
+ *   A[k] = the trilinear interpolation of grids[idx[b]][k] at (gz, gy, gx) (grid_sample with align_corners = True and border
+ *   padding);  out_c = A[4c] r + A[4c+1] g + A[4c+2] b + A[4c+3].
+ * Backward, from dL_dout: dL_dgrids (N,12,GZ,GY,GX), dense and FULLY written -- grids no image selected get exact zeros, a
+ * grid selected by several images the sum over them --; dL_dimg_m = sum_c dL_dout_c A[4c+m] + (0.299, 0.587, 0.114)_m
+ * (GZ - 1) sum_k dA[k]/dgz dL/dA[k], the second (guidance) term only where 0 < gray < 1.  Either output may be NULL: it is
+ * then not computed (both NULL: nothing is launched).
+ * TV: tv = (1 / N) sum over d in {z, y, x} of sum (forward difference along d)^2 / count_d, count_d = the differenced
+ * elements of ONE grid (12 (GZ - 1) GY GX for z); out1: one device float.  Its backward writes dL_dtv * d tv / d grids;
+ * dL_dtv is ONE device float read by the kernel.
+ * 2 <= GX, GY <= 32, 2 <= GZ <= 16, N, B, H, W >= 1, H W < 2^31 - 2^17 (else GSR_ERR_BAD_ARGUMENT).  workspace:
+ * gsr_bilagrid_workspace_size (the slice backward; needed only with dL_dgrids) or gsr_bilagrid_tv_workspace_size (the TV
+ * forward) bytes of device scratch, 8-byte aligned.  Coordinates, weights and sums are binary64, there are no atomics and
+ * every sum has a fixed order: all four results are the same bits on every run.  As with the loss, a failed launch is
+ * GSR_ERR_HIP and gsr_last_hip_error() is not updated. */
+int gsr_bilagrid_workspace_size(int B, int H, int W, int GX, int GY, int GZ, size_t* bytes);
+int gsr_bilagrid_slice_forward(void* stream, int B, int H, int W, int N, int GX, int GY, int GZ, const float* grids,
+                               const int64_t* idx, const float* img, float* out);
+int gsr_bilagrid_slice_backward(void* stream, int B, int H, int W, int N, int GX, int GY, int GZ, const float* grids,
+                                const int64_t* idx, const float* img, const float* dL_dout, void* workspace, float* dL_dimg,
+                                float* dL_dgrids);
+int gsr_bilagrid_tv_workspace_size(int N, int GX, int GY, int GZ, size_t* bytes);
+int gsr_bilagrid_tv_forward(void* stream, int N, int GX, int GY, int GZ, const float* grids, void* workspace, float* out1);
+int gsr_bilagrid_tv_backward(void* stream, int N, int GX, int GY, int GZ, const float* grids, const float* dL_dtv,
+                             float* dL_dgrids);
 
 /* ---- introspection used by the parity tests (not needed by the drop-in) ----
  * Copy internal per-Gaussian / per-instance / per-pixel state out of the opaque
