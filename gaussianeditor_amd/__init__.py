@@ -29,6 +29,15 @@ def install() -> None:
         _sys.modules["plyfile"] = _ply
 
 
+def __getattr__(name: str):
+    # contribution statistics / pick buffer (contrib.py), resolved on first use: importing the package loads no torch code
+    if name in ("ContributionStats", "trace_view"):
+        from . import contrib
+
+        return getattr(contrib, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 def set_tile_bounds(mode: str) -> None:
     """Opt-in binning rule: the default of the GSR_FLAG_TILE_BOUNDS_ALPHA flag (include/gsr.h) for renders started
     from now on (a render's backward always reuses the flags of its forward; `options.override` is per thread).

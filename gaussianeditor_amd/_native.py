@@ -156,6 +156,7 @@ SIGNATURES = {
                             _P, _P]),
     "gsr_mark_visible": (c_int, [_P, c_int, _P, _P, _P, _P]),
     "gsr_trace_weights": (c_int, [_P, c_int, c_int64, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, c_uint]),
+    "gsr_trace_contributions": (c_int, [_P, c_int, c_int64, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_uint]),
     "gsr_debug_export_geom": (c_int, [_P, c_int, _P, _P, _P, _P, _P, _P, _P]),
     "gsr_debug_cov3d": (c_int, [_P, c_int, _P, c_float, _P, _P]),
     "gsr_debug_export_binning": (c_int, [_P, c_int, c_int64, c_int, c_int, _P, _P, _P, _P]),

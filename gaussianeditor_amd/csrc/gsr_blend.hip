@@ -1576,6 +1576,147 @@ __global__ void __launch_bounds__(WAVE) trace_weights_kernel(const BlendArgs a) 
 }
 
 // ----------------------------------------------------------------------------------
+// Contribution statistics and the pick buffer (gsr_trace_contributions): K12's sibling that KEEPS the blending weight
+// w = alpha T of every (pixel, entry) the walk hands out.  No reference counterpart.  Per Gaussian g, in the int64 row
+// stats[g] (3 + C columns, accumulated in place):
+//   [0]     sum over the pixels that blend g of q(w),  q(x) = (uint32) trunc(x 2^32)   (w <= 0.99: q fits 32 bits)
+//   [1]     pixels whose largest weight is g's (the pick buffer's histogram)
+//   [2]     the largest w, as the float's bit pattern (w > 0: the unsigned order of the patterns is the floats')
+//   [3 + c] sum of q(w * m_c), m_c = the pixel's mask value of channel c clamped to [0, 1] (NaN -> 0), one binary32 multiply
+// Every accumulation is an integer add or an integer max, so a table does not depend on the grid, the quadrant cut, the
+// arrival order or the order of the views.  The wave sums stay on the float reduction K12 uses (wave_sum4_to_rows): q is
+// summed as its two 16-bit halves, each total <= 64 x 65535 < 2^24 and therefore exact in binary32 in any order, and
+// put together again as 64 bits behind the chunk.  A chunk's survivors leave with at most one atomic per column.
+// The per-pixel largest weight and its Gaussian live in registers across the chunks (strictly greater replaces: among
+// equal weights the front-most entry of the list wins); column 1 gets one add per pixel at the end of the item.
+// What is new beside a view's BlendArgs travels as a second kernel argument, as FeatureArgs does.
+// ----------------------------------------------------------------------------------
+struct ContribArgs {
+  unsigned long long* stats;  // (P, 3 + C), the int64 table (its values are never negative)
+  int32_t* top_id;            // (H,W) | null: fully written, -1 where the pixel blends nothing
+  float* top_weight;          // (H,W) | null: fully written, 0 where the pixel blends nothing
+};
+// max of each of four per-lane values over the 64 lanes: wave_fold4_to_rows / wave_sum4_to_rows with an unsigned max (its
+// identity is the 0 a DPP lane without a source reads).  The maximum of value r ends up in lane 16 r + 15.
+__device__ __forceinline__ uint32_t wave_max4_to_rows(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
+  {
+    auto r = __builtin_amdgcn_permlane32_swap(a, c, false, false);
+    a = r[0];
+    c = r[1];
+  }
+  {
+    auto r = __builtin_amdgcn_permlane32_swap(b, d, false, false);
+    b = r[0];
+    d = r[1];
+  }
+  uint32_t x = max(a, c), y = max(b, d);  // lanes 0-31: a | b, 32-63: c | d
+  {
+    auto r = __builtin_amdgcn_permlane16_swap(x, y, false, false);
+    x = r[0];
+    y = r[1];
+  }
+  uint32_t z = max(x, y);  // rows: a, b, c, d
+  z = max(z, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)z, 0x111, 0xf, 0xf, false));
+  z = max(z, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)z, 0x112, 0xf, 0xf, false));
+  z = max(z, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)z, 0x114, 0xf, 0xf, false));
+  z = max(z, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)z, 0x118, 0xf, 0xf, false));
+  return z;
+}
+template <int C, int SPLIT, bool FAST>
+__device__ __forceinline__ void contrib_item(const BlendArgs& a, const ContribArgs& f, uint32_t tile, uint32_t quad) {
+  PixelWave pw;
+  ItemBox box;
+  if (!setup_item<SPLIT>(a, tile, quad, pw, box)) return;
+  (void)box;
+  const int lane = lane_id();
+  const uint2 range = a.ranges[pw.tile];
+  const size_t pix = (size_t)pw.py * a.W + pw.px, HW = (size_t)a.H * a.W;
+  constexpr int COLS = 3 + C, SUMS = 1 + C;  // sums: the total, then the channels
+  float m[SUMS];                             // (m[0] unused: the total's "mask" is 1)
+  m[0] = 1.0f;
+#pragma unroll
+  for (int ch = 0; ch < C; ++ch) {
+    const float v = pw.inside ? a.image_weights[(size_t)ch * HW + pix] : 0.f;
+    m[1 + ch] = v > 0.0f ? fminf(v, 1.0f) : 0.0f;  // (NaN > 0 is false)
+  }
+  __shared__ __align__(16) uint32_t sid[WAVE];
+  __shared__ float slo[SUMS][WAVE], shi[SUMS][WAVE];
+  __shared__ uint32_t smax[WAVE];
+  const bool row_end = (lane & 15) == 15;
+  float best_w = 0.0f;
+  int32_t best_id = -1;
+  walk_front_to_back<FAST>(
+      a, pw, range, [&](uint32_t slot, const Entry& e) __attribute__((always_inline)) { sid[slot] = e.id; },
+      [&](uint32_t j, const bool(&hit)[GROUP], const float(&w)[GROUP]) __attribute__((always_inline)) {
+        const uint32_t e = j + ((uint32_t)lane >> 4);  // the entry whose totals end up in this lane's row
+        const uint4 ids = *reinterpret_cast<const uint4*>(&sid[j]);  // (j is a multiple of GROUP; uniform: one broadcast read)
+        const uint32_t id4[GROUP] = {ids.x, ids.y, ids.z, ids.w};
+        float wh[GROUP];  // the weight where the pixel blends the entry, 0 where it does not (w is meaningless there)
+#pragma unroll
+        for (int u = 0; u < GROUP; ++u) {
+          wh[u] = hit[u] ? w[u] : 0.0f;
+          const bool better = wh[u] > best_w;
+          best_w = better ? wh[u] : best_w;
+          best_id = better ? (int32_t)id4[u] : best_id;
+        }
+#pragma unroll
+        for (int k = 0; k < SUMS; ++k) {
+          float lo[GROUP], hi[GROUP];
+#pragma unroll
+          for (int u = 0; u < GROUP; ++u) {
+            const uint32_t q = (uint32_t)((k == 0 ? wh[u] : wh[u] * m[k]) * 4294967296.0f);
+            lo[u] = (float)(q & 0xffffu);
+            hi[u] = (float)(q >> 16);
+          }
+          const float zl = wave_sum4_to_rows(lo[0], lo[1], lo[2], lo[3]);
+          const float zh = wave_sum4_to_rows(hi[0], hi[1], hi[2], hi[3]);
+          if (row_end) {
+            slo[k][e] = zl;
+            shi[k][e] = zh;
+          }
+        }
+        const uint32_t zm = wave_max4_to_rows(__float_as_uint(wh[0]), __float_as_uint(wh[1]), __float_as_uint(wh[2]), __float_as_uint(wh[3]));
+        if (row_end) smax[e] = zm;
+      },
+      [&](uint32_t evaluated) __attribute__((always_inline)) {
+        __syncthreads();
+        // (the groups behind a break wrote nothing: their slots hold an earlier chunk's values)
+        if ((uint32_t)lane < evaluated) {
+          const unsigned long long total = ((unsigned long long)(uint32_t)shi[0][lane] << 16) + (uint32_t)slo[0][lane];
+          if (total != 0ull) {  // some pixel blends the entry (q(w) > 0 for every blended w: w >= 1e-4 / 255)
+            unsigned long long* row = f.stats + (size_t)sid[lane] * COLS;
+            atomicAdd(row, total);
+            atomicMax(row + 2, (unsigned long long)smax[lane]);
+#pragma unroll
+            for (int ch = 0; ch < C; ++ch) {
+              const unsigned long long wq = ((unsigned long long)(uint32_t)shi[1 + ch][lane] << 16) + (uint32_t)slo[1 + ch][lane];
+              if (wq != 0ull) atomicAdd(row + 3 + ch, wq);
+            }
+          }
+        }
+      });
+  if (pw.inside) {
+    if (f.top_id != nullptr) f.top_id[pix] = best_id;
+    if (f.top_weight != nullptr) f.top_weight[pix] = best_w;
+    if (best_id >= 0) atomicAdd(f.stats + (size_t)best_id * COLS + 1, 1ull);
+  }
+}
+template <int C, int SPLIT, bool FAST>
+__global__ void __launch_bounds__(WAVE) trace_contributions_kernel(const BlendArgs a, const ContribArgs f) {
+  // (the tiles no Gaussian touches are items only where a pixel image wants their -1 / 0)
+  run_work_queue<SPLIT>(a, f.top_id != nullptr || f.top_weight != nullptr, [&](uint32_t tile, uint32_t quad, bool empty) __attribute__((always_inline)) {
+    if (!empty) {
+      contrib_item<C, SPLIT, FAST>(a, f, tile, quad);
+    } else {
+      for_each_pixel_of_tile(a, tile, [&](size_t pix, size_t) __attribute__((always_inline)) {
+        if (f.top_id != nullptr) f.top_id[pix] = -1;
+        if (f.top_weight != nullptr) f.top_weight[pix] = 0.0f;
+      });
+    }
+  });
+}
+
+// ----------------------------------------------------------------------------------
 // Feature rendering: per-Gaussian feature vectors of C channels, alpha-composited into a (C,H,W) image on background 0
 // (gsr_blend_forward_features), and its backward (gsr_blend_backward_features).  No reference counterpart (the reference
 // composites three channels); the N-D `colors` of current 3DGS rasterizers.
@@ -2413,6 +2554,20 @@ hipError_t launch_trace_weights(hipStream_t s, BlendArgs a) {
                  OneOf<1, 2, 3>{a.C}, OneOf<1, 2, 4>{split}, a.fast_exp != 0);
   if (kernel == nullptr) return hipErrorInvalidValue;
   hipLaunchKernelGGL(kernel, g, b, 0, s, a);
+  return hipGetLastError();
+}
+// K12's sibling (gsr_trace_contributions): the same grid, cut and queue kind; a.C (0 .. 3) and a.image_weights as for K12.
+hipError_t launch_trace_contributions(hipStream_t s, BlendArgs a, int64_t* stats, int32_t* top_id, float* top_weight) {
+  unsigned grid;
+  hipError_t e = persistent_launch(s, a, 1, &grid);
+  if (e != hipSuccess) return e;
+  const int split = forward_split(grid, 4u * (unsigned)(a.gx * a.gy), false);
+  ContribArgs f = {reinterpret_cast<unsigned long long*>(stats), top_id, top_weight};
+  void (*kernel)(BlendArgs, ContribArgs) = nullptr;  // (stays null for a C that is not listed)
+  with_constants([&](auto C, auto SPLIT, auto FAST) { kernel = trace_contributions_kernel<C, SPLIT, FAST>; },
+                 OneOf<0, 1, 2, 3>{a.C}, OneOf<1, 2, 4>{split}, a.fast_exp != 0);
+  if (kernel == nullptr) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(WAVE), 0, s, a, f);
   return hipGetLastError();
 }
 

@@ -1105,6 +1105,27 @@ int gsr_trace_weights(void* stream, int P, int64_t R, int W, int H, int C, const
   return GSR_OK;
 }
 
+int gsr_trace_contributions(void* stream, int P, int64_t R, int W, int H, int C, const void* geom, const void* binning,
+                            const void* image, const float* image_weights, int64_t* stats, int32_t* top_id, float* top_weight,
+                            unsigned flags) {
+  if (C < 0 || C > 3) return GSR_ERR_BAD_CHANNELS;
+  if (flags & ~VIEW_FLAGS) return GSR_ERR_BAD_ARGUMENT;
+  if (P < 0 || R < 0 || W <= 0 || H <= 0 || !image || !stats || ((uintptr_t)stats & 7u)) return GSR_ERR_BAD_ARGUMENT;
+  if ((C > 0) != (image_weights != nullptr)) return GSR_ERR_BAD_ARGUMENT;
+  if (R > 0 && (!geom || !binning)) return GSR_ERR_BAD_ARGUMENT;
+  if (R == 0) {  // no pixel blends anything: the table stays as it is, the pixel images say "nothing"
+    const size_t n = (size_t)H * (size_t)W;
+    if (top_id) GSR_HIP(hipMemsetAsync(top_id, 0xff, sizeof(int32_t) * n, (hipStream_t)stream));
+    if (top_weight) GSR_HIP(hipMemsetAsync(top_weight, 0, sizeof(float) * n, (hipStream_t)stream));
+    return GSR_OK;
+  }
+  BlendArgs a = view_blend_args(P, R, W, H, geom, binning, image, nullptr, 2, flags);
+  a.C = C;
+  a.image_weights = image_weights;
+  GSR_HIP(launch_trace_contributions((hipStream_t)stream, a, stats, top_id, top_weight));
+  return GSR_OK;
+}
+
 int gsr_knn_workspace_size(int P, size_t* bytes) {
   if (P < 0 || !bytes) return GSR_ERR_BAD_ARGUMENT;
   *bytes = knn_workspace_bytes(P);

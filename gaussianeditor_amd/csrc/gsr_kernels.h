@@ -221,6 +221,8 @@ hipError_t launch_abs_grad_take(hipStream_t s, int P, float* acc, const uint8_t*
 // the alpha image (accumulated opacity) 1 - final_T of the image state a forward left (gsr_blend.hip)
 hipError_t launch_alpha_image(hipStream_t s, int W, int H, const float* final_T, float* out_alpha);
 hipError_t launch_trace_weights(hipStream_t s, BlendArgs a);
+// contribution statistics (P, 3 + a.C) int64 and the pick buffer of a view (gsr_blend.hip: trace_contributions_kernel)
+hipError_t launch_trace_contributions(hipStream_t s, BlendArgs a, int64_t* stats, int32_t* top_id, float* top_weight);
 // the feature image (C channels per Gaussian, composited once per 16-channel block) and its backward (gsr_blend.hip)
 hipError_t launch_feature_forward(hipStream_t s, BlendArgs a, const float* features, float* out, int C);
 hipError_t launch_feature_backward(hipStream_t s, BlendArgs a, const float* features, const float* dL_dimage,

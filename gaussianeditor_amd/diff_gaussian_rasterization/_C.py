@@ -769,6 +769,112 @@ def apply_weights(background, means3D, weights, opacity, scales, rotations, scal
     return None
 
 
+STATS_COLUMNS = 3  # include/gsr.h gsr_trace_contributions: total_q, top_count, max_bits, then one weighted_q per channel
+
+
+def _check_contribution_args(stats, image_weights, P: int, H: int, W: int, dev) -> int:
+    """`stats`: a contiguous int64 (P, 3 + C) table on `dev`; `image_weights`: None or a float32 (C,H,W) tensor, C <= 3;
+    errors name the argument.  -> C"""
+    C = 0
+    if image_weights is not None:
+        if not isinstance(image_weights, torch.Tensor) or image_weights.dtype != torch.float32:
+            raise RuntimeError("diff_gaussian_rasterization: `image_weights` must be a float32 tensor, got "
+                               f"{getattr(image_weights, 'dtype', type(image_weights).__name__)}")
+        if image_weights.dim() != 3 or tuple(image_weights.shape[1:]) != (H, W):
+            raise RuntimeError(f"diff_gaussian_rasterization: `image_weights` must be a (C, {H}, {W}) tensor, got "
+                               f"{tuple(image_weights.shape)}")
+        C = int(image_weights.size(0))
+        if C > 3:
+            raise _native.GsrError("gsr_trace_contributions", -2, f"Unsupported number of channels: {C}")
+    if not isinstance(stats, torch.Tensor) or stats.dtype != torch.int64:
+        raise RuntimeError("diff_gaussian_rasterization: `stats` must be an int64 tensor, got "
+                           f"{getattr(stats, 'dtype', type(stats).__name__)}")
+    if tuple(stats.shape) != (P, STATS_COLUMNS + C):
+        raise RuntimeError(f"diff_gaussian_rasterization: `stats` must be a ({P}, {STATS_COLUMNS + C}) tensor "
+                           f"(3 + {C} channels), got {tuple(stats.shape)}")
+    if not stats.is_contiguous():
+        raise RuntimeError("diff_gaussian_rasterization: `stats` must be contiguous (it is accumulated in place)")
+    if P != 0:
+        _require_cuda(stats, "stats")
+        _same_device(stats, "stats", dev)
+        if C and image_weights.numel() != 0:
+            _same_device(image_weights, "image_weights", dev)
+    return C
+
+
+def _trace_contributions(dev, P, R, H, W, C, geom, binning, img, image_weights, stats, return_pixels, debug, flags):
+    """gsr_trace_contributions on the current stream of `dev` -> (top_id, top_weight) | None"""
+    top_id = torch.empty((H, W), dtype=torch.int32, device=dev) if return_pixels else None
+    top_weight = torch.empty((H, W), dtype=torch.float32, device=dev) if return_pixels else None
+    torch.autograd.graph.increment_version(stats)  # accumulated through its raw pointer: what `+=` does by itself
+    _native.check("gsr_trace_contributions", _native.lib().gsr_trace_contributions(
+        _stream(dev), P, int(R), W, H, C, _ptr(geom), _ptr(binning), img.data_ptr(), _ptr(image_weights) if C else None,
+        stats.data_ptr(), _ptr(top_id), _ptr(top_weight), flags))
+    if debug:
+        torch.cuda.synchronize(dev)
+    return (top_id, top_weight) if return_pixels else None
+
+
+def _no_contributions(H: int, W: int, dev, return_pixels: bool):
+    """What a view that blends nothing returns: every pixel -1 / 0."""
+    if not return_pixels:
+        return None
+    return (torch.full((H, W), -1, dtype=torch.int32, device=dev), torch.zeros((H, W), dtype=torch.float32, device=dev))
+
+
+def trace_contributions_state(stats, num_rendered, geomBuffer, binningBuffer, imgBuffer, image_height, image_width,
+                              image_weights=None, return_pixels=False, debug=False, flags=None):
+    """Extension (no reference counterpart; include/gsr.h gsr_trace_contributions): per-Gaussian contribution statistics of
+    the view whose state (`geomBuffer`, `binningBuffer`, `imgBuffer`, `num_rendered`) a rasterize_gaussians() call returned.
+    `stats` (P, 3 + C) int64 is accumulated in place -- [0] the sum of the blending weights alpha T in units of 2^-32,
+    [1] the number of pixels the Gaussian is the top contributor of, [2] its largest weight as float bits, [3 + c] the sum of
+    weight x clamp(image_weights[c], 0, 1) -- in integers: the same bits on every run and in every order of the views.
+    `image_weights`: None or (C,H,W) float32, C <= 3.  With `return_pixels` -> (top_id (H,W) int32, top_weight (H,W) float32),
+    the Gaussian of the largest weight per pixel (-1 / 0 where nothing is blended); else None.  The saved state is left intact."""
+    flags = _flags(flags)
+    if not isinstance(stats, torch.Tensor):
+        raise RuntimeError(f"diff_gaussian_rasterization: `stats` must be a tensor, got {type(stats).__name__}")
+    dev = stats.device
+    P = int(stats.size(0)) if stats.dim() == 2 else -1
+    H, W = int(image_height), int(image_width)
+    C = _check_contribution_args(stats, image_weights, P, H, W, dev)
+    if P == 0 or geomBuffer.numel() == 0:
+        return _no_contributions(H, W, dev, return_pixels)
+    for name, buf in (("geomBuffer", geomBuffer), ("binningBuffer", binningBuffer), ("imgBuffer", imgBuffer)):
+        _on_device(buf, name, dev, torch.uint8)
+    if C:
+        image_weights = _f32(image_weights, "image_weights", dev)
+    with torch.cuda.device(dev):
+        return _trace_contributions(dev, P, int(num_rendered), H, W, C, geomBuffer, binningBuffer, imgBuffer, image_weights,
+                                    stats, return_pixels, debug, flags)
+
+
+def trace_contributions(background, means3D, stats, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
+                        projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered,
+                        image_weights=None, return_pixels=False, debug=False, flags=None):
+    """The argument list of apply_weights with `stats` in place of `weights` and `cnt`: preprocesses and bins the view without
+    colours, exactly as apply_weights does, then gsr_trace_contributions (trace_contributions_state says what it computes)."""
+    flags = _flags(flags)
+    _check_means(means3D)
+    P, H, W = int(means3D.size(0)), int(image_height), int(image_width)
+    dev = means3D.device
+    C = _check_contribution_args(stats, image_weights, P, H, W, dev)
+    if P == 0:
+        return _no_contributions(H, W, dev, return_pixels)
+    _require_cuda(means3D, "means3D")
+    means3D, opacity, viewmatrix, projmatrix, scales, rotations, cov3D_precomp = _f32_all(
+        dev, means3D=means3D, opacity=opacity, viewmatrix=viewmatrix, projmatrix=projmatrix, scales=scales,
+        rotations=rotations, cov3D_precomp=cov3D_precomp)
+    if C:
+        image_weights = _f32(image_weights, "image_weights", dev)
+    radii = torch.empty((P,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        R, geom, binning, img = _preprocess_and_bin(dev, P, 0, 0, means3D, scales, float(scale_modifier), rotations,
+                                                    opacity, None, cov3D_precomp, None, viewmatrix, projmatrix, None,
+                                                    W, H, float(tan_fovx), float(tan_fovy), prefiltered, 1, radii, flags)
+        return _trace_contributions(dev, P, R, H, W, C, geom, binning, img, image_weights, stats, return_pixels, debug, flags)
+
+
 def arrays_equal(pairs) -> bool:
     """Extension (include/gsr.h: gsr_arrays_equal): are the (a, b) tensor pairs -- contiguous, same shape and dtype, on one
     ROCm device, at most 8 -- identical bit for bit?  One compare launch; blocks until the device has answered (~10 us)."""

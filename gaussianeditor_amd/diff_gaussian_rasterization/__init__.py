@@ -350,3 +350,21 @@ class GaussianRasterizer(nn.Module):
         _C.apply_weights(rs.bg, means3D, weights, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
                          rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, shs,
                          rs.sh_degree, rs.campos, rs.prefiltered, image_weights, cnt, rs.debug)
+
+    @torch.no_grad()
+    def trace_contributions(self, means3D, opacities, scales=None, rotations=None, cov3Ds_precomp=None, stats=None,
+                            image_weights=None, return_pixels=False):
+        """Extension (no reference counterpart): the contribution-weighted sibling of apply_weights.  Every pixel adds, for
+        every Gaussian i it would blend, its blending weight alpha T to `stats[i]` -- an int64 (P, 3 + C) table, accumulated
+        in place in integers (_C.trace_contributions_state states the columns) -- and, with `image_weights` (C,H,W), C <= 3,
+        the weight times the pixel's mask value per channel.  With `return_pixels` -> (top_id (H,W) int32, top_weight (H,W)
+        float32): the Gaussian under every pixel, by largest weight; else None.  Not differentiable."""
+        assert stats is not None
+        rs = self.raster_settings
+        scales = _absent(means3D) if scales is None else scales
+        rotations = _absent(means3D) if rotations is None else rotations
+        cov3Ds_precomp = _absent(means3D) if cov3Ds_precomp is None else cov3Ds_precomp
+        return _C.trace_contributions(rs.bg, means3D, stats, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
+                                      rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width,
+                                      _absent(means3D), rs.sh_degree, rs.campos, rs.prefiltered, image_weights=image_weights,
+                                      return_pixels=return_pixels, debug=rs.debug)

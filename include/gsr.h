@@ -510,6 +510,35 @@ int gsr_mark_visible(void* stream, int P, const float* means3D, const float* vie
 int gsr_trace_weights(void* stream, int P, int64_t R, int W, int H, int C, const void* geom, const void* binning,
                       const void* image, const float* image_weights, float* weights, int32_t* cnt, unsigned flags);
 
+/* Contribution statistics and the pick buffer of a binned view (no reference counterpart): K12's walk -- the cull, the skip
+ * rules (power > 0, alpha < 1/255) and the termination (T (1 - alpha) < 1e-4 ends the pixel before the entry counts) of
+ * gsr_blend_forward and gsr_trace_weights -- keeping the blending weight w = alpha T of every (pixel, Gaussian) the pixel
+ * blends, the quantity the forward composites with.  One launch on the state gsr_bin left, which is only read.
+ *   stats (P, 3 + C) int64, accumulated IN PLACE (the caller zeroes a fresh table), row g:
+ *     [0]     total_q        sum over the pixels that blend g of q(w), q(x) = (uint32) trunc(x * 2^32): units of 2^-32
+ *                            (w <= 0.99, so q fits 32 bits)
+ *     [1]     top_count      number of pixels whose top contributor (below) is g
+ *     [2]     max_bits       the largest w of g over all pixels, as the binary32 bit pattern zero-extended (w > 0: the
+ *                            integer order of the patterns is the order of the floats)
+ *     [3 + c] weighted_q[c]  sum of q(w * m_c), m_c = min(max(image_weights[c][pixel], 0), 1) with NaN -> 0, the product
+ *                            one binary32 multiply rounded to nearest
+ *   image_weights (C,H,W) float32, C in {0,1,2,3}: NULL if and only if C == 0; only read for pixels inside the image.
+ *   top_id (H,W) int32 and top_weight (H,W) float32, each optional (NULL) and FULLY written: the largest w over the entries
+ *     the pixel blends and that entry's Gaussian index; among equal weights the front-most entry of the tile's list wins;
+ *     -1 and 0 for a pixel that blends nothing (the pixels of empty tiles and of a view with R == 0 included).
+ * Every accumulation into `stats` is integer -- 64-bit adds, and a max for column 2; no float atomics --: two calls commute,
+ * and a call's result is the same bits on every launch grid, with every cut of the quadrants and in every arrival order.
+ * Rows no pixel hits are not touched; with R == 0 `stats` is not touched at all.
+ * Overflow: a Gaussian gains at most H * W * 2^32 per view in a sum column -- 2^53 at 1920 x 1080 -- of the 2^63 an int64
+ * holds, i.e. no column can overflow within 2^10 views at that size even for a Gaussian that fills every pixel of every view
+ * with w near 1 (the weights of a pixel sum to at most 1: all rows TOGETHER gain at most H * W * 2^32 per view).
+ * `flags`: the view flags gsr_trace_weights accepts.  Errors, before the device is touched: C outside {0,1,2,3} ->
+ * GSR_ERR_BAD_CHANNELS; unknown flags, NULL stats (or one not 8-byte aligned) or image, NULL image_weights with C > 0 or
+ * non-NULL with C == 0, negative sizes, NULL geom / binning with R > 0 -> GSR_ERR_BAD_ARGUMENT. */
+int gsr_trace_contributions(void* stream, int P, int64_t R, int W, int H, int C, const void* geom, const void* binning,
+                            const void* image, const float* image_weights, int64_t* stats, int32_t* top_id, float* top_weight,
+                            unsigned flags);
+
 /* ---- the simple-knn submodule -------------------------------------------------
  * mean_dist2[i] = mean of the squared distances from point i to its 3 nearest other points (exact), i.e.
  * `simple_knn._C.distCUDA2(points)` (gaussiansplatting/submodules/simple-knn/spatial.cu:15-25, simple_knn.cu:185-221),
