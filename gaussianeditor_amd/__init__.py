@@ -35,6 +35,11 @@ def __getattr__(name: str):
         from . import contrib
 
         return getattr(contrib, name)
+    # similarity transforms of Gaussians (transform.py), likewise
+    if name in ("transform_rows", "transform_gaussians"):
+        from . import transform
+
+        return getattr(transform, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

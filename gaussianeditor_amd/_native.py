@@ -150,6 +150,11 @@ SIGNATURES = {
                                 POINTER(McmcRecord)]),
     "gsr_mcmc_relocation_values": (c_int, [_P, c_int64, c_int64, _P, _P, _P, _P, ctypes.c_double, _P, _P]),
     "gsr_mcmc_scatter": (c_int, [_P, c_int64, c_int64, _P, _P, c_int64, c_int, POINTER(McmcTensor)]),
+    # similarity transforms (gaussianeditor_amd/transform.py): (rot[9], out[83]), host only; (stream, P, rest, xyz | NULL,
+    # rotation | NULL, scaling | NULL, sh_rest | NULL, mask | NULL, rot[9], trans[3], scale, scale_eps)
+    "gsr_sh_rotation": (c_int, [POINTER(ctypes.c_double), POINTER(ctypes.c_double)]),
+    "gsr_transform_rows": (c_int, [_P, c_int64, c_int, _P, _P, _P, _P, _P, POINTER(ctypes.c_double), POINTER(ctypes.c_double),
+                                   ctypes.c_double, ctypes.c_double]),
     "gsr_adam_step": (c_int, [_P, c_int, POINTER(AdamTensor), c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P,
                             _P]),
     "gsr_adam_step_rows": (c_int, [_P, c_int, POINTER(AdamTensor), c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P,

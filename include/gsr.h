@@ -75,7 +75,8 @@ extern "C" {
  * GSR_MAX_FEATURE_CHANNELS, gsr_blend_forward_features and gsr_blend_backward_features (the feature image; no new flag bit).
  * Then, likewise additive: gsr_mcmc_noise, gsr_mcmc_workspace_size, gsr_mcmc_sample, gsr_mcmc_relocation_values and
  * gsr_mcmc_scatter (the 3DGS-MCMC strategy; no new flag bit, nothing existing changed).  Then, likewise additive: the six
- * gsr_bilagrid_* entry points (the bilateral-grid slice and its TV regulariser; nothing existing changed). */
+ * gsr_bilagrid_* entry points (the bilateral-grid slice and its TV regulariser; nothing existing changed).  Then, likewise
+ * additive: gsr_sh_rotation and gsr_transform_rows (similarity transforms of Gaussians; nothing existing changed). */
 #define GSR_ABI_VERSION 6
 /* The blend backward's accumulator table: GSR_ACC_ROW floats (one 64-byte line) per Gaussian, 64-byte aligned.  Columns:
  *   [GSR_ACC_MEAN2D] .x [+1] .y of dL_dmean2D      (backward.cu:545-546)
@@ -835,6 +836,32 @@ typedef struct gsr_mcmc_tensor {
 } gsr_mcmc_tensor;
 int gsr_mcmc_scatter(void* stream, int64_t P, int64_t n, const int32_t* src, const int32_t* dst_idx, int64_t dst_rows,
                      int num_tensors, const gsr_mcmc_tensor* tensors);
+
+/* ---- similarity transforms of Gaussians, with the rotation of the SH coefficients ----
+ * The editing operation "move what was selected": T: x -> s R x + t, R a proper rotation, s > 0 uniform.  Per selected row,
+ * in binary64 from the binary32 inputs, rounded once at the store:
+ *   xyz (P,3):             xyz' = s R^ xyz + t
+ *   rotation (P,4) w,x,y,z RAW: q' = q_R (x) q, the Hamilton product; the raw norm is kept (the activation normalises)
+ *   scaling (P,3) RAW:     sigma' = log(exp(sigma) s + scale_eps)
+ *   sh_rest (P,rest,3), rest = 3, 8 or 15 (SH degree 1, 2, 3 without the DC term): for each band l and each channel
+ *                          c' = D^l c, D^l the (2l+1) x (2l+1) matrix with sum_m c'_m Y_m(R^ d) = sum_m c_m Y_m(d) for every
+ *                          unit d, Y the real basis of the rasterizer (its order and signs).  Band 0 is invariant.
+ * q_R is the unit quaternion of rot (row-major, x' = rot x) by Shepperd's method in binary64, w >= 0, and R^ = matrix(q_R)
+ * is what all four use: an exactly orthonormal rotation even where rot was rounded to binary32.  rot is refused
+ * (GSR_ERR_BAD_ARGUMENT) unless it is a proper rotation: the largest absolute row sum of rot^T rot - I at most 1e-4 and a
+ * positive determinant -- no reflections, no non-uniform scale.
+ * gsr_sh_rotation: host only, no device.  out[83] = D1 (9) | D2 (25) | D3 (49), row-major, of R^.  The identity gives
+ *   exactly the identity.
+ * gsr_transform_rows: in place, one launch, no workspace, no host synchronisation, any stream.  rot, trans and the numbers
+ *   are read before the call returns (they travel as kernel arguments: no host-to-device copy).  Any of the four tensors
+ *   may be NULL = untouched; 4-byte alignment is all they need (views at any float offset).  mask (P) u8 or NULL (all rows):
+ *   a row whose mask is 0 is NEVER stored to, not even with its own value.  No atomics: the same bits on every run.
+ *   P == 0 returns GSR_OK.  GSR_ERR_BAD_ARGUMENT, before the device is touched: all four tensors NULL, rest outside
+ *   {0, 3, 8, 15}, sh_rest with rest == 0, rot not a proper rotation, scale <= 0, scale_eps < 0, a number that is not
+ *   finite, a misaligned pointer.  A failed launch is GSR_ERR_HIP and gsr_last_hip_error() is not updated. */
+int gsr_sh_rotation(const double rot[9], double out[83]);
+int gsr_transform_rows(void* stream, int64_t P, int rest, float* xyz, float* rotation, float* scaling, float* sh_rest,
+                       const uint8_t* mask, const double rot[9], const double trans[3], double scale, double scale_eps);
 
 /* ---- the training loss: fused L1 + SSIM of two images, and its gradient ----
  * Replaces l1_loss / ssim of gaussiansplatting/utils/loss_utils.py:17-63 and the loss line of the reference's trainers,
