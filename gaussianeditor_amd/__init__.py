@@ -40,6 +40,11 @@ def __getattr__(name: str):
         from . import transform
 
         return getattr(transform, name)
+    # surface normals (normals.py), likewise
+    if name in ("gaussian_normals", "depth_to_normals", "normal_consistency_loss", "camera_intrinsics"):
+        from . import normals
+
+        return getattr(normals, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

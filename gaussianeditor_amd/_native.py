@@ -155,6 +155,19 @@ SIGNATURES = {
     "gsr_sh_rotation": (c_int, [POINTER(ctypes.c_double), POINTER(ctypes.c_double)]),
     "gsr_transform_rows": (c_int, [_P, c_int64, c_int, _P, _P, _P, _P, _P, POINTER(ctypes.c_double), POINTER(ctypes.c_double),
                                    ctypes.c_double, ctypes.c_double]),
+    # surface normals (gaussianeditor_amd/normals.py): (stream, P, rotations, scales, means3D, viewmatrix, out);
+    # (stream, P, rotations, scales, means3D, viewmatrix, dL_dout, dL_drotations);
+    # (stream, H, W, fx, fy, cx, cy, alpha_min, depth, alpha | NULL, out);
+    # (stream, H, W, fx, fy, cx, cy, alpha_min, depth, alpha | NULL, dL_dout, dL_ddepth | NULL, dL_dalpha | NULL); (H, W, bytes);
+    # (stream, H, W, fx, fy, cx, cy, alpha_min, normals, depth, alpha, workspace, out_loss);
+    # (stream, H, W, fx, fy, cx, cy, alpha_min, normals, depth, alpha, dL_dloss, dL_dnormals | NULL, dL_ddepth | NULL, dL_dalpha | NULL)
+    "gsr_gaussian_normals_forward": (c_int, [_P, c_int64] + [_P] * 5),
+    "gsr_gaussian_normals_backward": (c_int, [_P, c_int64] + [_P] * 6),
+    "gsr_depth_normals_forward": (c_int, [_P, c_int, c_int] + [ctypes.c_double] * 5 + [_P] * 3),
+    "gsr_depth_normals_backward": (c_int, [_P, c_int, c_int] + [ctypes.c_double] * 5 + [_P] * 5),
+    "gsr_normal_loss_workspace_size": (c_int, [c_int, c_int, POINTER(c_size_t)]),
+    "gsr_normal_loss_forward": (c_int, [_P, c_int, c_int] + [ctypes.c_double] * 5 + [_P] * 5),
+    "gsr_normal_loss_backward": (c_int, [_P, c_int, c_int] + [ctypes.c_double] * 5 + [_P] * 7),
     "gsr_adam_step": (c_int, [_P, c_int, POINTER(AdamTensor), c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P,
                             _P]),
     "gsr_adam_step_rows": (c_int, [_P, c_int, POINTER(AdamTensor), c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P,

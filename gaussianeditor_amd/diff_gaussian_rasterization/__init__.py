@@ -294,8 +294,8 @@ class GaussianRasterizer(nn.Module):
             return _C.mark_visible(positions, rs.viewmatrix, rs.projmatrix)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, aux_colors=None, return_alpha=False, features=None):
-        """Reference signature (:258-309) plus three extensions.  With `aux_colors` (P,3) a second image of the same
+                cov3D_precomp=None, aux_colors=None, return_alpha=False, features=None, return_normals=False):
+        """Reference signature (:258-309) plus four extensions.  With `aux_colors` (P,3) a second image of the same
         view, blended with those colours instead, is returned as a fourth value (forward only, no gradient).  It is
         what a second call with colors_precomp=aux_colors would render, at the cost of the blend kernel alone.
         With `return_alpha=True` the alpha image (1,H,W) -- accumulated opacity, 1 - the final transmittance -- is an
@@ -304,7 +304,11 @@ class GaussianRasterizer(nn.Module):
         composited with the view's alpha on background 0, every 16 channels in one walk of the tile lists -- is appended
         as the LAST value: (color, radii, depth[, aux][, alpha], feature_image).  It is differentiable with respect to
         `features`, means3D, means2D, opacities and scales / rotations / cov3D_precomp, not with respect to shs /
-        colors_precomp.  The arity depends on these three arguments alone, never on process state."""
+        colors_precomp.  With `return_normals=True` the normal image (3,H,W) -- the camera-space normal of every Gaussian
+        (gaussianeditor_amd.normals.gaussian_normals of this view), composited like a feature -- is appended behind all of
+        them: (color, radii, depth[, aux][, alpha][, feature_image], normals), with a gradient to the rotations and the
+        geometry.  It rides the feature route (three more channels behind the caller's, so C <= 253 then) and needs
+        scales / rotations, not cov3D_precomp.  The arity depends on these four arguments alone, never on process state."""
         if (shs is None) == (colors_precomp is None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")  # sic, :271-276
         has_sr = scales is not None or rotations is not None
@@ -316,6 +320,9 @@ class GaussianRasterizer(nn.Module):
         scales = _absent(means3D) if scales is None else scales
         rotations = _absent(means3D) if rotations is None else rotations
         cov3D_precomp = _absent(means3D) if cov3D_precomp is None else cov3D_precomp
+        if return_normals:
+            return self._forward_with_normals(means3D, means2D, opacities, shs, colors_precomp, scales, rotations,
+                                              cov3D_precomp, aux_colors, return_alpha, features)
         if features is not None:
             if not isinstance(features, torch.Tensor) or features.dtype != torch.float32:
                 raise RuntimeError("diff_gaussian_rasterization: `features` must be a float32 tensor, got "
@@ -333,6 +340,33 @@ class GaussianRasterizer(nn.Module):
                                                 cov3D_precomp, self.raster_settings, aux_colors, return_alpha)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                                    self.raster_settings, return_alpha)
+
+    def _forward_with_normals(self, means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp,
+                              aux_colors, return_alpha, features):
+        """forward(..., return_normals=True): the Gaussian normals of this view as the last three feature channels, split
+        off again.  Absent arguments arrive as empty tensors."""
+        from .. import normals as _normals
+
+        if cov3D_precomp.numel() != 0:
+            raise RuntimeError("diff_gaussian_rasterization: `return_normals` needs scales and rotations; a precomputed 3D "
+                               "covariance has no axes to take a normal from")
+        C = 0
+        if features is not None:
+            if not isinstance(features, torch.Tensor) or features.dim() != 2:
+                raise RuntimeError("diff_gaussian_rasterization: `features` must be a (P, C) float32 tensor")
+            C = int(features.shape[1])
+            if C + 3 > 256:
+                raise RuntimeError(f"diff_gaussian_rasterization: `return_normals` takes three of the 256 feature channels: "
+                                   f"`features` may have at most 253 with it, got {C}")
+        nrm = _normals.gaussian_normals(rotations.contiguous(), scales.contiguous(), means3D.contiguous(),
+                                        self.raster_settings.viewmatrix.contiguous())
+        feats = nrm if features is None else torch.cat([features, nrm], dim=1)
+        outs = self.forward(means3D, means2D, opacities, shs=shs if shs.numel() else None,
+                            colors_precomp=colors_precomp if colors_precomp.numel() else None, scales=scales,
+                            rotations=rotations, aux_colors=aux_colors, return_alpha=return_alpha, features=feats)
+        if features is None:
+            return outs
+        return outs[:-1] + (outs[-1][:C], outs[-1][C:])
 
     def apply_weights(self, means3D, means2D, opacities, shs=None, weights=None, scales=None, rotations=None,
                       cov3Ds_precomp=None, cnt=None, image_weights=None):

@@ -68,7 +68,7 @@ def camera2rasterizer(viewpoint_camera, bg_color: torch.Tensor, sh_degree: int =
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
-           semantic_color=None, return_alpha=None, features=None):
+           semantic_color=None, return_alpha=None, features=None, return_normals=False):
     """gaussian_renderer/__init__.py:45-150.  Background tensor must be on the GPU.
 
     Extension: `semantic_color` (P,3) adds out["semantic"], the image the reference obtains from a SECOND
@@ -78,7 +78,12 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     (None: as FLAG_ALPHA_OUT of the calling thread says, gaussianeditor_amd.set_alpha_output; off by default).
     Extension: `features` (P,C) float32, 1 <= C <= 256, adds out["features"], the (C,H,W) image of those per-Gaussian
     features composited with this view's alpha on background 0, differentiable with respect to the features and the
-    geometry (GaussianRasterizer.forward)."""
+    geometry (GaussianRasterizer.forward).
+    Extension: `return_normals=True` adds out["normals"], the (3,H,W) image of the Gaussians' camera-space normals
+    (gaussianeditor_amd.normals.gaussian_normals: the shortest axis, turned towards the camera) composited with this view's
+    alpha on background 0, with a gradient to the rotations and the geometry; what normals.normal_consistency_loss takes.
+    It takes three of the 256 feature channels (`features` may have at most 253 with it) and is refused with
+    pipe.compute_cov3D_python."""
     if return_alpha is None:
         return_alpha = bool(_options.current_flags() & _options.FLAG_ALPHA_OUT)
     xyz = pc.get_xyz
@@ -122,6 +127,7 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         **({} if semantic_color is None else {"aux_colors": semantic_color.float()}),
         **({"return_alpha": True} if return_alpha else {}),
         **({} if features is None else {"features": features}),
+        **({"return_normals": True} if return_normals else {}),
     )
     rendered_image, radii, depth = outs[:3]
     out = {
@@ -133,10 +139,13 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     }
     if semantic_color is not None:
         out["semantic"] = outs[3]
+    tail = 1 if return_normals else 0  # (the normal image is the last value, the feature image in front of it)
     if return_alpha:
-        out["alpha"] = outs[-1 if features is None else -2]
+        out["alpha"] = outs[-1 - tail - (0 if features is None else 1)]
     if features is not None:
-        out["features"] = outs[-1]
+        out["features"] = outs[-1 - tail]
+    if return_normals:
+        out["normals"] = outs[-1]
     return out
 
 

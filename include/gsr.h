@@ -76,7 +76,9 @@ extern "C" {
  * Then, likewise additive: gsr_mcmc_noise, gsr_mcmc_workspace_size, gsr_mcmc_sample, gsr_mcmc_relocation_values and
  * gsr_mcmc_scatter (the 3DGS-MCMC strategy; no new flag bit, nothing existing changed).  Then, likewise additive: the six
  * gsr_bilagrid_* entry points (the bilateral-grid slice and its TV regulariser; nothing existing changed).  Then, likewise
- * additive: gsr_sh_rotation and gsr_transform_rows (similarity transforms of Gaussians; nothing existing changed). */
+ * additive: gsr_sh_rotation and gsr_transform_rows (similarity transforms of Gaussians; nothing existing changed).  Then,
+ * likewise additive: gsr_gaussian_normals_forward / _backward, gsr_depth_normals_forward / _backward,
+ * gsr_normal_loss_workspace_size and gsr_normal_loss_forward / _backward (surface normals; nothing existing changed). */
 #define GSR_ABI_VERSION 6
 /* The blend backward's accumulator table: GSR_ACC_ROW floats (one 64-byte line) per Gaussian, 64-byte aligned.  Columns:
  *   [GSR_ACC_MEAN2D] .x [+1] .y of dL_dmean2D      (backward.cu:545-546)
@@ -862,6 +864,61 @@ int gsr_mcmc_scatter(void* stream, int64_t P, int64_t n, const int32_t* src, con
 int gsr_sh_rotation(const double rot[9], double out[83]);
 int gsr_transform_rows(void* stream, int64_t P, int rest, float* xyz, float* rotation, float* scaling, float* sh_rest,
                        const uint8_t* mask, const double rot[9], const double trans[3], double scale, double scale_eps);
+
+/* ---- surface normals: per Gaussian, from the depth image, and the loss that ties them together ----
+ * Conventions.  viewmatrix: the 16 floats the rasterizer takes (the transposed view matrix V, row 3 the translation): the
+ * view-space point is p_c = p_w V[:3,:3] + V[3,:3], axes as COLMAP (z forward), and the depth of a Gaussian is p_c.z.
+ * Pixel (x, y) (column, row; integers) lies on the ray r(x,y) = ((x - cx) / fx, (y - cy) / fy, 1); what ndc2Pix implies is
+ * fx = W / (2 tanfovx), fy = H / (2 tanfovy), cx = (W - 1) / 2, cy = (H - 1) / 2.  Every normal is in camera space and
+ * points towards the camera (n . p_c < 0).  Inputs and outputs are binary32, the arithmetic is binary64, rounded once at
+ * the store; no atomics, every sum in a fixed order: the same bits on every run and on every stream.
+ *
+ * (a) The normal of a Gaussian.  rotations (P,4) w,x,y,z RAW, scales (P,3), means3D (P,3), out (P,3):
+ *   q^ = q / |q|;  k = argmin_j scales[j], on a tie the lowest index;  n_w = column k of R(q^), R as the reference's
+ *   build_rotation;  n_c = n_w V[:3,:3];  s = -1 if n_c . p_c > 0 else +1;  out = s n_c.
+ *   The backward, from dL_dout (P,3), writes dL_drotations (P,4): through column k and through the normalisation, so it is
+ *   orthogonal to q; k and s are recomputed from the inputs (no saved state).  scales, means3D and the camera get no
+ *   gradient: the output is piecewise constant in them.  A precomputed covariance is not supported.
+ *
+ * (b) The normal of the depth image.  depth (1,H,W); alpha (1,H,W) or NULL; out (3,H,W), planar.
+ *   z = depth / max(alpha, 1e-8) with alpha (depth is then the unnormalised sum of z w), z = depth without;
+ *   p(x,y) = z(x,y) r(x,y);  c = (p(x,y+1) - p(x,y-1)) x (p(x+1,y) - p(x-1,y));  n = c / |c|
+ *   (central differences; with this operand order the camera-facing normal, exact on a plane under perspective).
+ *   out is exactly (0,0,0) at an invalid pixel: one on the image border, one whose centre or any of whose four taps has
+ *   alpha <= alpha_min (with alpha) or z <= 0, or one with |c|^2 < 1e-30.  The normal depends on the four taps, not on the
+ *   centre.  The backward, from dL_dout (3,H,W), writes dL_ddepth and dL_dalpha (1,H,W) (through z only; the validity mask
+ *   carries no gradient): each depth pixel gathers the terms of the up to four normals around it.  Either may be NULL: it
+ *   is then not computed (both NULL: nothing is launched); dL_dalpha without alpha is refused.
+ *
+ * (c) The consistency loss.  normals N (3,H,W): the alpha-composited normal image (|N| <= A); depth, alpha (1,H,W) as in
+ *   (b), alpha required: it is also the weight A.
+ *   loss = 1 / (H W) sum over the valid pixels of (A - <N, n_d>),  n_d of (b), never written to memory.
+ *   Every term is >= 0 and equals A (1 - <N / A, n_d>).  The normalisation is H W, not the number of valid pixels: the loss
+ *   does not jump when a pixel changes validity.  out_loss: one device float.  workspace: gsr_normal_loss_workspace_size
+ *   bytes of device scratch, 8-byte aligned (one partial sum per tile, added in ascending order).
+ *   The backward reads dL_dloss, ONE device float (the host neither waits nor reads anything back), and writes
+ *   dL_dnormals (3,H,W) = -dL_dloss / (H W) n_d at valid pixels, 0 elsewhere, and dL_ddepth, dL_dalpha (1,H,W) through n_d;
+ *   the explicit A term gives no gradient (a constant weight).  Any of the three may be NULL: it is then not computed.
+ *
+ * All seven: the caller owns every buffer and every output element is written (no pre-zeroing); the caller's stream, no
+ * host synchronisation.  P == 0 and images without interior pixels (H < 3 or W < 3) are valid: outputs fully written, zeros.
+ * GSR_ERR_BAD_ARGUMENT, before the device is touched: P < 0 or > 2^31 - 1, H or W < 1, H W > 2^31 - 1, H > 524 280, fx or fy
+ * not finite and positive, cx, cy or alpha_min not finite, a required pointer NULL (P > 0 for (a)), a pointer of (a) that is
+ * not 4-byte aligned, a misaligned workspace.  A failed launch is GSR_ERR_HIP and gsr_last_hip_error() is not updated. */
+int gsr_gaussian_normals_forward(void* stream, int64_t P, const float* rotations, const float* scales, const float* means3D,
+                                 const float* viewmatrix, float* out);
+int gsr_gaussian_normals_backward(void* stream, int64_t P, const float* rotations, const float* scales, const float* means3D,
+                                  const float* viewmatrix, const float* dL_dout, float* dL_drotations);
+int gsr_depth_normals_forward(void* stream, int H, int W, double fx, double fy, double cx, double cy, double alpha_min,
+                              const float* depth, const float* alpha, float* out);
+int gsr_depth_normals_backward(void* stream, int H, int W, double fx, double fy, double cx, double cy, double alpha_min,
+                               const float* depth, const float* alpha, const float* dL_dout, float* dL_ddepth, float* dL_dalpha);
+int gsr_normal_loss_workspace_size(int H, int W, size_t* bytes);
+int gsr_normal_loss_forward(void* stream, int H, int W, double fx, double fy, double cx, double cy, double alpha_min,
+                            const float* normals, const float* depth, const float* alpha, void* workspace, float* out_loss);
+int gsr_normal_loss_backward(void* stream, int H, int W, double fx, double fy, double cx, double cy, double alpha_min,
+                             const float* normals, const float* depth, const float* alpha, const float* dL_dloss,
+                             float* dL_dnormals, float* dL_ddepth, float* dL_dalpha);
 
 /* ---- the training loss: fused L1 + SSIM of two images, and its gradient ----
  * Replaces l1_loss / ssim of gaussiansplatting/utils/loss_utils.py:17-63 and the loss line of the reference's trainers,
