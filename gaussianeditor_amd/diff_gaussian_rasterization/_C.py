@@ -178,6 +178,19 @@ class PendingForward:
     the native ticket of its counts."""
     __slots__ = ("dev", "stream", "P", "H", "W", "flags", "debug", "background", "radii", "geom", "ticket", "keep")
 
+    def cancel(self) -> None:
+        """Give up a view that will not be finished (a step that raised between begin and finish): the native ticket -- a
+        pinned host slot of the library's pool, which only gsr_preprocess_end returns -- is spent on the stream the view
+        began on, and nothing else of the view is enqueued.  No-op on a finished or cancelled view."""
+        if self.ticket is None:
+            return
+        ticket, self.ticket = self.ticket, None  # (spent by the native call whatever it returns)
+        counts = (ctypes.c_int64 * 2)()
+        with torch.cuda.device(self.dev):
+            _native.check("gsr_preprocess_end", _native.lib().gsr_preprocess_end(
+                self.stream, self.P, self.W, self.H, self.geom.data_ptr(), ticket, counts))
+        self.keep = None
+
 
 def rasterize_gaussians_begin(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                               viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,

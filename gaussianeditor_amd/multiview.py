@@ -51,8 +51,9 @@ import threading as _threading
 
 #: GSR_VIEW_PIPELINE=0: multiview_batch_step renders its views one after the other on the launch stream (default: two streams)
 _VIEW_PIPELINE = _os.environ.get("GSR_VIEW_PIPELINE", "1") != "0"
-#: GSR_VIEW_AHEAD: how many views' forwards the pipelined batch finishes ahead of the backward it issues (0 or 1; one stream
-#: per view in flight)
+#: GSR_VIEW_AHEAD: how many views' forwards the pipelined batch finishes ahead of the backward it issues (0, 1 or 2: 2, 3 or 4
+#: view streams, one per view in flight; other values are clamped to that range.  Every value gives the same results:
+#: tests/test_gpu_view_batch.py runs all three against per-view references)
 _VIEW_AHEAD = max(0, min(2, int(_os.environ.get("GSR_VIEW_AHEAD", "0"))))
 
 #: The helper streams of this module, ONE set per device and process, shared by every GradBucket: torch's caching allocator
@@ -704,41 +705,50 @@ def _batch_step(settings_list, params, dL_dcolor_list, bucket, group, marks, spe
                 # the launch thread never waits for a view's counts: a view's K1 is enqueued at least one backward before its
                 # binning (include/gsr.h gsr_preprocess_begin / _end; until round 6 the thread spent a K1 per view spinning
                 # and the batch was bound by the host, not by the GPU: profiles/r06_i_view_pipelining.md)
-                begin(0)
-                for u in range(1, min(ahead + 1, k_local)):
-                    begin(u)
-                for u in range(0, min(ahead, k_local)):
-                    finish(u)
                 packed_prev, all_radii = None, []
-                for v in range(k_local):
-                    if v + ahead < k_local:
-                        finish(v + ahead)
-                    if v + ahead + 1 < k_local:
-                        begin(v + ahead + 1)
-                    fstate = fstates.pop(v)
-                    with torch.cuda.stream(S[v % ns]):
-                        # the bucket is free once view v - 1's message holds its rows.  K7 writes the stream's accumulator
-                        # table and its row mask, not the bucket, so the wait sits between K7 and K8+K9 (in after_blend),
-                        # except on the L1 route, whose backward runs on the autograd engine's thread
-                        if packed_prev is not None:
-                            if len(fstate[3]) == 6:
-                                S[v % ns].wait_event(packed_prev)
-                            else:
-                                state["bucket_free"] = packed_prev
-                        _view_backward(settings_list[v], fstate, dL_dcolor_list[v], bucket)
-                        if state.pop("bucket_free", None) is not None:
-                            raise RuntimeError("multiview_batch_step: the backward did not announce its blend half "
-                                               "(after_blend_backward); the bucket may have been overwritten too early")
-                        colors.append(fstate[0].detach())
-                        depths.append(fstate[2].detach())
-                        all_radii.append(fstate[1])
-                        if state["planned"] is not None:
-                            S[v % ns].wait_event(state["planned"])
-                        _C.view_message_pack(state["plan"], grads5, bucket.rgb, bucket.campos, cap, send[v])
-                        packed_prev = torch.cuda.Event()
-                        packed_prev.record(S[v % ns])
-                for st_ in S:
-                    main.wait_stream(st_)
+                try:
+                    begin(0)
+                    for u in range(1, min(ahead + 1, k_local)):
+                        begin(u)
+                    for u in range(0, min(ahead, k_local)):
+                        finish(u)
+                    for v in range(k_local):
+                        if v + ahead < k_local:
+                            finish(v + ahead)
+                        if v + ahead + 1 < k_local:
+                            begin(v + ahead + 1)
+                        fstate = fstates.pop(v)
+                        with torch.cuda.stream(S[v % ns]):
+                            # the bucket is free once view v - 1's message holds its rows.  K7 writes the stream's accumulator
+                            # table and its row mask, not the bucket, so the wait sits between K7 and K8+K9 (in after_blend),
+                            # except on the L1 route, whose backward runs on the autograd engine's thread
+                            if packed_prev is not None:
+                                if len(fstate[3]) == 6:
+                                    S[v % ns].wait_event(packed_prev)
+                                else:
+                                    state["bucket_free"] = packed_prev
+                            _view_backward(settings_list[v], fstate, dL_dcolor_list[v], bucket)
+                            if state.pop("bucket_free", None) is not None:
+                                raise RuntimeError("multiview_batch_step: the backward did not announce its blend half "
+                                                   "(after_blend_backward); the bucket may have been overwritten too early")
+                            colors.append(fstate[0].detach())
+                            depths.append(fstate[2].detach())
+                            all_radii.append(fstate[1])
+                            if state["planned"] is not None:
+                                S[v % ns].wait_event(state["planned"])
+                            _C.view_message_pack(state["plan"], grads5, bucket.rgb, bucket.campos, cap, send[v])
+                            packed_prev = torch.cuda.Event()
+                            packed_prev.record(S[v % ns])
+                finally:
+                    # a step that raised between a view's begin and its finish: the forwards still pending hold a native
+                    # ticket each (a pinned host slot only gsr_preprocess_end returns) -- give them back; and whatever the
+                    # view streams still run is in front of what the caller enqueues next (it may touch the bucket)
+                    for b in begun.values():
+                        if b[0] == "split":
+                            b[1].cancel()
+                    begun.clear()
+                    for st_ in S:
+                        main.wait_stream(st_)
                 radii_max = all_radii[0].clone()
                 for r in all_radii[1:]:
                     torch.maximum(radii_max, r, out=radii_max)
@@ -757,8 +767,8 @@ def _batch_step(settings_list, params, dL_dcolor_list, bucket, group, marks, spe
             else:
                 if state["done"] is not None:
                     state["done"].synchronize()  # the side stream only: this view's K8+K9 still runs on the launch stream
-                c = max(int(state["count"].item()), 1)
-                counts.append(c)
+                counts.append(int(state["count"].item()))  # (the true count, 0 for a view that sees nothing: last_counts)
+                c = max(counts[-1], 1)
                 m = torch.empty(_C.view_message_words(P, c), dtype=torch.float32, device=dev)
                 _C.view_message_pack(state["plan"], grads5, bucket.rgb, bucket.campos, c, m)
                 tight.append((m, c))
@@ -811,7 +821,8 @@ def _batch_step(settings_list, params, dL_dcolor_list, bucket, group, marks, spe
     if multi:
         dist.all_reduce(radii_max, op=dist.ReduceOp.MAX, group=group)
     bucket.last_counts = all_counts
-    bucket._cap_hint = (int(1.5 * max(max(all_counts), 1)) + 1023) // 1024 * 1024  # identical on every rank
+    # ceil(1.5 x the largest count / 1024) x 1024, in integers (int(1.5 x) dropped the half row: 1024 for a count of 683)
+    bucket._cap_hint = -(-3 * max(max(all_counts), 1) // 2048) * 1024  # identical on every rank
     sh = torch.empty((P, bucket.M, 3), dtype=torch.float32, device=dev)
     _C.view_messages_accumulate(recv, P, cap, bucket.sh_degree, bucket.M, bucket.means3D_ref, grads5 + [sh],
                                 row_valid=bucket.row_valid)
