@@ -100,6 +100,11 @@ SIGNATURES = {
     # (stream, P, R, W, H, C, geom, binning, image, features, dL_dfeature_image (C,H,W), acc, dL_dfeatures (P,C), flags)
     "gsr_blend_forward_features": (c_int, [_P, c_int, c_int64, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_uint]),
     "gsr_blend_backward_features": (c_int, [_P, c_int, c_int64, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_uint]),
+    # distortion image: (stream, P, R, W, H, geom, binning, image, near, far, out (H,W), moments (H,W,4) | NULL, flags); its
+    # backward: (stream, P, R, W, H, geom, binning, image, near, far, moments, dL_ddistortion (H,W), acc, flags)
+    "gsr_blend_forward_distortion": (c_int, [_P, c_int, c_int64, c_int, c_int, _P, _P, _P, c_float, c_float, _P, _P, c_uint]),
+    "gsr_blend_backward_distortion": (c_int, [_P, c_int, c_int64, c_int, c_int, _P, _P, _P, c_float, c_float, _P, _P, _P,
+                                              c_uint]),
     # (... radii, geom, acc, dL_dmeans2D, dL_dopacity, dL_dcolors, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drots, flags)
     "gsr_preprocess_backward": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_float, _P, _P, _P, _P, _P,
                                         c_float, c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_uint]),

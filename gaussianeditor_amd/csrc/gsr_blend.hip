@@ -2101,6 +2101,302 @@ feature_backward_kernel(const BlendArgs a, const FeatureArgs f) {
   if (a.self_reset && threadIdx.x == 0) retire_queue(a.queue);
 }
 
+// ----------------------------------------------------------------------------------
+// The depth-distortion image (gsr_blend_forward_distortion) and its backward (gsr_blend_backward_distortion): the
+// regulariser of Mip-NeRF 360 / 2DGS, per pixel D = 1/2 sum_{i != j} w_i w_j (m_i - m_j)^2 = A M2 - M1^2 with w = alpha T,
+// A = sum w, M1 = sum w m, M2 = sum w m^2 over the entries the colour image blends.  No reference counterpart.
+// m is the entry's view-space depth z (rec1.z, what the depth image blends), or 2DGS's mapping f (z - n) / ((f - n) z) of it.
+// D does not change under m -> m - m0: the moments are accumulated of m' = m - m(z0), z0 the depth of the pixel's FIRST
+// blended entry, formed from the difference of the z's -- linear: z - z0; mapped: kappa (z - z0) / (z0 z), kappa = f n / (f - n)
+// -- so that A M2' - M1'^2 does not cancel on a thin surface far from the camera (the unshifted float32 moments lose D
+// entirely at depth 50, spread 0.05).  One code path for both depths: m' = (kz0 (z - z0)) rz with
+// kz0 = 1, rz = 1 (linear: exact) or kz0 = kappa / z0, rz = 1 / z (mapped).
+// The forward saves (z0, A, M1', M2') per pixel; with them the backward needs no second pass:
+//   dD/dw_k = m'_k^2 A + M2' - 2 m'_k M1' =: c_k,   dD/dm_k = 2 w_k (m'_k A - M1'),   nothing reaches z0 (shift invariance),
+//   dL/dalpha_k = T_k (gD c_k - rec_k): K7's recurrence with the scalar gD c_k in the place of the collapsed colour, background 0.
+// What is new beside a view's BlendArgs travels as a second kernel argument, as FeatureArgs does.
+// ----------------------------------------------------------------------------------
+struct DistortionArgs {
+  float* out;               // forward: (H,W), fully written
+  float4* moments;          // forward: (H,W) (z0, A, M1', M2'), fully written | null
+  const float4* moments_in; // backward: what the forward saved
+  const float* dL_dD;       // backward: (H,W), the gradient of `out`
+  float kappa;              // mapped depth: f n / (f - n); linear: unused
+  int mapped;
+};
+
+template <bool FAST>
+__device__ __forceinline__ void distortion_forward_item(const BlendArgs& a, const DistortionArgs& f, uint32_t tile, uint32_t quad) {
+  PixelWave pw;
+  ItemBox box;
+  if (!setup_item<1>(a, tile, quad, pw, box)) return;
+  (void)box;
+  const uint2 range = a.ranges[pw.tile];
+  const size_t pix = (size_t)pw.py * a.W + pw.px;
+  __shared__ __align__(16) float2 szr[WAVE];  // (z, rz) of the chunk's survivors
+  const bool mapped = f.mapped != 0;
+  const float kappa = wave_uniform(f.kappa);
+  bool have = false;
+  float z0 = 0.f, kz0 = 1.0f, A = 0.f, M1 = 0.f, M2 = 0.f;
+  walk_front_to_back<FAST>(
+      a, pw, range,
+      [&](uint32_t slot, const Entry& e) __attribute__((always_inline)) {
+        szr[slot] = make_float2(e.r1.z, mapped ? 1.0f / e.r1.z : 1.0f);
+      },
+      [&](uint32_t j, const bool(&hit)[GROUP], const float(&w)[GROUP]) __attribute__((always_inline)) {
+        const float4 p01 = *reinterpret_cast<const float4*>(&szr[j]), p23 = *reinterpret_cast<const float4*>(&szr[j + 2]);
+        const float zs[GROUP] = {p01.x, p01.z, p23.x, p23.z}, rs[GROUP] = {p01.y, p01.w, p23.y, p23.w};
+#pragma unroll
+        for (int u = 0; u < GROUP; ++u) {
+          if (hit[u]) {  // the pixel blends the entry: w = alpha T (a lane-masked region, as the feature forward's)
+            if (!have) {
+              have = true;
+              z0 = zs[u];
+              if (mapped) kz0 = kappa / z0;
+            }
+            const float m = (kz0 * (zs[u] - z0)) * rs[u];
+            A += w[u];
+            M1 = __builtin_fmaf(w[u], m, M1);
+            M2 = __builtin_fmaf(w[u] * m, m, M2);
+          }
+        }
+      },
+      [](uint32_t) __attribute__((always_inline)) {});
+  if (pw.inside) {
+    f.out[pix] = __builtin_fmaf(A, M2, -(M1 * M1));
+    if (f.moments != nullptr) f.moments[pix] = make_float4(z0, A, M1, M2);
+  }
+}
+template <bool FAST>
+__global__ void __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(4, 4)))
+distortion_forward_kernel(const BlendArgs a, const DistortionArgs f) {
+  run_work_queue<1>(a, true, [&](uint32_t tile, uint32_t quad, bool empty) __attribute__((always_inline)) {
+    if (!empty) {
+      distortion_forward_item<FAST>(a, f, tile, quad);
+    } else {  // a tile no Gaussian touches: zeros
+      for_each_pixel_of_tile(a, tile, [&](size_t pix, size_t) __attribute__((always_inline)) {
+        f.out[pix] = 0.f;
+        if (f.moments != nullptr) f.moments[pix] = make_float4(0.f, 0.f, 0.f, 0.f);
+      });
+    }
+  });
+}
+
+// The distortion backward: K7's workgroup (the four quadrant waves of a tile, or of half a heavy one), walking the first
+// n_contrib entries of every pixel back to front from final_T, as the feature backward does: no checkpoints, a work list
+// without list segments.  Per entry a wave reduces SEVEN raw moments: K7's six geometry moments of q = G dL/dalpha and the
+// depth moment gD 2 w (m' A - M1'); the four waves add them into one LDS row per chunk slot (rows of 9 floats: odd), and the
+// flush -- deferred by a chunk -- is ONE memory-side request per (tile, Gaussian) into the columns ACC_MEAN2D, ACC_OPACITY,
+// ACC_CONIC and ACC_DEPTH of the Gaussian's accumulator row; the depth column takes the moment times mu = dm/dz, a constant
+// of the entry (1, or kappa / z^2).  ACC_COLOR and ACC_ABS2D are not written.
+constexpr int DIST_NM = 7;
+constexpr int DIST_LDS_ROW = 9;
+static_assert(pack_lanes<DIST_NM>().ok, "every moment of every entry reaches a lane");
+
+template <bool FAST>
+__device__ __forceinline__ void distortion_backward_tile(const BlendArgs& a, const DistortionArgs& f, const uint4 item,
+                                                         float4 (*s0)[WAVE], float4 (*s1)[WAVE], uint32_t (*sid)[WAVE],
+                                                         float4 (*sco)[WAVE], float2 (*szr)[WAVE],
+                                                         float (*sacc)[WAVE][DIST_LDS_ROW]) {
+  const int w = (int)(threadIdx.x >> 6), lane = lane_id();
+  constexpr PackLanes tg = pack_lanes<DIST_NM>();
+  auto bit = [lane](uint64_t plane) __attribute__((always_inline)) { return (uint32_t)(plane >> (uint32_t)lane) & 1u; };
+  const uint32_t g_term = bit(tg.term_bit[0]) | bit(tg.term_bit[1]) << 1 | bit(tg.term_bit[2]) << 2 | bit(tg.term_bit[3]) << 3;
+  const uint32_t g_entry = bit(tg.entry_bit[0]) | bit(tg.entry_bit[1]) << 1;
+  const bool g_adds = bit(tg.adds) != 0u;
+  // the item: a whole tile (wave w = quadrant w) or half of one (K7's item codes; the work list is built without segments)
+  uint32_t tile = item.x;
+  const bool half_item = (tile & BWD_ITEM_HALF) != 0u;
+  const uint32_t part = (tile & BWD_ITEM_PART) ? 1u : 0u;
+  tile &= BWD_ITEM_TILE;
+  const uint32_t list_base = item.y, tile_max = item.z;
+  if (tile_max == 0) return;  // (uniform: nothing of the item's pixels ever contributed)
+  PixelWave pw;
+  const bool has_pixels = setup_wave(a, tile, half_item ? 2u * part + (uint32_t)(w >> 1) : (uint32_t)w, pw);
+  const float pfx = (float)pw.px, pfy = (float)pw.py;
+  const float qx0 = (float)(pw.px - (lane & 7)), qy0 = (float)(pw.py - (lane >> 3));
+  if (half_item) pw.inside = pw.inside && ((lane >> 5) == (w & 1));
+  const bool live = has_pixels && pw.inside;
+  // per-pixel inputs: unconditional loads (a lane without a pixel reads pixel 0 and drops the values)
+  const size_t pix = live ? (size_t)pw.py * a.W + pw.px : (size_t)0;
+  const float T_final_ld = a.final_T[pix];
+  const uint32_t n_contrib_ld = a.n_contrib[pix];
+  const float4 mom_ld = f.moments_in[pix];
+  const float gD_ld = f.dL_dD[pix];
+  ChunkWalker<false> walk(a, list_base, tile_max);
+  const float T_final = live ? T_final_ld : 0.f;
+  const uint32_t last_contributor = live ? n_contrib_ld : 0u;
+  const uint32_t maxc = wave_max_u32_dpp(last_contributor);
+  const float gD = live ? gD_ld : 0.f;
+  const bool mapped = f.mapped != 0;
+  const float kappa = wave_uniform(f.kappa);
+  const float z0 = live ? mom_ld.x : 0.f, A = live ? mom_ld.y : 0.f, M1 = live ? mom_ld.z : 0.f, M2 = live ? mom_ld.w : 0.f;
+  const float kz0 = mapped ? (z0 > 0.f ? kappa / z0 : 0.f) : 1.0f;  // (z0 = 0: the pixel blends nothing)
+  const float nM1x2 = -2.0f * M1;
+  const float ddelx_dx = 0.5f * a.W, ddely_dy = 0.5f * a.H;
+  const uint64_t lt_mask = (1ull << lane) - 1ull;
+  float T = T_final;
+  float B_acc = 0.f, last_cdot = 0.f, last_alpha = 0.f;
+
+  auto flush = [&](uint32_t fb, uint32_t fsize) __attribute__((always_inline)) {
+    const uint32_t col = (uint32_t)lane & 15u, sub = (uint32_t)lane >> 4;
+    // raw moments a column reads (K7's flush): dL_dmean2D (1, 2); opacity 0; conic x / y / w: 3 / 4 / 5; depth 6
+    const uint32_t ia = col == ACC_MEAN2D || col == ACC_MEAN2D + 1u ? 1u
+                        : col == ACC_OPACITY ? 0u
+                        : col == ACC_CONIC ? 3u : col == ACC_CONIC + 1u ? 4u : col == ACC_CONIC + 3u ? 5u
+                        : col == ACC_DEPTH ? 6u
+                        : (uint32_t)DIST_NM;  // DIST_NM: the column is not written
+#pragma unroll
+    for (uint32_t jj = 0; jj < 4u; ++jj) {
+      const uint32_t p = 16u * (uint32_t)w + 4u * jj + sub;
+      if (16u * (uint32_t)w + 4u * jj >= fsize) break;  // (wave-uniform)
+      const bool in = p < fsize;
+      float* const row = sacc[fb][in ? p : 0u];
+      const bool used = in && ia < (uint32_t)DIST_NM;
+      const float ma = used ? row[ia] : 0.f;
+      const float mb = used && ia == 1u ? row[2] : 0.f;
+      const float4 co = sco[fb][in ? p : 0u];  // conic.x, conic.y, conic.z, opacity
+      const float rz = szr[fb][in ? p : 0u].y;
+      const size_t id = sid[fb][in ? p : 0u];
+      float val;
+      bool nz;
+      if (ia == 1u) {  // backward.cu:545-546
+        const bool xcol = col == ACC_MEAN2D;
+        const float scale = xcol ? ddelx_dx : ddely_dy, c1 = xcol ? co.x : co.y, c2 = xcol ? co.y : co.z;
+        val = -(scale * co.w) * (c1 * ma + c2 * mb);
+        nz = ma != 0.f || mb != 0.f;
+      } else if (ia == 6u) {  // dL/dz = mu dL/dm, mu = dm/dz
+        val = mapped ? ((kappa * rz) * rz) * ma : ma;
+        nz = ma != 0.f;
+      } else {  // backward.cu:549-551: -0.5 o t; opacity (:554): the moment itself
+        const bool conic = ia >= 3u && ia <= 5u;
+        val = conic ? (-0.5f * co.w) * ma : ma;
+        nz = ma != 0.f;
+      }
+      if (used && nz) unsafeAtomicAdd(&a.acc[id * ACC_ROW + col], val);
+      if (in && col < (uint32_t)DIST_NM) row[col] = 0.f;  // (every read of this instruction precedes it: one wave, program order)
+    }
+  };
+
+  uint32_t pend_size = 0u;
+  for (; walk.valid(); walk.advance()) {
+    const uint32_t csize = walk.chunk_size();
+    const uint32_t cb = walk.chunk & 1u;
+    if (w == 0 && (uint32_t)lane < csize) {
+      sid[cb][lane] = walk.cur.id;
+      sco[cb][lane] = walk.cur.r0;
+      szr[cb][lane] = make_float2(walk.cur.r1.z, mapped ? 1.0f / walk.cur.r1.z : 1.0f);
+    }
+    const uint32_t pos = walk.lane_pos();
+    const uint32_t chunk_lo = tile_max - min(tile_max, (walk.chunk + 1u) * (uint32_t)WAVE);
+    const uint64_t live_m = __ballot(last_contributor > chunk_lo);
+    bool keep = false;
+    if (live_m != 0) keep = chunk_cull(live_m, qx0, qy0, ((uint32_t)lane < csize) && (pos < maxc), walk.cur);
+    const uint64_t m = __ballot(keep);
+    const uint32_t cnt = (uint32_t)__popcll(m);
+    const uint32_t cnt4 = (cnt + GROUP - 1) & ~(uint32_t)(GROUP - 1);
+    if (keep) {
+      const uint32_t slot = (uint32_t)__popcll(m & lt_mask);
+      s0[w][slot] = make_float4(-0.5f * walk.cur.r0.x, -walk.cur.r0.y, -0.5f * walk.cur.r0.z, walk.cur.r0.w);
+      // .z: the entry's index inside the chunk (= the lane that holds it): its LDS accumulator slot and its (z, rz)
+      s1[w][slot] = make_float4(walk.cur.r1.x, walk.cur.r1.y, __uint_as_float((uint32_t)lane), __uint_as_float(pos));
+    }
+    if ((uint32_t)lane >= cnt && (uint32_t)lane < cnt4) {
+      s0[w][lane] = make_float4(0.f, 0.f, 0.f, 0.f);  // null entry: alpha 0 => never contributes
+      s1[w][lane] = make_float4(0.f, 0.f, __uint_as_float(0u), __uint_as_float(0xffffffffu));
+    }
+    __syncthreads();  // (A) the chunk's sid / sco / szr and this wave's survivors are staged
+    if (pend_size != 0u) flush(cb ^ 1u, pend_size);
+    pend_size = csize;
+
+    for (uint32_t j = 0; j < cnt4; j += GROUP) {
+      float G[GROUP], al[GROUP], dxs[GROUP], dys[GROUP], ms[GROUP];
+      bool contrib[GROUP];
+      bool any = false;
+#pragma unroll
+      for (int u = 0; u < GROUP; ++u) {
+        const float4 g = s1[w][j + u];
+        const float4 co = s0[w][j + u];
+        const float2 zr = szr[cb][__float_as_uint(g.z)];
+        const uint32_t c = __float_as_uint(g.w);
+        dxs[u] = g.x - pfx;
+        dys[u] = g.y - pfy;
+        ms[u] = (kz0 * (zr.x - z0)) * zr.y;
+        const float power = blend_power_prescaled(co.x, co.y, co.z, dxs[u], dys[u]);
+        G[u] = blend_exp<FAST>(power);
+        al[u] = fminf(0.99f, co.w * G[u]);
+        contrib[u] = (c < last_contributor) && !(power > 0.0f) && !(al[u] < 1.0f / 255.0f);
+        any = any || contrib[u];
+      }
+      if (!__any(any)) continue;  // wave-uniform
+
+      float v[DIST_NM][GROUP];
+      {
+#pragma clang fp contract(fast)  // gradients are tolerance-checked, not bit-compared
+#pragma unroll
+        for (int u = 0; u < GROUP; ++u) {
+          const bool on = contrib[u];
+          const float alpha = on ? al[u] : 0.f;
+          const float mk = on ? ms[u] : 0.f;  // (a skipped entry's depth never enters the recurrence)
+          const float cdot = gD * (mk * (mk * A + nM1x2) + M2);  // gD c_k
+          const RecStep rs = accum_rec_step(T, B_acc, last_alpha, last_cdot, rcp_refined(1.f - alpha), cdot);
+          T = rs.T;
+          B_acc = rs.B_acc;
+          last_alpha = alpha;
+          last_cdot = on ? cdot : last_cdot;
+          const float q = on ? G[u] * rs.dL_dalpha : 0.f;
+          geometry_moments(v, u, q, dxs[u], dys[u]);
+          v[6][u] = (2.0f * gD) * ((alpha * T) * (mk * A - M1));  // gD dD/dm_k (0 for a skipped lane: alpha = 0)
+        }
+      }
+      float tot = wave_sum4_pack<DIST_NM>(v);
+      asm volatile("" : "+v"(tot));
+      if (g_adds) atomicAdd(&sacc[cb][__float_as_uint(s1[w][j + g_entry].z)][g_term], tot);
+    }
+    __syncthreads();  // (B) every quadrant's contribution to this chunk is in sacc[cb]
+  }
+  asm volatile("" ::"v"(walk.nxt.r0.x), "v"(walk.nxt.r1.x), "v"(walk.id_next), "v"(walk.id_next2));
+  if (pend_size != 0u) flush((walk.chunk - 1u) & 1u, pend_size);
+}
+
+template <bool FAST>
+__global__ void __launch_bounds__(WAVE* BWD_WAVES) __attribute__((amdgpu_waves_per_eu(4, 4)))
+distortion_backward_kernel(const BlendArgs a, const DistortionArgs f) {
+  __shared__ float4 s0[BWD_WAVES][WAVE], s1[BWD_WAVES][WAVE];
+  __shared__ uint32_t sid[2][WAVE];  // (sid, sco, szr, sacc: double-buffered by chunk parity)
+  __shared__ float4 sco[2][WAVE];
+  __shared__ float2 szr[2][WAVE];
+  __shared__ float sacc[2][WAVE][DIST_LDS_ROW];
+  __shared__ uint32_t s_item;
+  for (int i = threadIdx.x; i < 2 * WAVE * DIST_LDS_ROW; i += WAVE * BWD_WAVES) (&sacc[0][0][0])[i] = 0.f;
+  __syncthreads();
+  // item-granular queue, as K7: queue x (one per XCD) owns items x, x + 8, ... of the backward's work list
+  const uint32_t x = xcc_id() & 7u;
+  const uint32_t nwork = a.bwd_meta[0];
+  const uint32_t n_x = nwork > x ? (nwork - x + 7u) / 8u : 0u;
+  uint32_t* head = a.queue + x * QUEUE_STRIDE;
+  auto run_tile = [&](uint32_t index) __attribute__((always_inline)) {
+    uint4 item = load_backward_item(a, index);
+    item.z = min(item.z, item.w);  // (the depths are the forward's own: never beyond the tile's list)
+    distortion_backward_tile<FAST>(a, f, item, s0, s1, sid, sco, szr, sacc);
+  };
+  uint32_t x0, base;
+  const uint32_t q0 = first_item_of_block((uint32_t)a.units, x0, base);
+  {
+    const uint32_t n0 = nwork > x0 ? (nwork - x0 + 7u) / 8u : 0u;
+    if (q0 < n0) run_tile(x0 + 8u * q0);
+  }
+  for (;;) {
+    __syncthreads();
+    if (threadIdx.x == 0) s_item = base + __hip_atomic_fetch_add(head, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    const uint32_t q = s_item;
+    if (q >= n_x) break;
+    run_tile(x + 8u * q);
+  }
+  if (a.self_reset && threadIdx.x == 0) retire_queue(a.queue);
+}
+
 // Work list of the backward blend: tiles ordered by the work the FORWARD blend measured for them (entries evaluated,
 // summed over the four quadrants; the backward revisits the same (pixel, entry) pairs), heaviest first, in buckets of
 // 16 entries; tiles in which the forward evaluated nothing have no contributor anywhere and are dropped.  The list
@@ -2596,6 +2892,32 @@ hipError_t launch_feature_backward(hipStream_t s, BlendArgs a, const float* feat
   FeatureArgs f = {features, nullptr, dL_dimage, dL_dfeatures, C};
   void (*kernel)(BlendArgs, FeatureArgs) = nullptr;
   with_constants([&](auto FAST) { kernel = feature_backward_kernel<FAST>; }, a.fast_exp != 0);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(WAVE * BWD_WAVES), 0, s, a, f);
+  return hipGetLastError();
+}
+
+// The distortion image and its backward (gsr_blend_forward_distortion / gsr_blend_backward_distortion): one launch each, plus
+// the backward's own work list, built as the feature backward's.  kappa = f n / (f - n) of the mapped depth, 0: linear.
+hipError_t launch_distortion_forward(hipStream_t s, BlendArgs a, float kappa, float* out, float* moments) {
+  unsigned grid;
+  hipError_t e = persistent_launch(s, a, 1, &grid);
+  if (e != hipSuccess) return e;
+  DistortionArgs f = {out, reinterpret_cast<float4*>(moments), nullptr, nullptr, kappa, kappa != 0.f ? 1 : 0};
+  void (*kernel)(BlendArgs, DistortionArgs) = nullptr;
+  with_constants([&](auto FAST) { kernel = distortion_forward_kernel<FAST>; }, a.fast_exp != 0);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(WAVE), 0, s, a, f);
+  return hipGetLastError();
+}
+hipError_t launch_distortion_backward(hipStream_t s, BlendArgs a, float kappa, const float* moments, const float* dL_ddistortion) {
+  // #CUs x 4 workgroups of 4 waves, as K7
+  unsigned grid;
+  hipError_t e = persistent_launch(s, a, BWD_WAVES, &grid);
+  if (e != hipSuccess) return e;
+  if (a.work_est == nullptr || a.work_maxc == nullptr || a.bwd_order == nullptr) return hipErrorInvalidValue;
+  launch_backward_worklist(s, a, grid, ClearArgs{{nullptr, nullptr, nullptr, nullptr}, {0, 0, 0, 0}}, 0u, 0);
+  DistortionArgs f = {nullptr, nullptr, reinterpret_cast<const float4*>(moments), dL_ddistortion, kappa, kappa != 0.f ? 1 : 0};
+  void (*kernel)(BlendArgs, DistortionArgs) = nullptr;
+  with_constants([&](auto FAST) { kernel = distortion_backward_kernel<FAST>; }, a.fast_exp != 0);
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(WAVE * BWD_WAVES), 0, s, a, f);
   return hipGetLastError();
 }

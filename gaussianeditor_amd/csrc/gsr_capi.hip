@@ -817,6 +817,55 @@ int gsr_blend_backward_features(void* stream, int P, int64_t R, int W, int H, in
   return GSR_OK;
 }
 
+// The distortion image: near = far = 0 selects the linear depth, else finite 0 < near < far (2DGS's mapping).  -> kappa =
+// f n / (f - n) (0: linear), or a negative value for a pair that is neither.
+static float distortion_kappa(float near, float far) {
+  if (near == 0.f && far == 0.f) return 0.f;
+  if (!(near > 0.f) || !(far > near) || !(far - far == 0.f)) return -1.f;  // (NaN fails every comparison; far finite => near finite)
+  const float k = (float)((double)far * (double)near / ((double)far - (double)near));
+  return (k > 0.f && k - k == 0.f) ? k : -1.f;
+}
+
+int gsr_blend_forward_distortion(void* stream, int P, int64_t R, int W, int H, const void* geom, const void* binning,
+                                 void* image, float near, float far, float* out_distortion, float* moments, unsigned flags) {
+  if (flags & ~FEATURE_FLAGS) return GSR_ERR_BAD_ARGUMENT;
+  if (P < 0 || R < 0 || W <= 0 || H <= 0) return GSR_ERR_BAD_ARGUMENT;
+  const float kappa = distortion_kappa(near, far);
+  if (kappa < 0.f) return GSR_ERR_BAD_ARGUMENT;
+  if (!image || !out_distortion || ((uintptr_t)out_distortion & 3u) || ((uintptr_t)moments & 15u)) return GSR_ERR_BAD_ARGUMENT;
+  if (R > 0 && (!geom || !binning)) return GSR_ERR_BAD_ARGUMENT;
+  if (P == 0 || R == 0) {  // nothing is blended: zeros
+    GSR_HIP(hipMemsetAsync(out_distortion, 0, sizeof(float) * (size_t)H * (size_t)W, (hipStream_t)stream));
+    if (moments) GSR_HIP(hipMemsetAsync(moments, 0, sizeof(float) * 4 * (size_t)H * (size_t)W, (hipStream_t)stream));
+    return GSR_OK;
+  }
+  if (misaligned(geom) || misaligned(binning) || misaligned(image)) return GSR_ERR_BAD_ARGUMENT;
+  BlendArgs a = view_blend_args(P, R, W, H, geom, binning, image, nullptr, 0, flags);
+  keep_main_render_state(a);
+  GSR_HIP(launch_distortion_forward((hipStream_t)stream, a, kappa, out_distortion, moments));
+  return GSR_OK;
+}
+
+int gsr_blend_backward_distortion(void* stream, int P, int64_t R, int W, int H, const void* geom, const void* binning,
+                                  const void* image, float near, float far, const float* moments,
+                                  const float* dL_ddistortion, float* acc, unsigned flags) {
+  if (flags & ~FEATURE_FLAGS) return GSR_ERR_BAD_ARGUMENT;
+  if (P < 0 || R < 0 || W <= 0 || H <= 0) return GSR_ERR_BAD_ARGUMENT;
+  const float kappa = distortion_kappa(near, far);
+  if (kappa < 0.f) return GSR_ERR_BAD_ARGUMENT;
+  if (!image || !moments || !dL_ddistortion || !acc || ((uintptr_t)acc & 63u)) return GSR_ERR_BAD_ARGUMENT;
+  if (((uintptr_t)moments & 15u) || ((uintptr_t)dL_ddistortion & 3u)) return GSR_ERR_BAD_ARGUMENT;
+  if (R > 0 && (!geom || !binning)) return GSR_ERR_BAD_ARGUMENT;
+  if (P == 0 || R == 0) return GSR_OK;  // no pixel blends anything: nothing to add
+  if (misaligned(geom) || misaligned(binning) || misaligned(image)) return GSR_ERR_BAD_ARGUMENT;
+  if ((int64_t)((W + TILE - 1) / TILE) * ((H + TILE - 1) / TILE) > (int64_t)GSR_MAX_TILES) return GSR_ERR_BAD_ARGUMENT;
+  BlendArgs a = view_blend_args(P, R, W, H, geom, binning, image, nullptr, 1, flags);
+  a.acc = acc;
+  a.P = P;
+  GSR_HIP(launch_distortion_backward((hipStream_t)stream, a, kappa, moments, dL_ddistortion));
+  return GSR_OK;
+}
+
 // the flags K8+K9 reads (the persistent-rows form takes GSR_FLAG_ANTIALIAS alone)
 static const unsigned PRE_BWD_FLAGS = GSR_FLAG_ACC_SELF_CLEAN | GSR_FLAG_DEPTH_GRAD | GSR_FLAG_ANTIALIAS;
 

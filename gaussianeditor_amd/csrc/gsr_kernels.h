@@ -227,6 +227,10 @@ hipError_t launch_trace_contributions(hipStream_t s, BlendArgs a, int64_t* stats
 hipError_t launch_feature_forward(hipStream_t s, BlendArgs a, const float* features, float* out, int C);
 hipError_t launch_feature_backward(hipStream_t s, BlendArgs a, const float* features, const float* dL_dimage,
                                    float* dL_dfeatures, int C);
+// the depth-distortion image (A M2 - M1^2 of the blended depths, shifted per pixel) and its backward (gsr_blend.hip);
+// kappa = f n / (f - n) of the mapped depth, 0 = the linear depth; moments: (H,W) float4, null in a forward without backward
+hipError_t launch_distortion_forward(hipStream_t s, BlendArgs a, float kappa, float* out, float* moments);
+hipError_t launch_distortion_backward(hipStream_t s, BlendArgs a, float kappa, const float* moments, const float* dL_ddistortion);
 
 // The camera gradient (pose_backward_kernel, gsr_pose.hip): between K7 and K8+K9, from the accumulator rows K7 left
 struct PoseArgs {

@@ -347,6 +347,53 @@ def rasterize_features(features, num_rendered, geomBuffer, binningBuffer, imgBuf
     return out
 
 
+def check_near_far(near_far, name: str = "near_far"):
+    """The depth of a distortion image: None -> (0.0, 0.0), the linear view-space depth; a pair (near, far) of finite numbers
+    with 0 < near < far -> 2DGS's mapped depth far (z - near) / ((far - near) z).  Anything else: RuntimeError naming `name`."""
+    if near_far is None:
+        return 0.0, 0.0
+    try:
+        near, far = near_far
+        near, far = float(near), float(far)
+    except (TypeError, ValueError):
+        raise RuntimeError(f"diff_gaussian_rasterization: `{name}` must be None or a pair (near, far), got {near_far!r}") from None
+    if not (near == near and far == far and abs(far) != float("inf") and 0.0 < near < far):
+        raise RuntimeError(f"diff_gaussian_rasterization: `{name}` must be finite with 0 < near < far, got ({near}, {far})")
+    return near, far
+
+
+def rasterize_distortion(num_points, num_rendered, geomBuffer, binningBuffer, imgBuffer, image_height, image_width, near_far=None,
+                         with_moments=True, debug=False, flags=None):
+    """Extension (no reference counterpart; include/gsr.h gsr_blend_forward_distortion): the depth-distortion image of the view
+    whose state (`geomBuffer`, `binningBuffer`, `imgBuffer`, `num_rendered`) a rasterize_gaussians() call of `num_points`
+    Gaussians returned -- per pixel 1/2 sum_{i != j} w_i w_j (m_i - m_j)^2 over the entries the colour image blends, m the view-space depth or, with
+    `near_far` = (near, far), 2DGS's mapped depth.  -> (distortion (1,H,W), moments (H,W,4) | None): `moments` is what
+    rasterize_gaussians_backward(distortion_moments=, dL_dout_distortion=, distortion_near_far=) takes; with_moments=False (a
+    render without a backward) leaves it out.  The saved state is left intact.  An empty state (no Gaussians): zeros."""
+    flags = _flags(flags)
+    near, far = check_near_far(near_far)
+    P, H, W = int(num_points), int(image_height), int(image_width)
+    for name, buf in (("geomBuffer", geomBuffer), ("binningBuffer", binningBuffer), ("imgBuffer", imgBuffer)):
+        if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8:
+            raise RuntimeError(f"diff_gaussian_rasterization: `{name}` must be a torch.uint8 tensor")
+    dev = imgBuffer.device
+    if P == 0 or geomBuffer.numel() == 0 or imgBuffer.numel() == 0:
+        return (torch.zeros((1, H, W), dtype=torch.float32, device=dev),
+                torch.zeros((H, W, 4), dtype=torch.float32, device=dev) if with_moments else None)
+    _require_cuda(imgBuffer, "imgBuffer")
+    for name, buf in (("geomBuffer", geomBuffer), ("binningBuffer", binningBuffer)):
+        _on_device(buf, name, dev, torch.uint8)
+    out = torch.empty((1, H, W), dtype=torch.float32, device=dev)
+    moments = torch.empty((H, W, 4), dtype=torch.float32, device=dev) if with_moments else None
+    with torch.cuda.device(dev):
+        _native.check("gsr_blend_forward_distortion", _native.lib().gsr_blend_forward_distortion(
+            _stream(dev), P, int(num_rendered), W, H, geomBuffer.data_ptr(), _ptr(binningBuffer), imgBuffer.data_ptr(),
+            near, far, out.data_ptr(), None if moments is None else moments.data_ptr(), flags & _FEATURE_FLAGS))
+        if debug:
+            torch.cuda.synchronize(dev)
+    return out, moments
+
+
 #: The blend backward's accumulator table kept ACROSS backwards (GSR_FLAG_ACC_SELF_CLEAN, include/gsr.h): one zeroed (P,16)
 #: buffer per (device, stream), checked out for the duration of a backward's two native calls and put back only when both were
 #: enqueued -- K8+K9 leaves it all zero again in stream order, so the next backward on that stream needs no clear (64 MB in
@@ -375,7 +422,8 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                                  viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, sh, degree, campos,
                                  geomBuffer, R, binningBuffer, imageBuffer, debug, flags=None, grad_allocator=None,
                                  dL_dout_depth=None, abs_grad_out=None, dL_dout_alpha=None, pose_grad_out=None,
-                                 features=None, dL_dout_features=None, feature_grad_out=None):
+                                 features=None, dL_dout_features=None, feature_grad_out=None, distortion_moments=None,
+                                 dL_dout_distortion=None, distortion_near_far=None):
     """RasterizeGaussiansBackwardCUDA, rasterize_points.cu:97-157 ->
     (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D | None, dL_dsh, dL_dscales, dL_drotations).
     `flags` (extension, keyword): the flags the forward of this view ran with; None = options.current_flags().
@@ -419,6 +467,13 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     absolute values cannot take a signed share afterwards: folding it in would need a fused kernel; not offered).  Not with
     the grad_allocator's "sh_rgb" and "row_state" modes.  Without the keywords the backward makes exactly the native calls it
     made before they existed.
+    `distortion_moments`, `dL_dout_distortion` (extension, keywords; both or none), `distortion_near_far`: the (H,W,4) float32
+    moments a rasterize_distortion() of this view returned, the (1,H,W) float32 gradient of its image, and the `near_far` that
+    call was given (None: the linear depth).  Given, gsr_blend_backward_distortion runs between the two halves, behind
+    gsr_blend_backward_features and in front of gsr_pose_backward, and adds the distortion image's share of the geometry
+    gradients and of dL/ddepth into the accumulator rows; gsr_pose_backward and K8+K9 then get GSR_FLAG_DEPTH_GRAD, which
+    carries the depth column on.  `abs_grad_out` is what it is without the distortion image, as with features.  Not with the
+    grad_allocator's "sh_rgb" and "row_state" modes.  Without the keywords: the native calls made before they existed.
     Every backward is issued as its two halves (a blend half, then a K8+K9 half), never through the fused gsr_backward."""
     flags = _flags(flags)
     dev = means3D.device
@@ -443,6 +498,26 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
             raise RuntimeError(f"diff_gaussian_rasterization: `feature_grad_out` must be a contiguous ({P}, {feat_C}) tensor, "
                                f"got {tuple(feature_grad_out.shape)}")
         _same_device(feature_grad_out, "feature_grad_out", dev)
+    dist = distortion_moments is not None or dL_dout_distortion is not None
+    dist_nf = (0.0, 0.0)
+    if dist:
+        if distortion_moments is None or dL_dout_distortion is None:
+            raise RuntimeError("diff_gaussian_rasterization: `distortion_moments` and `dL_dout_distortion` are given together or "
+                               "not at all")
+        dist_nf = check_near_far(distortion_near_far, "distortion_near_far")
+        hw = tuple(dL_dout_color.shape[1:]) if isinstance(dL_dout_color, torch.Tensor) and dL_dout_color.dim() == 3 else None
+        for name, t, shape in (("distortion_moments", distortion_moments, None if hw is None else hw + (4,)),
+                               ("dL_dout_distortion", dL_dout_distortion, None if hw is None else (1,) + hw)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+                raise RuntimeError(f"diff_gaussian_rasterization: `{name}` must be a float32 tensor, got "
+                                   f"{getattr(t, 'dtype', type(t).__name__)}")
+            if shape is None or tuple(t.shape) != shape:
+                raise RuntimeError(f"diff_gaussian_rasterization: `{name}` must be a {shape or '(H, W, ...)'} tensor, got "
+                                   f"{tuple(t.shape)}")
+            _same_device(t, name, dev)
+    elif distortion_near_far is not None:
+        raise RuntimeError("diff_gaussian_rasterization: `distortion_near_far` without `distortion_moments` and "
+                           "`dL_dout_distortion`")
     if dL_dout_alpha is not None:
         hw = tuple(dL_dout_color.shape[1:]) if isinstance(dL_dout_color, torch.Tensor) and dL_dout_color.dim() == 3 else None
         if not isinstance(dL_dout_alpha, torch.Tensor) or dL_dout_alpha.dtype != torch.float32:
@@ -487,6 +562,8 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     dL_dalpha = None if dL_dout_alpha is None else _f32(dL_dout_alpha, "dL_dout_alpha", dev)
     if feat_C:
         features, dL_dfeat_img = _f32(features, "features", dev), _f32(dL_dout_features, "dL_dout_features", dev)
+    if dist:
+        dist_mom, dL_ddist = _f32(distortion_moments, "distortion_moments", dev), _f32(dL_dout_distortion, "dL_dout_distortion", dev)
     _on_device(radii, "radii", dev, torch.int32)
     for name, buf in (("geomBuffer", geomBuffer), ("binningBuffer", binningBuffer), ("imageBuffer", imageBuffer)):
         _on_device(buf, name, dev, torch.uint8)
@@ -518,6 +595,9 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     if dL_drgb is not None and feat_C:
         raise RuntimeError("diff_gaussian_rasterization: feature gradients are not supported with the colour-gradient exchange "
                            "(the grad_allocator's \"sh_rgb\" mode)")
+    if dL_drgb is not None and dist:
+        raise RuntimeError("diff_gaussian_rasterization: distortion gradients are not supported with the colour-gradient "
+                           "exchange (the grad_allocator's \"sh_rgb\" mode)")
     dL_dsh = None if dL_drgb is not None else _alloc(grad_alloc, "sh", (P, M, 3), M == 0, dev)
     dL_dscales = _alloc(grad_alloc, "scales", (P, 3), not has_scales, dev)
     dL_drotations = _alloc(grad_alloc, "rotations", (P, 4), not has_scales, dev)
@@ -530,6 +610,9 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                            "(the grad_allocator's \"row_state\" mode)")
     if row_state is not None and feat_C:
         raise RuntimeError("diff_gaussian_rasterization: feature gradients are not supported with persistent gradient rows "
+                           "(the grad_allocator's \"row_state\" mode)")
+    if row_state is not None and dist:
+        raise RuntimeError("diff_gaussian_rasterization: distortion gradients are not supported with persistent gradient rows "
                            "(the grad_allocator's \"row_state\" mode)")
     if row_state is not None and pose_grad_out is not None:
         raise RuntimeError("diff_gaussian_rasterization: camera gradients are not supported with persistent gradient rows "
@@ -556,8 +639,9 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
     # persistent one again (ACC_SELF_CLEAN) and takes DEPTH_GRAD; ANTIALIAS, a flag of the view, goes to both.
     blend_flags = (flags | (0 if persist else options.FLAG_CLEAR_GRADS)
                    | (options.FLAG_ABS_GRAD if abs_grad_out is not None else 0))
-    pre_flags = ((options.FLAG_ACC_SELF_CLEAN if persist else 0) | (options.FLAG_DEPTH_GRAD if dL_ddepth is not None else 0)
-                 | (flags & options.FLAG_ANTIALIAS))
+    # (the distortion backward adds to the depth column: K8+K9 and the pose backward must carry it on, as with a depth gradient)
+    depth_col = options.FLAG_DEPTH_GRAD if (dL_ddepth is not None or dist) else 0
+    pre_flags = (options.FLAG_ACC_SELF_CLEAN if persist else 0) | depth_col | (flags & options.FLAG_ANTIALIAS)
     # K7's row mask (it clears it and marks the rows it adds to): only where somebody reads it -- with a mask the work-list
     # launch carries extra fill blocks
     touched = torch.empty(((P + 15) // 16) * 16, dtype=torch.uint8, device=dev) \
@@ -583,6 +667,10 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                 features.data_ptr(), dL_dfeat_img.data_ptr(), acc.data_ptr(), feature_grad_out.data_ptr(),
                 flags & _FEATURE_FLAGS))
             torch.autograd.graph.increment_version(feature_grad_out)  # written through a raw pointer
+        if dist:  # adds the distortion image's share into the rows, the depth column included
+            _native.check("gsr_blend_backward_distortion", L.gsr_blend_backward_distortion(
+                _stream(dev), P, int(R), W, H, geomBuffer.data_ptr(), _ptr(binningBuffer), imageBuffer.data_ptr(),
+                dist_nf[0], dist_nf[1], dist_mom.data_ptr(), dL_ddist.data_ptr(), acc.data_ptr(), flags & _FEATURE_FLAGS))
         if pose_grad_out is not None:  # reads the rows K7 left, in front of K8+K9 (which may clean them); changes nothing
             nbytes = ctypes.c_size_t(0)
             _native.check("gsr_pose_workspace_size", L.gsr_pose_workspace_size(P, ctypes.byref(nbytes)))
@@ -592,7 +680,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rot
                 _ptr(cov3D_precomp), viewmatrix.data_ptr(), projmatrix.data_ptr(), _ptr(campos) if M != 0 else None,
                 float(tan_fovx), float(tan_fovy), radii.data_ptr(), geomBuffer.data_ptr(), acc.data_ptr(), pose_ws.data_ptr(),
                 pose_grad_out.data_ptr(),
-                (options.FLAG_DEPTH_GRAD if dL_ddepth is not None else 0) | (flags & options.FLAG_ANTIALIAS)))
+                depth_col | (flags & options.FLAG_ANTIALIAS)))
         if dL_drgb is not None:
             # notification (no allocation): K7 is enqueued, K8+K9 not yet -- multiview.py starts the exchange of the
             # touched-row counts here (from K7's row mask), so that it and the host's wait for it run underneath K8+K9

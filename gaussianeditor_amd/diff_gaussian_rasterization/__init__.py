@@ -63,7 +63,9 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings, aux_colors=None, return_alpha=False, viewmatrix=None, projmatrix=None, campos=None,
-                features=None):
+                features=None, distortion=None):
+        # (distortion: None, or the (near, far) pair of a render with `return_distortion` -- (0.0, 0.0): the linear depth --,
+        #  whose (1,H,W) depth-distortion image is returned behind everything else; passed by such a render only)
         # (features: (P,C) per-Gaussian features, composited into a differentiable (C,H,W) image that is returned last --
         #  passed by a render with `features=` only; every other render passes the argument tuple it always passed)
         # (viewmatrix, projmatrix, campos: rs.viewmatrix / rs.projmatrix / rs.campos once more, as inputs autograd can see --
@@ -92,8 +94,20 @@ class _RasterizeGaussians(torch.autograd.Function):
         _reuse.remember(rs, flags, means3D, scales, rotations, opacities, cov3Ds_precomp, num_rendered, geomBuffer,
                         binningBuffer, imgBuffer, radii, depth)
         ctx.gsr_features = features is not None
+        dist_out = dist_moments = None
+        if distortion is not None:
+            # extension: the distortion image, one forward kernel on the state K6 just left; the per-pixel moments for the
+            # backward only where there will be one
+            dist_out, dist_moments = _call_native(
+                run(_C.rasterize_distortion), (int(means3D.shape[0]), num_rendered, geomBuffer, binningBuffer, imgBuffer,
+                                               rs.image_height, rs.image_width, None if distortion == (0.0, 0.0) else distortion,
+                                               any(ctx.needs_input_grad), rs.debug), rs.debug, "snapshot_fw.dump",
+                "\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
+        ctx.gsr_distortion_slot = distortion is not None  # (the image is an output, the (near, far) pair input 15)
+        ctx.gsr_distortion = distortion if dist_moments is not None else None
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
-                              binningBuffer, imgBuffer, *((features,) if features is not None else ()))
+                              binningBuffer, imgBuffer, *((features,) if features is not None else ()),
+                              *((dist_moments,) if dist_moments is not None else ()))
         ctx.mark_non_differentiable(radii)
         # radii / depth never carry a gradient: do not let autograd fill zero tensors for them on every backward
         ctx.set_materialize_grads(False)
@@ -106,6 +120,8 @@ class _RasterizeGaussians(torch.autograd.Function):
                 run(_C.rasterize_features), (features.detach(), num_rendered, geomBuffer, binningBuffer, imgBuffer,
                                              rs.image_height, rs.image_width, rs.debug), rs.debug, "snapshot_fw.dump",
                 "\nAn error occured in forward. Please forward snapshot_fw.dump for debugging."),)
+        if dist_out is not None:
+            alpha = alpha + (dist_out,)
         if aux_colors is None:
             return (color, radii, depth) + alpha
         # extension: a second, gradient-free image of the same view with other colours (K6 only)
@@ -117,11 +133,17 @@ class _RasterizeGaussians(torch.autograd.Function):
         return (color, radii, depth, aux) + alpha
 
     @staticmethod
-    def backward(ctx, grad_out_color, grad_radii, grad_depth, *grad_rest):  # (grad_rest: of aux, alpha, features, in that order)
+    def backward(ctx, grad_out_color, grad_radii, grad_depth, *grad_rest):  # (grad_rest: of aux, alpha, features, distortion)
         # grad_radii is ignored exactly as in the reference (:137, :155-177); so is grad_depth -- depth is a forward-only
         # output -- unless this render ran with FLAG_DEPTH_GRAD (gaussianeditor_amd.set_depth_grad)
         (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer, binningBuffer,
          imgBuffer) = ctx.saved_tensors[:10]
+        dist = None
+        has_dist_out = ctx.gsr_distortion_slot  # (its image is the last output)
+        if has_dist_out:
+            if ctx.gsr_distortion is not None and grad_rest[-1] is not None:
+                dist = (ctx.saved_tensors[-1], grad_rest[-1], ctx.gsr_distortion)
+            grad_rest = grad_rest[:-1]
         feats = None
         if ctx.gsr_features:  # the feature image is the last output, the alpha image the one in front of it
             feats = (ctx.saved_tensors[10], grad_rest[-1])
@@ -129,10 +151,11 @@ class _RasterizeGaussians(torch.autograd.Function):
         return _backward(ctx, (means3D, sh, colors_precomp, scales, rotations, cov3Ds_precomp),
                          (ctx.num_rendered, radii, geomBuffer, binningBuffer, imgBuffer),
                          (grad_out_color, grad_depth, grad_rest[-1] if ctx.gsr_alpha else None), dump=True, features=feats,
+                         **({"distortion": dist, "distortion_slot": True} if has_dist_out else {}),
                          grad_allocator=getattr(ctx, "gsr_grad_allocator", None))
 
 
-def _backward(ctx, inputs, state, grads, dump=False, features=None, **route_kw):
+def _backward(ctx, inputs, state, grads, dump=False, features=None, distortion=None, distortion_slot=False, **route_kw):
     """The backward of both autograd functions: _C.rasterize_gaussians_backward on `inputs` (means3D, sh, colors_precomp, scales,
     rotations, cov3Ds_precomp) and the `state` their forward left (num_rendered, radii, geomBuffer, binningBuffer, imgBuffer),
     with `grads`, the gradients of the colour, depth and alpha outputs -> one gradient slot per forward() input (:213-225).
@@ -140,7 +163,9 @@ def _backward(ctx, inputs, state, grads, dump=False, features=None, **route_kw):
     FLAG_DEPTH_GRAD (depth is a forward-only output otherwise), the tensor for the absolute screen-space gradient under
     FLAG_ABS_GRAD (a new (P,3) one per backward, assigned to `means2D.absgrad`), a gradient of an alpha image that was
     returned AND used, `features` = (the features, the gradient of their image) of a render with `features=` whose feature
-    image was used (one more gradient slot then, the last); `route_kw` likewise -- so that every other backward is the
+    image was used (one more gradient slot then), `distortion` = (the moments, the gradient of the image, its (near, far)) of
+    a render with `return_distortion` whose distortion image was used (`distortion_slot`: the render had that input, one
+    more gradient slot behind the features'); `route_kw` likewise -- so that every other backward is the
     reference's call, to any `_C` backend."""
     rs, flags = ctx.raster_settings, ctx.gsr_flags
     means3D, sh, colors_precomp, scales, rotations, cov3Ds_precomp = inputs
@@ -161,7 +186,11 @@ def _backward(ctx, inputs, state, grads, dump=False, features=None, **route_kw):
     if features is not None and features[1] is not None:
         grad_features = torch.zeros_like(features[0], memory_format=torch.contiguous_format)  # (added into: zeroed here)
         kw.update(features=features[0], dL_dout_features=features[1], feature_grad_out=grad_features)
-    if grad_out_color is None:  # only the depth, alpha and / or feature output was used downstream
+    if distortion is not None:
+        kw.update(distortion_moments=distortion[0], dL_dout_distortion=distortion[1])
+        if distortion[2] != (0.0, 0.0):
+            kw["distortion_near_far"] = distortion[2]
+    if grad_out_color is None:  # only the depth, alpha, feature and / or distortion output was used downstream
         grad_out_color = torch.zeros((3, rs.image_height, rs.image_width), dtype=torch.float32, device=means3D.device)
     # argument order of _C.rasterize_gaussians_backward (rasterize_points.h:38-60)
     args = (rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
@@ -175,7 +204,9 @@ def _backward(ctx, inputs, state, grads, dump=False, features=None, **route_kw):
         ctx.gsr_means2D.absgrad = abs_grad
     out = (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales, grad_rotations,
            grad_cov3Ds_precomp, None, None, None)
-    tail = () if features is None else (grad_features,)  # (input 14; the camera tensors keep 11 .. 13)
+    tail = () if features is None and not distortion_slot else (grad_features,)  # (input 14; the camera tensors keep 11 .. 13)
+    if distortion_slot:
+        tail = tail + (None,)  # (input 15: the (near, far) pair)
     if pose is None:
         return out + ((None, None, None) + tail if tail else ())
     # three more slots, in the layout of the tensors themselves; None for one that does not require a gradient
@@ -236,12 +267,14 @@ def _pose_inputs(rs):
 
 
 def _rasterize_with_features(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                             raster_settings, aux_colors, return_alpha, features):
-    """A render with `features=`: always in full (never served by view reuse; it may be remembered), the features a
-    trailing input autograd sees, behind the camera tensors' slots."""
+                             raster_settings, aux_colors, return_alpha, features, distortion=None):
+    """A render with `features=` and / or `return_distortion`: always in full (never served by view reuse; it may be
+    remembered), the features a trailing input autograd sees, behind the camera tensors' slots, the distortion image's
+    (near, far) behind them -- passed only where that image is asked for."""
     pose = _pose_inputs(raster_settings) or (None, None, None)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                                     raster_settings, aux_colors, bool(return_alpha), *pose, features)
+                                     raster_settings, aux_colors, bool(return_alpha), *pose, features,
+                                     *(() if distortion is None else (distortion,)))
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
@@ -276,6 +309,11 @@ def rasterize_gaussians_with_aux(means3D, means2D, sh, colors_precomp, opacities
                                      cov3Ds_precomp, raster_settings, aux_colors, *((True,) if return_alpha else ()))
 
 
+def distortion_asked(return_distortion) -> bool:
+    """`return_distortion` of GaussianRasterizer.forward / render(): False / None -- no; True or a (near, far) pair -- yes."""
+    return return_distortion is not False and return_distortion is not None
+
+
 def _absent(like: torch.Tensor) -> torch.Tensor:
     """The reference encodes "not provided" as an empty float32 tensor on "cuda" (:285-295);
     we put it on the device of `means3D`, which is the same thing for every valid call."""
@@ -294,8 +332,9 @@ class GaussianRasterizer(nn.Module):
             return _C.mark_visible(positions, rs.viewmatrix, rs.projmatrix)
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, aux_colors=None, return_alpha=False, features=None, return_normals=False):
-        """Reference signature (:258-309) plus four extensions.  With `aux_colors` (P,3) a second image of the same
+                cov3D_precomp=None, aux_colors=None, return_alpha=False, features=None, return_normals=False,
+                return_distortion=False):
+        """Reference signature (:258-309) plus five extensions.  With `aux_colors` (P,3) a second image of the same
         view, blended with those colours instead, is returned as a fourth value (forward only, no gradient).  It is
         what a second call with colors_precomp=aux_colors would render, at the cost of the blend kernel alone.
         With `return_alpha=True` the alpha image (1,H,W) -- accumulated opacity, 1 - the final transmittance -- is an
@@ -308,7 +347,13 @@ class GaussianRasterizer(nn.Module):
         (gaussianeditor_amd.normals.gaussian_normals of this view), composited like a feature -- is appended behind all of
         them: (color, radii, depth[, aux][, alpha][, feature_image], normals), with a gradient to the rotations and the
         geometry.  It rides the feature route (three more channels behind the caller's, so C <= 253 then) and needs
-        scales / rotations, not cov3D_precomp.  The arity depends on these four arguments alone, never on process state."""
+        scales / rotations, not cov3D_precomp.  With `return_distortion=True`, or `return_distortion=(near, far)` with finite
+        0 < near < far, the depth-distortion image (1,H,W) -- per pixel 1/2 sum_{i != j} w_i w_j (m_i - m_j)^2 over the
+        entries the colour image blends, m the view-space depth or 2DGS's mapped depth far (z - near) / ((far - near) z);
+        the regulariser of Mip-NeRF 360 / 2DGS, accumulated in depths shifted by the pixel's first blended one -- is appended
+        as the LAST value, behind all of the others, with a gradient to means3D, means2D, opacities and scales / rotations /
+        cov3D_precomp.  `means2D.absgrad` (FLAG_ABS_GRAD) is what it is without the distortion image, as with features.  The
+        arity depends on these five arguments alone, never on process state."""
         if (shs is None) == (colors_precomp is None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")  # sic, :271-276
         has_sr = scales is not None or rotations is not None
@@ -320,9 +365,12 @@ class GaussianRasterizer(nn.Module):
         scales = _absent(means3D) if scales is None else scales
         rotations = _absent(means3D) if rotations is None else rotations
         cov3D_precomp = _absent(means3D) if cov3D_precomp is None else cov3D_precomp
+        distortion = None
+        if distortion_asked(return_distortion):
+            distortion = _C.check_near_far(None if return_distortion is True else return_distortion, "return_distortion")
         if return_normals:
             return self._forward_with_normals(means3D, means2D, opacities, shs, colors_precomp, scales, rotations,
-                                              cov3D_precomp, aux_colors, return_alpha, features)
+                                              cov3D_precomp, aux_colors, return_alpha, features, return_distortion)
         if features is not None:
             if not isinstance(features, torch.Tensor) or features.dtype != torch.float32:
                 raise RuntimeError("diff_gaussian_rasterization: `features` must be a float32 tensor, got "
@@ -334,7 +382,11 @@ class GaussianRasterizer(nn.Module):
                 raise RuntimeError(f"diff_gaussian_rasterization: `features` is on {features.device} but `means3D` is on "
                                    f"{means3D.device}")
             return _rasterize_with_features(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                            cov3D_precomp, self.raster_settings, aux_colors, return_alpha, features)
+                                            cov3D_precomp, self.raster_settings, aux_colors, return_alpha, features,
+                                            distortion)
+        if distortion is not None:
+            return _rasterize_with_features(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+                                            cov3D_precomp, self.raster_settings, aux_colors, return_alpha, None, distortion)
         if aux_colors is not None:
             return rasterize_gaussians_with_aux(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                                 cov3D_precomp, self.raster_settings, aux_colors, return_alpha)
@@ -342,7 +394,7 @@ class GaussianRasterizer(nn.Module):
                                    self.raster_settings, return_alpha)
 
     def _forward_with_normals(self, means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp,
-                              aux_colors, return_alpha, features):
+                              aux_colors, return_alpha, features, return_distortion=False):
         """forward(..., return_normals=True): the Gaussian normals of this view as the last three feature channels, split
         off again.  Absent arguments arrive as empty tensors."""
         from .. import normals as _normals
@@ -363,10 +415,14 @@ class GaussianRasterizer(nn.Module):
         feats = nrm if features is None else torch.cat([features, nrm], dim=1)
         outs = self.forward(means3D, means2D, opacities, shs=shs if shs.numel() else None,
                             colors_precomp=colors_precomp if colors_precomp.numel() else None, scales=scales,
-                            rotations=rotations, aux_colors=aux_colors, return_alpha=return_alpha, features=feats)
+                            rotations=rotations, aux_colors=aux_colors, return_alpha=return_alpha, features=feats,
+                            **({"return_distortion": return_distortion} if distortion_asked(return_distortion) else {}))
+        tail = ()
+        if distortion_asked(return_distortion):  # (the distortion image is the last value, the normals in front of it)
+            outs, tail = outs[:-1], outs[-1:]
         if features is None:
-            return outs
-        return outs[:-1] + (outs[-1][:C], outs[-1][C:])
+            return outs + tail
+        return outs[:-1] + (outs[-1][:C], outs[-1][C:]) + tail
 
     def apply_weights(self, means3D, means2D, opacities, shs=None, weights=None, scales=None, rotations=None,
                       cov3Ds_precomp=None, cnt=None, image_weights=None):

@@ -14,7 +14,7 @@ import math
 import torch
 
 from . import options as _options
-from .diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer
+from .diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer, distortion_asked
 
 _SH_C0 = 0.28209479177387814
 _SH_C1 = 0.4886025119029199
@@ -68,7 +68,7 @@ def camera2rasterizer(viewpoint_camera, bg_color: torch.Tensor, sh_degree: int =
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
-           semantic_color=None, return_alpha=None, features=None, return_normals=False):
+           semantic_color=None, return_alpha=None, features=None, return_normals=False, return_distortion=False):
     """gaussian_renderer/__init__.py:45-150.  Background tensor must be on the GPU.
 
     Extension: `semantic_color` (P,3) adds out["semantic"], the image the reference obtains from a SECOND
@@ -83,7 +83,11 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     (gaussianeditor_amd.normals.gaussian_normals: the shortest axis, turned towards the camera) composited with this view's
     alpha on background 0, with a gradient to the rotations and the geometry; what normals.normal_consistency_loss takes.
     It takes three of the 256 feature channels (`features` may have at most 253 with it) and is refused with
-    pipe.compute_cov3D_python."""
+    pipe.compute_cov3D_python.
+    Extension: `return_distortion=True`, or `(near, far)` with finite 0 < near < far, adds out["distortion"], the (1,H,W)
+    depth-distortion image of Mip-NeRF 360 / 2DGS over the entries the colour image blends -- of the view-space depth, or of
+    2DGS's mapped depth -- with a gradient to the geometry (GaussianRasterizer.forward); its mean is the regulariser."""
+    distortion = distortion_asked(return_distortion)
     if return_alpha is None:
         return_alpha = bool(_options.current_flags() & _options.FLAG_ALPHA_OUT)
     xyz = pc.get_xyz
@@ -128,6 +132,7 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         **({"return_alpha": True} if return_alpha else {}),
         **({} if features is None else {"features": features}),
         **({"return_normals": True} if return_normals else {}),
+        **({"return_distortion": return_distortion} if distortion else {}),
     )
     rendered_image, radii, depth = outs[:3]
     out = {
@@ -139,6 +144,9 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     }
     if semantic_color is not None:
         out["semantic"] = outs[3]
+    if distortion:  # (the distortion image is the last value of all)
+        out["distortion"] = outs[-1]
+        outs = outs[:-1]
     tail = 1 if return_normals else 0  # (the normal image is the last value, the feature image in front of it)
     if return_alpha:
         out["alpha"] = outs[-1 - tail - (0 if features is None else 1)]

@@ -78,7 +78,9 @@ extern "C" {
  * gsr_bilagrid_* entry points (the bilateral-grid slice and its TV regulariser; nothing existing changed).  Then, likewise
  * additive: gsr_sh_rotation and gsr_transform_rows (similarity transforms of Gaussians; nothing existing changed).  Then,
  * likewise additive: gsr_gaussian_normals_forward / _backward, gsr_depth_normals_forward / _backward,
- * gsr_normal_loss_workspace_size and gsr_normal_loss_forward / _backward (surface normals; nothing existing changed). */
+ * gsr_normal_loss_workspace_size and gsr_normal_loss_forward / _backward (surface normals; nothing existing changed).
+ * Then, likewise additive: gsr_blend_forward_distortion and gsr_blend_backward_distortion (the depth-distortion image; no
+ * new flag bit, nothing existing changed). */
 #define GSR_ABI_VERSION 6
 /* The blend backward's accumulator table: GSR_ACC_ROW floats (one 64-byte line) per Gaussian, 64-byte aligned.  Columns:
  *   [GSR_ACC_MEAN2D] .x [+1] .y of dL_dmean2D      (backward.cu:545-546)
@@ -452,6 +454,44 @@ int gsr_blend_forward_features(void* stream, int P, int64_t R, int W, int H, int
 int gsr_blend_backward_features(void* stream, int P, int64_t R, int W, int H, int C, const void* geom, const void* binning,
                                 const void* image, const float* features, const float* dL_dfeature_image,
                                 float* acc, float* dL_dfeatures, unsigned flags);
+
+/* Depth-distortion image (opt-in; no flag bit: the call says what is asked): the regulariser of Mip-NeRF 360 / 2DGS, through
+ * the geometry / binning state an earlier gsr_preprocess + gsr_bin left, with the alpha of gsr_blend_forward under the view's
+ * flags.  The entries of a pixel are exactly the ones the colour image blends (the first n_contrib list entries: the same
+ * alpha, 0.99 clamp, power > 0 and alpha < 1/255 skips, and the T < 1e-4 stop).  With w_i = alpha_i T_i and m_i the depth of
+ * entry i,
+ *     D = 1/2 sum_{i != j} w_i w_j (m_i - m_j)^2 = A M2 - M1^2,   A = sum w, M1 = sum w m, M2 = sum w m^2
+ *       = 2DGS's running sum  sum_i w_i (m_i^2 A_{i-1} + M2_{i-1} - 2 m_i M1_{i-1}).
+ * Depth of an entry: z_i, the view-space depth of the geometry state (what the depth image blends).  near = far = 0: m = z.
+ * Finite 0 < near < far: 2DGS's mapping m = far (z - near) / ((far - near) z).
+ * Shift: D does not change under m -> m - m0.  The moments are accumulated, in float32, of the SHIFTED depth m', with z0 the
+ * z of the pixel's first blended entry:  linear m'_i = z_i - z0, mu_i = dm/dz = 1;  mapped m'_i = kappa (z_i - z0) / (z0 z_i),
+ * mu_i = kappa / z_i^2, kappa = far near / (far - near) -- formed from the difference of the z's, never from two mapped
+ * values.  Without the shift A M2 - M1^2 cancels where the term is meant to work, on thin surfaces far from the camera.
+ * gsr_blend_forward_distortion: out_distortion (H,W) = A M2' - M1'^2, fully written; a pixel with no entry or one entry
+ *   gets exactly 0.  moments (H,W) float4, 16-byte aligned, = (z0, A, M1', M2') per pixel for the backward, or NULL (a
+ *   forward without a backward).  final_T / n_contrib in `image` are left untouched.  P == 0 or R == 0: zeros.
+ * gsr_blend_backward_distortion: dL_ddistortion (H,W) in, gD.  From the pixel's totals alone,
+ *     dD/dw_k = m'_k^2 A + M2' - 2 m'_k M1' =: c_k,   dD/dm_k = 2 w_k (m'_k A - M1'),   no term reaches z0;
+ *     dL/dalpha_k = T_k (gD c_k - rec_k): the colour backward's recurrence with the scalar gD c_k in the place of the
+ *     collapsed colour, background 0.
+ *   Walks the first n_contrib entries of every pixel back to front from final_T and ADDS the geometry share into the columns
+ *   GSR_ACC_MEAN2D, GSR_ACC_OPACITY, GSR_ACC_CONIC of `acc` in the colour backward's conventions, and dL/dz_k = sum over
+ *   pixels of gD 2 w_k (m'_k A - M1') mu_k into GSR_ACC_DEPTH (GSR_ACC_COLOR and GSR_ACC_ABS2D are not written).  Called
+ *   AFTER the blend half of the view's colour backward, gsr_abs_grad_take and gsr_blend_backward_features where those are
+ *   called, and BEFORE gsr_pose_backward and the view's K8+K9 entry point, on the same stream; both must then be given
+ *   GSR_FLAG_DEPTH_GRAD, which is what carries the GSR_ACC_DEPTH column on (and, with GSR_FLAG_ACC_SELF_CLEAN, zeroes it).
+ *   No checkpoints, no list segments, as gsr_blend_backward_features.  The absolute sums of GSR_FLAG_ABS_GRAD do not hold
+ *   the distortion image's share.  P == 0 or R == 0: nothing is launched.
+ * flags: as the feature entry points (0 | GSR_FLAG_FAST_EXP | GSR_FLAG_ANTIALIAS | GSR_FLAG_TILE_BOUNDS_ALPHA |
+ *   GSR_FLAG_SHARED_SIMDS); any other bit is GSR_ERR_BAD_ARGUMENT.  Arguments are checked before any device work: a NULL
+ *   pointer where one is required, a (near, far) that is neither (0, 0) nor finite with 0 < near < far, a `moments` that is
+ *   not 16-byte aligned and an `acc` that is not 64-byte aligned are GSR_ERR_BAD_ARGUMENT. */
+int gsr_blend_forward_distortion(void* stream, int P, int64_t R, int W, int H, const void* geom, const void* binning,
+                                 void* image, float near, float far, float* out_distortion, float* moments, unsigned flags);
+int gsr_blend_backward_distortion(void* stream, int P, int64_t R, int W, int H, const void* geom, const void* binning,
+                                  const void* image, float near, float far, const float* moments,
+                                  const float* dL_ddistortion, float* acc, unsigned flags);
 
 /* Multi-GPU exchange support (gaussianeditor_amd/multiview.py).  Per view the SH gradient is
  * rank one, dL_dsh[k] = c_k(dir) * dL_dRGB with dir = normalize(mean - campos) (backward.cu:44-98), so ranks exchange
