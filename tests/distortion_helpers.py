@@ -125,8 +125,9 @@ def f64_distortion(f, case, GDist, near_far=None, G=None, with_colour_only=False
     geo = (cam.world_view_transform, cam.full_proj_transform, cam.camera_center)
     tail = (W, H, case["tfx"], case["tfy"], 1.0, case["D"])
     z = f["depths"].astype(np.float64)  # the data: float32 values
-    m, mu = mapped(z, near_far)
     vis = f["radii"] > 0
+    z = np.where(vis, z, 1.0)  # (a culled Gaussian is on no list: its depth, 0 in the oracle's table, must not reach 1 / z)
+    m, mu = mapped(z, near_far)
     c = float(np.median(m[vis])) if vis.any() else 0.0
     mc = torch.from_numpy(m - c)
     moment_colours = torch.stack([torch.ones_like(mc), mc, mc * mc], dim=1)
@@ -174,18 +175,28 @@ def expectation(name, near_far=None, colour=False):
     cpu.build()
     case = get_case(name)
     f = oracle_forward(cpu, case)
-    e = f64_distortion(f, case, weights(case), near_far=near_far, G=colour_weights(case) if colour else None)
+    e, masked = expectation_of(case, f, name, near_far=near_far, colour=colour)
+    return case, f, e, masked
+
+
+def expectation_of(case, f, name, near_far=None, colour=False, GDist=None, lam=None):
+    """`expectation` of any case and its float32 oracle forward `f` -> (f64_distortion(...) with "lam", masked rows).
+    `GDist`: another pixel gradient than weights(case); `lam`: a given weight instead of the one chosen here."""
+    e = f64_distortion(f, case, weights(case) if GDist is None else GDist, near_far=near_far,
+                       G=colour_weights(case) if colour else None)
     e["lam"] = 1.0
     if colour:
-        ratio = float(np.abs(e["colour_only"]["dL_dmeans3D"]).max()) / float(np.abs(e["share"]["dL_dmeans3D"]).max())
-        lam = e["lam"] = 10.0 ** round(math.log10(ratio))
+        if lam is None:
+            ratio = float(np.abs(e["colour_only"]["dL_dmeans3D"]).max()) / float(np.abs(e["share"]["dL_dmeans3D"]).max())
+            lam = 10.0 ** round(math.log10(ratio))
+        e["lam"] = lam
         e["share"] = {k: v * lam for k, v in e["share"].items()}
         e["dL_dz"] = e["dL_dz"] * lam
         e["want"] = {k: e["share"][k] + e["colour_only"][k] for k in e["share"]}
     r = dict(name="distortion:" + name, case=case)
     masked, report = R.masked_rows(r, f, e["stats"])
     print(f"[distortion:{name}] {report}")
-    return case, f, e, masked
+    return e, masked
 
 
 def assert_share_visible(e, tag=""):
