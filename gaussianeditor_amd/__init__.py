@@ -45,6 +45,11 @@ def __getattr__(name: str):
         from . import normals
 
         return getattr(normals, name)
+    # Mip-Splatting's 3D filter (filter3d.py), likewise
+    if name in ("pack_cameras", "compute_3d_filter", "apply_3d_filter", "bake_3d_filter"):
+        from . import filter3d
+
+        return getattr(filter3d, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -173,6 +173,14 @@ SIGNATURES = {
     "gsr_normal_loss_workspace_size": (c_int, [c_int, c_int, POINTER(c_size_t)]),
     "gsr_normal_loss_forward": (c_int, [_P, c_int, c_int] + [ctypes.c_double] * 5 + [_P] * 5),
     "gsr_normal_loss_backward": (c_int, [_P, c_int, c_int] + [ctypes.c_double] * 5 + [_P] * 7),
+    # Mip-Splatting's 3D filter (gaussianeditor_amd/filter3d.py): (P, bytes);
+    # (stream, P, V, means3D, cameras (V,20) f64, f_max, coef, workspace, filter_3D (P,1), valid (P) u8);
+    # (stream, P, from_raw, scales, opacity, filter_3D, scales_eff, opacity_eff);
+    # (stream, P, from_raw, scales, opacity, filter_3D, dL_dscales_eff | NULL, dL_dopacity_eff | NULL, dL_dscales | NULL, dL_dopacity | NULL)
+    "gsr_filter3d_workspace_size": (c_int, [c_int64, POINTER(c_size_t)]),
+    "gsr_filter3d_sweep": (c_int, [_P, c_int64, c_int, _P, _P, ctypes.c_double, ctypes.c_double, _P, _P, _P]),
+    "gsr_filter3d_apply_forward": (c_int, [_P, c_int64, c_int] + [_P] * 5),
+    "gsr_filter3d_apply_backward": (c_int, [_P, c_int64, c_int] + [_P] * 7),
     "gsr_adam_step": (c_int, [_P, c_int, POINTER(AdamTensor), c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P,
                             _P]),
     "gsr_adam_step_rows": (c_int, [_P, c_int, POINTER(AdamTensor), c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P,

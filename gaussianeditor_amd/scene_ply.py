@@ -55,12 +55,17 @@ def load_gaussians_ply(path: str, device="cpu") -> Dict[str, torch.Tensor]:
     scales = np.stack([col(n) for n in scale_names], axis=1)
     rots = np.stack([col(n) for n in rot_names], axis=1)
     t = lambda a: torch.tensor(a, dtype=torch.float, device=device)  # noqa: E731
-    return {"xyz": t(xyz), "f_dc": t(f_dc).transpose(1, 2).contiguous(), "f_rest": t(f_rest).transpose(1, 2).contiguous(),
-            "opacity": t(opacity), "scaling": t(scales), "rotation": t(rots), "max_sh_degree": degree}
+    out = {"xyz": t(xyz), "f_dc": t(f_dc).transpose(1, 2).contiguous(), "f_rest": t(f_rest).transpose(1, 2).contiguous(),
+           "opacity": t(opacity), "scaling": t(scales), "rotation": t(rots), "max_sh_degree": degree}
+    if "filter_3D" in names:  # Mip-Splatting's extra property (gaussianeditor_amd/filter3d.py)
+        out["filter_3D"] = t(col("filter_3D")[..., np.newaxis])
+    return out
 
 
-def save_gaussians_ply(path: str, xyz, f_dc, f_rest, opacity, scaling, rotation) -> None:
-    """`GaussianModel.save_ply` (gaussian_model.py:410-445) for raw (un-activated) tensors of those shapes."""
+def save_gaussians_ply(path: str, xyz, f_dc, f_rest, opacity, scaling, rotation, filter_3D=None) -> None:
+    """`GaussianModel.save_ply` (gaussian_model.py:410-445) for raw (un-activated) tensors of those shapes.  With
+    `filter_3D` (P,1) Mip-Splatting's extra `filter_3D` property follows the rotation columns, as its `save_ply` writes it;
+    `load_gaussians_ply` then returns the key "filter_3D"."""
     pf = _plyfile()
     n = lambda t: t.detach().cpu().numpy().astype(np.float32)  # noqa: E731
     xyz_ = n(xyz)
@@ -69,7 +74,11 @@ def save_gaussians_ply(path: str, xyz, f_dc, f_rest, opacity, scaling, rotation)
     attrs = ["x", "y", "z", "nx", "ny", "nz"] + [f"f_dc_{i}" for i in range(dc.shape[1])] + \
             [f"f_rest_{i}" for i in range(rest.shape[1])] + ["opacity"] + [f"scale_{i}" for i in range(scaling.shape[1])] + \
             [f"rot_{i}" for i in range(rotation.shape[1])]  # construct_list_of_attributes, :396-408
-    table = np.concatenate((xyz_, np.zeros_like(xyz_), dc, rest, n(opacity).reshape(-1, 1), n(scaling), n(rotation)), axis=1)
+    columns = (xyz_, np.zeros_like(xyz_), dc, rest, n(opacity).reshape(-1, 1), n(scaling), n(rotation))
+    if filter_3D is not None:
+        attrs.append("filter_3D")
+        columns += (n(filter_3D).reshape(-1, 1),)
+    table = np.concatenate(columns, axis=1)
     elements = np.empty(xyz_.shape[0], dtype=[(a, "f4") for a in attrs])
     for i, a in enumerate(attrs):
         elements[a] = table[:, i]

@@ -80,7 +80,8 @@ extern "C" {
  * likewise additive: gsr_gaussian_normals_forward / _backward, gsr_depth_normals_forward / _backward,
  * gsr_normal_loss_workspace_size and gsr_normal_loss_forward / _backward (surface normals; nothing existing changed).
  * Then, likewise additive: gsr_blend_forward_distortion and gsr_blend_backward_distortion (the depth-distortion image; no
- * new flag bit, nothing existing changed). */
+ * new flag bit, nothing existing changed).  Then, likewise additive: GSR_FILTER3D_CAMERA_DOUBLES, gsr_filter3d_workspace_size,
+ * gsr_filter3d_sweep and gsr_filter3d_apply_forward / _backward (Mip-Splatting's 3D filter; nothing existing changed). */
 #define GSR_ABI_VERSION 6
 /* The blend backward's accumulator table: GSR_ACC_ROW floats (one 64-byte line) per Gaussian, 64-byte aligned.  Columns:
  *   [GSR_ACC_MEAN2D] .x [+1] .y of dL_dmean2D      (backward.cu:545-546)
@@ -959,6 +960,58 @@ int gsr_normal_loss_forward(void* stream, int H, int W, double fx, double fy, do
 int gsr_normal_loss_backward(void* stream, int H, int W, double fx, double fy, double cx, double cy, double alpha_min,
                              const float* normals, const float* depth, const float* alpha, const float* dL_dloss,
                              float* dL_dnormals, float* dL_ddepth, float* dL_dalpha);
+
+/* ---- Mip-Splatting's 3D smoothing filter: the camera sweep and the fused apply ----
+ * What a scene trained with Mip-Splatting (compute_3D_filter, get_scaling_with_3D_filter, get_opacity_with_3D_filter) needs
+ * next to the 2D filter of GSR_FLAG_ANTIALIAS: a per-Gaussian filter size from the training cameras, folded into scales and
+ * opacity in front of every render.
+ *
+ * (a) The sweep.  means3D (P,3) f32; cameras: V records of GSR_FILTER3D_CAMERA_DOUBLES binary64 ON THE DEVICE, 8-byte
+ *   aligned, packed once by the caller.  With M = the camera's transposed view matrix (the 16 floats the rasterizer takes, row 3
+ *   the translation), W, H its image size and fx = W / (2 tan(FoVx / 2)), fy = H / (2 tan(FoVy / 2)) its focal lengths in
+ *   pixels, a record is
+ *     [3 r + k] = (double)M[r][k], r = 0..3, k = 0..2 | [12] fx | [13] fy | [14] 0.5 W | [15] 0.5 H |
+ *     [16] -0.15 W | [17] 1.15 W | [18] -0.15 H | [19] 1.15 H            (each product one binary64 multiplication).
+ *   All arithmetic is binary64 on the binary32 inputs, one IEEE operation per operator, in exactly this order.  For the row
+ *   (x, y, z) and every camera:
+ *     p_k = ((x M[0][k] + y M[1][k]) + z M[2][k]) + M[3][k], k = 0, 1, 2;   zc = p_2;   zz = max(zc, 0.001);
+ *     u = (p_0 / zz) fx + 0.5 W;   v = (p_1 / zz) fy + 0.5 H;
+ *     the camera sees the row if zc > (double)0.2f (the rasterizer's near plane) and -0.15 W <= u <= 1.15 W and
+ *     -0.15 H <= v <= 1.15 H (bounds inclusive);  then d = min(d, zc).
+ *   valid (P) u8: 1 where at least one camera saw the row.  A row no camera saw takes d = the largest d of the seen rows;
+ *   when no row at all was seen every row takes d = 100000 (Mip-Splatting raises there; nothing here waits for the device
+ *   in order to raise).  filter_3D (P,1) f32 = (float)((d / f_max) coef): the caller passes f_max = the largest fx of ALL
+ *   cameras, whether they saw anything or not, and coef = sqrt(0.2).
+ *   One launch sweeps all cameras, a second small one fills in the unseen rows; the host reads nothing back.  workspace:
+ *   gsr_filter3d_workspace_size bytes of device scratch, 8-byte aligned, zeroed by the call itself (one 64-bit word: the
+ *   maximum, by an integer atomic max on the bits of the positive double -- independent of the order; no float atomics).
+ *
+ * (b) The apply.  scales (P,3), opacity (P,1), filter_3D (P,1) -> scales_eff (P,3), opacity_eff (P,1).  from_raw = 0: the
+ *   inputs are the activated values s, o;  from_raw = 1: they are the raw parameters and s = exp(raw), o = 1 / (1 + exp(-raw)).
+ *   With f = filter_3D of the row and e_k = s_k^2 + f^2:
+ *     s_eff_k = sqrt(e_k);   coef = sqrt((s_0^2 / e_0) (s_1^2 / e_1) (s_2^2 / e_2));   o_eff = o coef.
+ *   At f = 0 coef is exactly 1 and s_eff = s.  The backward, from dL_dscales_eff (P,3) and dL_dopacity_eff (P,1) (either may
+ *   be NULL = zero), writes
+ *     dL_ds_k = dL_ds_eff_k s_k / s_eff_k + dL_do_eff o_eff f^2 / (s_k e_k);   dL_do = dL_do_eff coef
+ *   (no 0 / 0 at f = 0: the cross term is then exactly 0), with from_raw = 1 multiplied by s_k and o (1 - o): the gradient
+ *   of the raw parameters.  Either output may be NULL: it is then not computed (both NULL: nothing is launched).  filter_3D
+ *   gets no gradient.  Everything is recomputed from the inputs (no saved state).  Scales must be positive.
+ *
+ * All four: binary32 in and out, binary64 inside, rounded once at the store; the caller owns every buffer and every output
+ * element is written; the caller's stream, no host synchronisation; the same bits on every run.  P == 0 returns GSR_OK
+ * without a launch.  GSR_ERR_BAD_ARGUMENT, before the device is touched: P < 0 or > 2^31 - 1, V <= 0, f_max not finite and
+ * positive, coef not finite, from_raw outside {0, 1}, a required pointer NULL (P > 0; cameras always), a float pointer that
+ * is not 4-byte aligned, cameras or workspace not 8-byte aligned.  A failed launch is GSR_ERR_HIP and gsr_last_hip_error()
+ * is not updated. */
+#define GSR_FILTER3D_CAMERA_DOUBLES 20
+int gsr_filter3d_workspace_size(int64_t P, size_t* bytes);
+int gsr_filter3d_sweep(void* stream, int64_t P, int V, const float* means3D, const double* cameras, double f_max, double coef,
+                       void* workspace, float* filter_3D, uint8_t* valid);
+int gsr_filter3d_apply_forward(void* stream, int64_t P, int from_raw, const float* scales, const float* opacity,
+                               const float* filter_3D, float* scales_eff, float* opacity_eff);
+int gsr_filter3d_apply_backward(void* stream, int64_t P, int from_raw, const float* scales, const float* opacity,
+                                const float* filter_3D, const float* dL_dscales_eff, const float* dL_dopacity_eff,
+                                float* dL_dscales, float* dL_dopacity);
 
 /* ---- the training loss: fused L1 + SSIM of two images, and its gradient ----
  * Replaces l1_loss / ssim of gaussiansplatting/utils/loss_utils.py:17-63 and the loss line of the reference's trainers,
