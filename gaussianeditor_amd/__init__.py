@@ -50,6 +50,11 @@ def __getattr__(name: str):
         from . import filter3d
 
         return getattr(filter3d, name)
+    # TSDF fusion and mesh extraction (tsdf.py), likewise
+    if name in ("TSDFVolume", "extract_mesh", "save_mesh_ply", "load_mesh_ply"):
+        from . import tsdf
+
+        return getattr(tsdf, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -181,6 +181,16 @@ SIGNATURES = {
     "gsr_filter3d_sweep": (c_int, [_P, c_int64, c_int, _P, _P, ctypes.c_double, ctypes.c_double, _P, _P, _P]),
     "gsr_filter3d_apply_forward": (c_int, [_P, c_int64, c_int] + [_P] * 5),
     "gsr_filter3d_apply_backward": (c_int, [_P, c_int64, c_int] + [_P] * 7),
+    # TSDF fusion and mesh extraction (gaussianeditor_amd/tsdf.py): (stream, nx, ny, nz, origin x y z, voxel_size, V, H, W,
+    # depth (V,1,H,W), alpha | NULL, color (V,3,H,W) | NULL, cameras (V,20) f64, trunc, alpha_min, max_weight, tsdf, weight,
+    # vol_color (3,nx,ny,nz) | NULL); (nx, ny, nz, bytes); (stream, nx, ny, nz, tsdf, weight, workspace, counts_host[2]);
+    # (stream, nx, ny, nz, origin x y z, voxel_size, tsdf, weight, vol_color | NULL, workspace, n_vertices, n_faces,
+    #  vertices (Nv,3), colors (Nv,3) | NULL, faces (Nf,3) i32)
+    "gsr_tsdf_integrate": (c_int, [_P, c_int, c_int, c_int] + [c_float] * 4 + [c_int] * 3 + [_P] * 4
+                           + [ctypes.c_double, ctypes.c_double, c_float] + [_P] * 3),
+    "gsr_tsdf_mesh_workspace_size": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
+    "gsr_tsdf_mesh_count": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, POINTER(c_int64)]),
+    "gsr_tsdf_mesh_emit": (c_int, [_P, c_int, c_int, c_int] + [c_float] * 4 + [_P] * 4 + [c_int64, c_int64] + [_P] * 3),
     "gsr_adam_step": (c_int, [_P, c_int, POINTER(AdamTensor), c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P,
                             _P]),
     "gsr_adam_step_rows": (c_int, [_P, c_int, POINTER(AdamTensor), c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P,

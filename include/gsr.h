@@ -81,7 +81,9 @@ extern "C" {
  * gsr_normal_loss_workspace_size and gsr_normal_loss_forward / _backward (surface normals; nothing existing changed).
  * Then, likewise additive: gsr_blend_forward_distortion and gsr_blend_backward_distortion (the depth-distortion image; no
  * new flag bit, nothing existing changed).  Then, likewise additive: GSR_FILTER3D_CAMERA_DOUBLES, gsr_filter3d_workspace_size,
- * gsr_filter3d_sweep and gsr_filter3d_apply_forward / _backward (Mip-Splatting's 3D filter; nothing existing changed). */
+ * gsr_filter3d_sweep and gsr_filter3d_apply_forward / _backward (Mip-Splatting's 3D filter; nothing existing changed).
+ * Then, likewise additive: gsr_tsdf_integrate, gsr_tsdf_mesh_workspace_size, gsr_tsdf_mesh_count and gsr_tsdf_mesh_emit (TSDF
+ * fusion and mesh extraction; nothing existing changed). */
 #define GSR_ABI_VERSION 6
 /* The blend backward's accumulator table: GSR_ACC_ROW floats (one 64-byte line) per Gaussian, 64-byte aligned.  Columns:
  *   [GSR_ACC_MEAN2D] .x [+1] .y of dL_dmean2D      (backward.cu:545-546)
@@ -1012,6 +1014,67 @@ int gsr_filter3d_apply_forward(void* stream, int64_t P, int from_raw, const floa
 int gsr_filter3d_apply_backward(void* stream, int64_t P, int from_raw, const float* scales, const float* opacity,
                                 const float* filter_3D, const float* dL_dscales_eff, const float* dL_dopacity_eff,
                                 float* dL_dscales, float* dL_dopacity);
+
+/* ---- TSDF fusion of rendered depth and mesh extraction by marching tetrahedra ----
+ * A dense truncated-signed-distance volume on a lattice of nx x ny x nz points, fused from depth images, and the mesh of
+ * its zero level.  Lattice point (i, j, k) sits at origin + voxel_size (i, j, k); its linear index is n = (i ny + j) nz + k
+ * (k fastest).  tsdf (nx,ny,nz) f32 (a fresh volume holds 1), weight (nx,ny,nz) f32 (a fresh volume holds 0), optionally
+ * vol_color (3,nx,ny,nz) f32; the caller owns and initialises them.
+ *
+ * (a) gsr_tsdf_integrate fuses V views, IN ORDER, in one launch: depth (V,1,H,W) f32, alpha (V,1,H,W) f32 | NULL, color
+ *   (V,3,H,W) f32 | NULL (given exactly when vol_color is), cameras: V records of GSR_FILTER3D_CAMERA_DOUBLES binary64 on the
+ *   device, the layout of gsr_filter3d_sweep, of which [0..11] (the view rows M) and [12] fx, [13] fy are read; the image
+ *   size is the W, H of the call.  Projection and comparisons are binary64 on the binary32 inputs, the running average is
+ *   binary32; one IEEE operation per operator in exactly this order.  With cx = ((double)W - 1) 0.5, cy = ((double)H - 1) 0.5
+ *   (the rasterizer's pixel centres, ndc2Pix) and the point x_c = (double)origin_c + (double)voxel_size (double)index_c,
+ *   per lattice point and per view:
+ *     1. p_k = ((x M[0][k] + y M[1][k]) + z M[2][k]) + M[3][k], k = 0, 1, 2;  zc = p_2;  skip unless zc > (double)0.2f;
+ *     2. u = (p_0 / zc) fx + cx;  v = (p_1 / zc) fy + cy;
+ *     3. iu = floor(u + 0.5), iv = floor(v + 0.5);  skip unless 0 <= iu < W and 0 <= iv < H;
+ *     4. d = depth[iv][iu];  with alpha: a = alpha[iv][iu], skip if (double)a < alpha_min, else d = d / a (binary32);
+ *        skip unless d > 0;
+ *     5. sdf = (double)d - zc;  skip if sdf < -trunc;  obs = (float)min(sdf / trunc, 1);
+ *     6. w1 = w + 1;  tsdf = (tsdf w + obs) / w1, and color_c = (color_c w + pixel_c) / w1 for the three channels;
+ *        if max_weight > 0: w1 = min(w1, max_weight);  w = w1                                   (all binary32).
+ *   A lattice point's state stays in registers over all V views and is stored once, so a call with V views gives the bits of
+ *   V calls with one view each.  No atomics; the same bits on every run.
+ *   GSR_ERR_BAD_ARGUMENT, before the device is touched: an extent < 1, nx ny nz > 2^31 - 1, V < 1, W or H < 1, V H W >
+ *   2^31 - 1, voxel_size, trunc or alpha_min not finite and positive, max_weight negative or not finite, origin not finite,
+ *   a required pointer NULL, color given without vol_color or the reverse, a float pointer not 4-byte aligned, cameras not
+ *   8-byte aligned.
+ *
+ * (b) Mesh extraction, marching tetrahedra on the same lattice.  A point is inside iff tsdf < 0 and observed iff weight > 0.
+ *   Cube (i, j, k), i < nx - 1, j < ny - 1, k < nz - 1, is cut into the six Kuhn tetrahedra, one per axis permutation in the
+ *   order xyz, xzy, yxz, yzx, zxy, zyx:  v0 = the corner, v1 = v0 + e_pi1, v2 = v1 + e_pi2, v3 = corner + (1,1,1) ("path
+ *   order").  A tetrahedron emits nothing unless all four points are observed.  One point a inside (or, mirrored, one
+ *   outside), the others b < c < d in path order: the triangle over the edges (a,b), (a,c), (a,d).  Two inside a < b, two
+ *   outside c < d: the quad q0 = (a,c), q1 = (a,d), q2 = (b,d), q3 = (b,c) as the triangles (q0,q1,q2), (q0,q2,q3).  Where the
+ *   6 x 16 orientation table (tetrahedron, case; built at compile time in integers from the edge midpoints, never from the
+ *   values) says so, a triangle (A,B,C) is emitted as (A,C,B): every normal points to the outside (positive) half.
+ *   A vertex lives on a lattice edge from a lower point in one of the 7 directions d, kinds 0..6 = 100, 010, 001, 110, 101,
+ *   011, 111 (as dx dy dz), with key 7 n(lower) + kind.  With f0, f1 the values at the lower and the upper point, in binary32:
+ *     t = f0 / (f0 - f1);  position_c = origin_c + voxel_size ((float)lower_c + t d_c);  color_c = c0 + t (c1 - c0).
+ *   Vertex ids are the ranks of the used keys in ascending order; faces are ordered by (n of the cube's corner, tetrahedron,
+ *   triangle); every vertex is referenced by a face.
+ *   gsr_tsdf_mesh_count marks the used edges, counts the faces per cube, scans, and returns counts_host[0] = vertices,
+ *   counts_host[1] = faces after ONE host synchronisation of `stream` (the caller sizes the outputs by them).
+ *   gsr_tsdf_mesh_emit, with the SAME workspace untouched in between and the same volume, fills vertices (n_vertices,3) f32,
+ *   colors (n_vertices,3) f32 | NULL (needs vol_color) and faces (n_faces,3) i32; no host synchronisation.  With both counts
+ *   0 nothing is launched and the pointers may be NULL.  workspace: gsr_tsdf_mesh_workspace_size bytes, 256-byte aligned.
+ *   Integer atomics only (an OR of marks: independent of the order); the same bits on every run.
+ *   GSR_ERR_TOO_MANY: 7 nx ny nz >= 2^31 (the keys are 31-bit) or more than 2^31 - 1 faces.  GSR_ERR_BAD_ARGUMENT, before the
+ *   device is touched: an extent < 1, a required pointer NULL, a misaligned pointer, voxel_size or origin not finite,
+ *   negative counts.
+ * A failed launch is GSR_ERR_HIP and gsr_last_hip_error() is not updated. */
+int gsr_tsdf_integrate(void* stream, int nx, int ny, int nz, float origin_x, float origin_y, float origin_z, float voxel_size,
+                       int V, int H, int W, const float* depth, const float* alpha, const float* color, const double* cameras,
+                       double trunc, double alpha_min, float max_weight, float* tsdf, float* weight, float* vol_color);
+int gsr_tsdf_mesh_workspace_size(int nx, int ny, int nz, size_t* bytes);
+int gsr_tsdf_mesh_count(void* stream, int nx, int ny, int nz, const float* tsdf, const float* weight, void* workspace,
+                        int64_t* counts_host);
+int gsr_tsdf_mesh_emit(void* stream, int nx, int ny, int nz, float origin_x, float origin_y, float origin_z, float voxel_size,
+                       const float* tsdf, const float* weight, const float* vol_color, const void* workspace,
+                       int64_t n_vertices, int64_t n_faces, float* vertices, float* colors, int32_t* faces);
 
 /* ---- the training loss: fused L1 + SSIM of two images, and its gradient ----
  * Replaces l1_loss / ssim of gaussiansplatting/utils/loss_utils.py:17-63 and the loss line of the reference's trainers,
